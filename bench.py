@@ -3,10 +3,12 @@
 loss + backward, gradient sync + clip + AdamW on every 2nd micro-step as in
 config/train-tvr-8gpu.json) on synthetic TVR-shaped batches, one process per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for every field).
+Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for every field).  A plain run sets up, warms up, times the
+K steps and prints the line; `--full` adds everything else the line can carry (box probes, the roofline leg and its
+counters, cpu_baseline, the secondary workloads at N = 1, the comm block at N > 1).
 """
 import argparse
 import ctypes as C
@@ -114,6 +116,48 @@ def build_pretraining_model(device, cfg_path):
     return model
 
 
+_CFG_DIR = []
+
+
+def config_file(cfg, tag):
+    """`cfg` as a JSON file in a temporary directory of this process's own (from_pretrained reads a path); a fixed name
+    under /tmp could belong to another user or another run."""
+    import atexit
+    import shutil
+    import tempfile
+    if not _CFG_DIR:
+        _CFG_DIR.append(tempfile.mkdtemp(prefix="hero_bench_"))
+        atexit.register(shutil.rmtree, _CFG_DIR[0], True)
+    path = os.path.join(_CFG_DIR[0], "%s.json" % tag)
+    with open(path, "w") as f:
+        json.dump(cfg, f)
+    return path
+
+
+DUMP_SAMPLE = 1 << 21          # elements drawn from the parameters and from their gradients (8 MB each in fp32)
+
+
+def dump_outputs(out_dir, model, loss, prefix=""):
+    """What the timed path handed its caller in its last micro-step, as float .npy files under `out_dir`:
+    `loss` (the micro-step's loss, float64 [1]), and a fixed, seeded sample (DUMP_SAMPLE positions, the same in every run
+    of the same model) of the fp32 master parameters the step updated in place (`params_sample`) and of their gradients
+    as the step left them (`grads_sample`: all zeros after a micro-step that ended with the optimiser step).  Positions
+    index the concatenation of model.parameters() in order, flattened."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = list(model.parameters())
+    total = sum(p.numel() for p in params)
+    idx = torch.randint(0, total, (min(DUMP_SAMPLE, total),), generator=torch.Generator().manual_seed(0)).sort().values
+    idx = idx.to(params[0].device)
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+        np.save(os.path.join(out_dir, prefix + "params_sample.npy"), flat[idx].cpu().numpy().astype(np.float32))
+        flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+        np.save(os.path.join(out_dir, prefix + "grads_sample.npy"), flat[idx].cpu().numpy().astype(np.float32))
+        del flat
+    np.save(os.path.join(out_dir, prefix + "loss.npy"), np.array([float(loss)], dtype=np.float64))
+
+
 def cpu_baseline(model, cfg, sample_videos=32, reps=3, threads=16):
     """The CPU oracle (kind 'port': verified == reference in tests/test_oracle_golden.py) timed on
     this box's host cores on the SAME workload: the full 32-video D2 batch (rounds 1-3 timed a 16-video
@@ -148,8 +192,9 @@ def cpu_baseline(model, cfg, sample_videos=32, reps=3, threads=16):
                       "median %.2f s" % ("the full" if sample_videos == 32 else "a slice of the", sample_videos, reps, med)}
 
 
-def _timed(trainer, batch, task, steps, warmup, world):
-    """prepare (untimed) + warm-up + `steps` micro-steps bracketed by barrier + synchronise; max over ranks."""
+def _timed(trainer, batch, task, steps, warmup, world, dump=None, prefix=""):
+    """prepare (untimed) + warm-up + `steps` micro-steps bracketed by barrier + synchronise; max over ranks.  dump: a
+    directory that receives the last micro-step's outputs (dump_outputs) after the timed region."""
     def sync():
         torch.cuda.synchronize()
         if torch.distributed.is_initialized():
@@ -168,6 +213,8 @@ def _timed(trainer, batch, task, steps, warmup, world):
         t = torch.tensor([dt], device=batch["c_v_feats"].device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if dump:
+        dump_outputs(dump, trainer.model, loss, prefix)
     return dt, float(loss)
 
 
@@ -184,15 +231,13 @@ def secondary_workload(args, device, world, rank, steps=None, warmup=None):
     base = {"unit": "videos/s", "n_gpus": world, "steps": steps, "warmup": warmup, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if args.dtype == "bf16" else "f32",
             "data": "synthetic"}
-    cfg_path = "/tmp/hero_bench_%s_%d.json" % (args.workload, rank)
+    dump = getattr(args, "dump_outputs", None) if rank == 0 else None
 
     if args.workload == "D2r":
-        with open(cfg_path, "w") as f:
-            json.dump(cfg, f)
-        model = build_model(device, cfg_path)
+        model = build_model(device, config_file(cfg, "D2r"))
         batch = make_batch("D2", vfeat_dim=VFEAT, vocab=50272, seed=1 + rank, device=device, ragged=True)
         trainer = TrainStep(model, use_graph=graph, static_usage=True)
-        dt, loss = _timed(trainer, batch, None, steps, warmup, world)
+        dt, loss = _timed(trainer, batch, None, steps, warmup, world, dump)
         B = batch["c_v_feats"].shape[0]
         vps = B * world * steps / dt
         fl = algorithmic_flops_of_batch({k: (v.cpu() if torch.is_tensor(v) else v) for k, v in batch.items()})
@@ -210,9 +255,7 @@ def secondary_workload(args, device, world, rank, steps=None, warmup=None):
                    peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
     elif args.workload == "D3":
         cfg["f_config"]["vocab_size"] = 50265                      # config/hero_pretrain.json; pad_vocab() -> 50272
-        with open(cfg_path, "w") as f:
-            json.dump(cfg, f)
-        model = build_model(device, cfg_path, pretraining=True)
+        model = build_model(device, config_file(cfg, "D3"), pretraining=True)
         batches = make_pretrain_batches("D2", vfeat_dim=VFEAT, vocab=50265, seed=1 + rank, device=device)
         opts = dict(learning_rate=3e-5, gradient_accumulation_steps=2)      # config/pretrain-tv-16gpu.json:33-34
         trainer = TrainStep(model, opts=opts, task="vsm", use_graph=graph)
@@ -220,7 +263,7 @@ def secondary_workload(args, device, world, rank, steps=None, warmup=None):
         B = SHAPES["D2"]["videos"]
         per_task, t_mix, losses = {}, 0.0, {}
         for task, w in mix.items():                                         # fixed schedule, one task per window
-            dt, losses[task] = _timed(trainer, batches[task], task, steps, warmup, world)
+            dt, losses[task] = _timed(trainer, batches[task], task, steps, warmup, world, dump, task + "_")
             per_task[task] = {"videos_per_s": round(B * world * steps / dt, 2), "ms_per_step": round(dt / steps * 1e3, 3)}
             t_mix += w * dt / steps
         vps = sum(mix.values()) * B * world / t_mix
@@ -235,9 +278,7 @@ def secondary_workload(args, device, world, rank, steps=None, warmup=None):
                    per_task=per_task, final_loss=losses,
                    peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
     else:   # D4
-        with open(cfg_path, "w") as f:
-            json.dump(cfg, f)
-        model = build_model(device, cfg_path)
+        model = build_model(device, config_file(cfg, "D4"))
         trainer = TrainStep(model, use_graph=False, static_usage=True)
         total = torch.cuda.get_device_properties(device).total_memory
         B = args.videos
@@ -255,7 +296,7 @@ def secondary_workload(args, device, world, rank, steps=None, warmup=None):
             try:
                 torch.cuda.reset_peak_memory_stats()
                 batch = make_batch("D4", vfeat_dim=VFEAT, vocab=50272, seed=1 + rank, device=device, videos=B)
-                dt, loss = _timed(trainer, batch, None, steps, warmup, world)
+                dt, loss = _timed(trainer, batch, None, steps, warmup, world, dump)
                 break
             except torch.OutOfMemoryError:
                 batch = None
@@ -285,10 +326,7 @@ def feed_run(device, rank, steps, warmup, n_batches=4):
     from hero_amd.loader import StaticBatchFeeder, pin_batch
     from hero_amd.step import TrainStep
     from hero_amd.synth import SHAPES, make_batch
-    cfg_path = "/tmp/hero_bench_feed_%d.json" % rank
-    with open(cfg_path, "w") as f:
-        json.dump(HERO_BASE, f)
-    model = build_model(device, cfg_path)
+    model = build_model(device, config_file(HERO_BASE, "feed"))
     trainer = TrainStep(model, use_graph=True, static_usage=True, uniform_shapes=True)
     host = [pin_batch(make_batch("D2", vfeat_dim=VFEAT, vocab=50272, seed=1 + rank + 100 * i)) for i in range(n_batches)]
     feeder = StaticBatchFeeder(host[0], device)
@@ -325,10 +363,7 @@ def feed_ragged_run(device, rank, steps, warmup, n_batches=8, n_buckets=3):
     from hero_amd.loader import BucketedBatchFeeder, batch_dims, pin_batch
     from hero_amd.step import TrainStep
     from hero_amd.synth import SHAPES, make_batch
-    cfg_path = "/tmp/hero_bench_feedr_%d.json" % rank
-    with open(cfg_path, "w") as f:
-        json.dump(HERO_BASE, f)
-    model = build_model(device, cfg_path)
+    model = build_model(device, config_file(HERO_BASE, "feed_ragged"))
     trainer = TrainStep(model, use_graph=True, static_usage=True, uniform_shapes=True)
     raw = [make_batch("D2", vfeat_dim=VFEAT, vocab=50272, seed=1 + rank + 100 * i, ragged=True) for i in range(n_batches)]
     dims = [batch_dims(b) for b in raw]
@@ -454,7 +489,7 @@ def box_probe(device):
 
 
 def launch_command(n, argv, n_devices, port=None):
-    """The command (and extra environment) `python bench.py --gpus N` turns itself into when N > 1 and no launcher has
+    """The command (and extra environment) `python bench.py --gpus N` starts as a child when N > 1 and no launcher has
     set WORLD_SIZE: one process per GPU under torch.distributed.run on 127.0.0.1, exactly what the driver's own N > 1
     command line is.  On a box with fewer than N GPUs the ranks share device 0 and talk over gloo (RCCL refuses two
     ranks on one device): a PLUMBING run - process group, broadcast, bucketed exchange, negatives, max-over-ranks
@@ -481,7 +516,10 @@ def self_launch(args):
         raise SystemExit("bench.py: no GPU visible (the hot path has no CPU fallback)")
     cmd, env = launch_command(args.gpus, sys.argv[1:], n_dev)
     sys.stdout.flush()
-    os.execve(cmd[0], cmd, dict(os.environ, **env))
+    # the launcher runs as a child: this process has already initialised the GPU runtime (device_count), so it waits for
+    # the ranks and leaves with their exit status instead of replacing itself
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=dict(os.environ, **env)))
 
 
 def main():
@@ -513,6 +551,15 @@ def main():
     ap.add_argument("--exchange", default="torch", choices=["torch", "abi"],
                     help="N > 1: what carries the device collectives - torch.distributed's process group (default, DESIGN 6) or "
                          "hero_comm_* of the C ABI (RCCL on a side stream of this process)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: the box probes (`box`), the roofline leg and its "
+                         "counters (`roofline`), `cpu_baseline`, at N = 1 the short D2r / D3 / D4 / feed runs (`secondary`), at "
+                         "N > 1 the cost of the gradient exchange (`comm`); the --no-* switches above thin a --full run out.  "
+                         "Without it those fields are null and the run only sets up, warms up, times --steps micro-steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed micro-step handed back (its loss, a fixed seeded "
+                         "sample of the updated parameters and of their gradients) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.steps is None:                           # 20 steps were a 0.125 s timed region
         args.steps = 20 if args.workload == "D4" else 200
@@ -555,15 +602,12 @@ def main():
             torch.distributed.destroy_process_group()
         return
     box = None
-    if not args.no_box_probe:
+    if args.full and not args.no_box_probe:
         try:
             box = box_probe(device)                  # every rank probes its own GPU (rank 0's goes on the line)
         except Exception as e:                       # noqa: BLE001 - a probe never takes the headline down
             box = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
-    cfg_path = "/tmp/hero_finetune_bench_%d.json" % rank
-    with open(cfg_path, "w") as f:
-        json.dump(HERO_BASE, f)
-    model = build_model(device, cfg_path)
+    model = build_model(device, config_file(HERO_BASE, "D2"))
     # drop_svmr_prob = 0: every step uses the same parameters; every rank's batch has the same shape.
     # N = 1: the step is captured in hipGraphs and replayed.  N > 1: the eager run (RCCL all-reduces issued from the
     # backward hooks) is timed FIRST - it is the mode every multi-rank test covers - and then, unless HERO_DP_GRAPH=0,
@@ -617,6 +661,8 @@ def main():
         return dt_, float(loss_)
 
     dt, loss_val = timed_run()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss_val)
     graph_mode = trainer.use_graph
     # (the captured run needs device-side collectives: over gloo - the plumbing run - they are host-staged and cannot be captured)
     try_graph = (dist_on and not args.no_graph and os.environ.get("HERO_DP_GRAPH", "1") not in ("", "0")
@@ -625,7 +671,7 @@ def main():
 
     # ---- N > 1: what the collectives cost, so that the line itself shows that RCCL saw N ranks ---------------------
     comm = None
-    if dist_on:
+    if dist_on and args.full:
         accum = trainer.opts.gradient_accumulation_steps
         ones = torch.ones(1, device=device)
         torch.distributed.all_reduce(ones)                                 # every rank contributes a 1
@@ -655,7 +701,7 @@ def main():
 
     # ---- roofline leg: HIP events around every GEMM launch over extra, identical steps ----------
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         L.check(L.lib().hero_prof_enable(1))
         trainer.use_graph = False                    # events cannot be recorded inside a replay
         for _ in range(args.profile_steps):
@@ -723,11 +769,11 @@ def main():
                     "clock_ghz": box.get("mfma_clock_ghz") if box else None,
                     "counters_source": live[2] if live else
                     "profiles/%s + profiles/%s (rocprofv3 --pmc passes of this command, committed)" % (PROFILE_TRAFFIC, PROFILE_MFMA)}
-    elif world > 1:
+    elif world > 1 and args.full:
         for _ in range(args.profile_steps):
             trainer.micro_step(batch)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(model, HERO_BASE)
 
     def line(dt_, loss_, launch_mode):
@@ -760,7 +806,7 @@ def main():
         }
 
     out = line(dt, loss_val, "hipGraph replay" if graph_mode else "eager")
-    hard_exit = False
+    hard_exit = graph_won = False
     if try_graph:
         # Second measured run of the same K steps: the step captured WITH its RCCL collectives.  A watchdog prints the
         # eager line and leaves if the captured run does not come back (a wedged collective cannot be recovered from
@@ -789,6 +835,7 @@ def main():
             if dt_g < dt and loss_g == loss_g:
                 out = line(dt_g, loss_g, "hipGraph replay (step captured with its RCCL collectives)")
                 out["config"]["eager_ms_per_step"] = round(eager_ms, 3)
+                graph_won = True
             else:
                 out["config"]["graph_ms_per_step"] = round(dt_g / args.steps * 1e3, 3)
         except Exception as e:                       # noqa: BLE001 - any capture failure: the eager measurement stands
@@ -796,12 +843,15 @@ def main():
             hard_exit = True                         # the process group may be unusable: no orderly teardown
         finished.set()
         timer.cancel()
+        if graph_won and args.dump_outputs and rank == 0:       # the reported run's outputs replace the eager run's
+            dump_outputs(args.dump_outputs, model, loss_g)
     # ---- N = 1: the other configurations ride on the line (short runs, after everything that is timed above) -------
-    if rank == 0 and world == 1 and not dist_on and not args.no_secondary and not args.feed:
+    if rank == 0 and world == 1 and not dist_on and args.full and not args.no_secondary and not args.feed:
         del trainer, model, batch
         _forget_previous_models()
         sec, t_sec = {}, time.perf_counter()
         ns = argparse.Namespace(**vars(args))
+        ns.dump_outputs = None                           # the outputs are the headline run's
         for w in ("D2r", "D3", "D4"):
             try:
                 ns.workload = w

@@ -15,7 +15,7 @@ import pytest
 import torch
 
 from oracle import hero_oracle as O
-from tests.util import rel_err, to_dev
+from tests.util import config_file, rel_err, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -56,9 +56,7 @@ def hero_base(seed=0, cls=None, **head):
     from hero_amd.model import HeroForVcmr
     from hero_amd.utils.misc import set_dropout
     HeroForVcmr = cls or HeroForVcmr
-    path = "/tmp/hero_base_small_vocab_cfg.json"
-    with open(path, "w") as f:
-        json.dump(HERO_BASE, f)
+    path = config_file(HERO_BASE, "hero_base_small_vocab_cfg.json")
     torch.manual_seed(seed)
     args = dict(lw_neg_ctx=8.0, lw_neg_q=8.0, lw_st_ed=0.01, ranking_loss_type="hinge", use_hard_negative=False,
                 hard_pool_size=20, margin=0.1, use_all_neg=True, drop_svmr_prob=0.0)
@@ -516,9 +514,7 @@ def test_hero_base_bf16_full_vocabulary_mlm_loss_and_tied_embedding_gradient():
     HF.clear_weight_cache()
     cfg_d = json.loads(json.dumps(HERO_BASE))
     cfg_d["f_config"]["vocab_size"] = cfg_d["q_config"]["vocab_size"] = 50265
-    path = "/tmp/hero_base_full_vocab_cfg.json"
-    with open(path, "w") as f:
-        json.dump(cfg_d, f)
+    path = config_file(cfg_d, "hero_base_full_vocab_cfg.json")
     torch.manual_seed(0)
     model = HeroForPretraining.from_pretrained(path, {}, vfeat_dim=4352, max_frm_seq_len=100, lw_neg_ctx=8.0, lw_neg_q=8.0,
                                                lw_st_ed=0.01, ranking_loss_type="hinge", use_hard_negative=False,

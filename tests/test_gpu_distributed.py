@@ -54,14 +54,14 @@ def test_two_ranks_several_queries_per_video_fused_head(tmp_path):
 
 
 def test_bench_plain_command_launches_two_ranks_on_one_device():
-    """`python bench.py --gpus 2` as a PLAIN command (no launcher, no WORLD_SIZE): bench.py re-executes itself under
+    """`python bench.py --gpus 2` as a PLAIN command (no launcher, no WORLD_SIZE): bench.py runs itself under
     torch.distributed.run (one process per rank on 127.0.0.1 - the driver's own N > 1 command line, which
     test_bench_one_rank_over_rccl covers as such); on this 1-GPU box both ranks share the device and talk over gloo, and the
     line says it is a plumbing run.  Covered end to end: process-group setup, parameter broadcast, bucketed bf16 gradient
     all-reduce overlapped with backward, cross-rank negatives, max-over-ranks timing, the one JSON line on rank 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "HERO_BENCH_ONE_DEVICE",
                                                             "HERO_BENCH_BACKEND", "HERO_DP_FORCE_COLLECTIVES")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -122,7 +122,7 @@ def test_bench_one_rank_over_rccl_captured_in_a_hipgraph():
         env = dict(base, HERO_DP_GRAPH=mode)
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                "--master-addr", "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"),
-               "--gpus", "1", "--steps", "8", "--warmup", "2", "--no-cpu-baseline"]
+               "--gpus", "1", "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--full"]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
         res[mode] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -147,7 +147,7 @@ def test_bench_wedged_capture_falls_back_to_the_eager_line():
                HERO_DP_GRAPH_TEST_WEDGE="1", HERO_DP_GRAPH_TIMEOUT="5")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", "29557", os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"]
+           "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -229,7 +229,7 @@ def test_bench_one_rank_exchange_through_the_c_abi_captured_in_a_hipgraph():
                HERO_DP_GRAPH="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", "29563", os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--exchange", "abi"]
+           "--gpus", "1", "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--exchange", "abi", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

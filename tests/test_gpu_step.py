@@ -210,3 +210,33 @@ def test_multi_task_graph_replay_keeps_per_parameter_adam_steps():
     assert sg == se, {k: (sg[k], se[k]) for k in se if sg.get(k) != se[k]}
     for k in (only_mlm, only_vsm, both):
         assert rel_err(pg[k], pe[k]) < 5e-4, (k, rel_err(pg[k], pe[k]))
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline fields for exactly K timed steps,
+    none of the `--full` blocks, and the last timed micro-step's outputs in DIR (float .npy files, 64 MB at most, its loss
+    the line's `final_loss`)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+           "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 6 and out["warmup"] == 2 and out["n_gpus"] == 1 and out["dtype"] == "bf16"
+    assert out["unit"] == "videos/s" and out["higher_is_better"] is True and out["config"]["launch"] == "hipGraph replay"
+    assert out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] / 1e3 - 32) < 0.05     # 32 videos per step
+    assert out["box"] is None and out["roofline"] is None and out["cpu_baseline"] is None and "secondary" not in out
+    names = sorted(os.listdir(out_dir))
+    assert names == ["grads_sample.npy", "loss.npy", "params_sample.npy"]
+    assert sum(os.path.getsize(out_dir / n) for n in names) <= 64 << 20
+    arrays = {n: np.load(out_dir / n) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert float(arrays["loss.npy"][0]) == out["final_loss"]
+    assert arrays["params_sample.npy"].size > 1000 and arrays["params_sample.npy"].std() > 0

@@ -1,5 +1,9 @@
 """Shared helpers for the parity tests (fixtures -> hero_amd models / device batches)."""
+import atexit
+import json
 import os
+import shutil
+import tempfile
 
 import torch
 
@@ -20,6 +24,21 @@ def load_tiny(device, cls=None, **kw):
                                                  {k: v.clone() for k, v in P.items()},
                                                  vfeat_dim=vfeat, max_frm_seq_len=max_frm, **args)
     return model.to(device), P, O.cfg_from_json(cfgj)
+
+
+_CFG_DIR = []
+
+
+def config_file(cfg, name):
+    """`cfg` as a JSON file in a temporary directory of this process's own (from_pretrained reads a path; a fixed name
+    under /tmp could belong to another user or another run)."""
+    if not _CFG_DIR:
+        _CFG_DIR.append(tempfile.mkdtemp(prefix="hero_tests_"))
+        atexit.register(shutil.rmtree, _CFG_DIR[0], True)
+    path = os.path.join(_CFG_DIR[0], name)
+    with open(path, "w") as f:
+        json.dump(cfg, f)
+    return path
 
 
 def elem_rel_err(a, b, mask=None):

@@ -21,8 +21,8 @@ python tools/lab/graph_gaps.py $OUT/${TAG}_gaps > $OUT/${TAG}_graph_gaps.txt 2>&
 find $OUT/${TAG}_gaps -name "*kernel_trace.csv" -delete
 # the line reads its counters from profiles/ (stamped with the kernel-source hash): the passes of THIS call
 cp $OUT/${TAG}_pmc_traffic.json $OUT/${TAG}_pmc_mfma.json profiles/
-(timeout 600 python bench.py --steps 20 --warmup 4) > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
-(timeout 600 python bench.py --steps 20 --warmup 4 --feed 4 --no-cpu-baseline | tail -1) > $OUT/${TAG}_bench_feed.json 2>> $OUT/${TAG}_bench.err
+(timeout 600 python bench.py --steps 20 --warmup 4 --full) > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+(timeout 600 python bench.py --steps 20 --warmup 4 --feed 4 --no-cpu-baseline --full | tail -1) > $OUT/${TAG}_bench_feed.json 2>> $OUT/${TAG}_bench.err
 for w in D2r D3 D4; do
   timeout 400 python bench.py --workload $w --no-cpu-baseline 2> $OUT/${TAG}_$w.err | tail -1 > $OUT/${TAG}_bench_$w.json
 done
