@@ -21,8 +21,8 @@ arrays and derives, with kernels, in place, into buffers of fixed capacity:
 
 Because the outputs keep their addresses, a hipGraph captured on one batch replays on the next batch of
 the same SHAPE after `update()` + `hero_amd.functional.refresh_memo()` (tests/test_gpu_collate.py).
-The packed (variable-length) formulation of ragged batches changes the GEMM row counts with the batch
-and therefore stays an eager-mode feature.
+The packed (variable-length) formulation of ragged batches replays too when the batch's feeder owns a pack plan
+of fixed row capacity (hero_amd.loader.StaticBatchFeeder(packed_rows=...), BertEncoder.register_static_plan).
 """
 import numpy as np
 import torch

@@ -852,7 +852,22 @@ def _as2d(x):
     return x.view(-1, x.shape[-1])
 
 
+class _MemoEntry:
+    """One memoised derived tensor: `out` = fn() of `sources`, found under `key` (identity + version of the sources).  `seq`
+    is its creation number: an entry is created after the tensors it derives from, so creation order is dependency order."""
+    __slots__ = ("tag", "extra", "sources", "out", "fn", "spec", "key", "seq")
+
+    def __init__(self, tag, extra, sources, out, fn, spec, key, seq):
+        self.tag, self.extra, self.sources, self.out, self.fn, self.spec, self.key, self.seq = \
+            tag, extra, sources, out, fn, spec, key, seq
+
+
 _MEMO = {}
+_MEMO_SEQ = 0           # creation number of the next entry
+
+
+def _memo_key(tag, extra, tensors):
+    return (tag, extra) + tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype) for t in tensors)
 
 
 def memo(tag, tensors, fn, extra=(), spec=None):
@@ -862,10 +877,11 @@ def memo(tag, tensors, fn, extra=(), spec=None):
     dozen tiny launches each time.  The sources are kept alive so their addresses stay unique.
     spec = (L.DERIVE_* mode, p0, p1, p2): the entry is an elementwise function of ONE contiguous int64 source that
     hero_derive_multi computes - refresh_memo then redoes all such entries in one launch."""
-    key = (tag, extra) + tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype) for t in tensors)
+    global _MEMO_SEQ
+    key = _memo_key(tag, extra, tensors)
     hit = _MEMO.get(key)
     if hit is not None:
-        return hit[0]
+        return hit.out
     if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
         # A miss while a hipGraph is being captured is computed INSIDE that graph and not remembered: a remembered entry would
         # live in the graph's private pool and be found - not recomputed - by the next capture (TrainStep records a plain
@@ -878,7 +894,8 @@ def memo(tag, tensors, fn, extra=(), spec=None):
     if spec is not None and not (len(tensors) == 1 and tensors[0].dtype == torch.int64 and tensors[0].is_contiguous()
                                  and tensors[0].is_cuda and out.is_contiguous() and out.numel() == tensors[0].numel()):
         spec = None
-    _MEMO[key] = (out, tensors, fn, spec)
+    _MEMO[key] = _MemoEntry(tag, extra, tensors, out, fn, spec, key, _MEMO_SEQ)
+    _MEMO_SEQ += 1
     return out
 
 
@@ -888,10 +905,12 @@ def reset_caches():
     optimiser step), memoised batch tensors, workspaces, weight-gradient plans, the gradient sink.  For processes that build
     several models in a row (bench.py's secondary workloads: each would otherwise pay for its predecessors' copies).
     Not while a captured hipGraph that references those buffers is still going to be replayed."""
+    global _MEMO_SEQ
     clear_weight_cache()
     _REFRESH.clear()
     _REFRESH_PINNED.clear()
     _MEMO.clear()
+    _MEMO_SEQ = 0
     _WS.clear()
     _WPLANS.clear()
     _WPLANS_PINNED.clear()
@@ -912,20 +931,16 @@ def host_sortable_orders(batch):
     re-sorting on the device inside every commit (hero_segment_sort is one workgroup: 69 us for 9600 ids)."""
     # by address (callers pass views, idx.view(-1)) - and ONLY the plain int32 casts of a batch tensor (`row_index`, spec
     # DERIVE_I32): an index derived any other way (a flat gather map ...) must keep its device sort (ADVICE r5)
-    by_out = {v[0].data_ptr(): v for k_, v in _MEMO.items()
-              if isinstance(v[0], torch.Tensor) and k_[0] == "row_index" and v[3] is not None and v[3][0] == L.DERIVE_I32}
+    ids_of = {e.out.data_ptr(): e.sources[0].data_ptr() for e in _MEMO.values()
+              if e.tag == "row_index" and e.spec is not None and e.spec[0] == L.DERIVE_I32}
     keys = {t.data_ptr(): k for k, t in batch.items() if torch.is_tensor(t) and t.dtype == torch.int64}
     found = []
-    for mk, (out, srcs, fn, spec) in _MEMO.items():
-        if mk[0] != "seg_order" or len(srcs) != 1:
+    for e in sorted(_MEMO.values(), key=lambda e: e.seq):
+        if e.tag != "seg_order" or len(e.sources) != 1:
             continue
-        ridx = by_out.get(srcs[0].data_ptr())                  # the int32 row index the order was sorted from ...
-        if ridx is None or len(ridx[1]) != 1:
-            continue
-        ids = ridx[1][0]                                       # ... itself derived from this int64 tensor
-        k = keys.get(ids.data_ptr())
-        if k is not None and batch[k].numel() == out.numel():
-            found.append((k, out, int(mk[1][1])))
+        k = keys.get(ids_of.get(e.sources[0].data_ptr()))    # the int64 tensor the order's int32 row index was cast from
+        if k is not None and batch[k].numel() == e.out.numel():
+            found.append((k, e.out, int(e.extra[1])))
     return found
 
 
@@ -940,76 +955,53 @@ def refresh_memo(sources=None, skip_outputs=()):
     """Recompute memoised derived tensors IN PLACE from the current contents of their sources.  For callers that
     rewrite batch buffers in place (hero_amd.collate.DeviceCollate, or new data copied into a captured batch):
     captured graphs and cached maps hold the derived tensors by address.  sources: only the entries derived - directly or
-    through other entries - from one of these tensors (default: every entry).  Entries with a `spec` go out together as
-    hero_derive_multi launches.  Order: an entry is redone once every entry it is derived from has been (waves of a
-    topological order over the output addresses; round 6: a 0/1 mask gathered per (query, video) pair and THEN cast to fp32
-    is a spec entry behind a builder entry - the old "spec entries first" order left it one batch behind)."""
+    through other entries - from one of these tensors (default: every entry).  An entry is redone after the entries it is
+    derived from (round 6: a 0/1 mask gathered per (query, video) pair and THEN cast to fp32 is a spec entry behind a
+    builder entry - a "spec entries first" order left it one batch behind): one pass in creation order gives every entry
+    a level, 1 + the highest level among the entries whose outputs it reads; level by level, the entries with a `spec` go
+    out together as hero_derive_multi launches, then the others are rebuilt.  Returns the entries redone, in that order."""
     skip_ids = {id(t) for t in skip_outputs}                  # entries the caller refreshes itself (host-computed orders)
-    entries = [e for e in _MEMO.values() if id(e[0]) not in skip_ids]
-    if sources is not None:                                    # what this call keeps current (the caller may restamp_memo them)
-        src_ptrs = {t.data_ptr() for t in sources}
-        _LAST_REFRESHED[:] = [k for k, e in _MEMO.items() if any(t.data_ptr() in src_ptrs for t in e[1])]
-        dirty = set(src_ptrs)
-        hit = [False] * len(entries)
-        grew = True
-        while grew:                                            # everything downstream of the sources
-            grew = False
-            for n, (out, srcs, fn, spec) in enumerate(entries):
-                if not hit[n] and any(t.data_ptr() in dirty for t in srcs):
-                    hit[n] = grew = True
-                    if isinstance(out, torch.Tensor):
-                        dirty.add(out.data_ptr())
-        todo = [e for n, e in enumerate(entries) if hit[n]]
-    else:
-        todo = list(entries)
-    waiting = {e[0].data_ptr() for e in todo if isinstance(e[0], torch.Tensor)}      # outputs not yet redone
-    while todo:
-        ready = [e for e in todo if not any(t.data_ptr() in waiting and t is not e[0] for t in e[1])]
-        if not ready:
-            raise RuntimeError("refresh_memo: memo entries derive from each other in a cycle")
-        batch = [L.Derive(L.ptr(srcs[0]), L.ptr(out), out.numel(), spec[0], spec[1], spec[2], spec[3])
-                 for out, srcs, fn, spec in ready if spec is not None]
-        for i in range(0, len(batch), 16):
-            part = batch[i:i + 16]
-            L.check(L.lib().hero_derive_multi((L.Derive * len(part))(*part), len(part), L.stream()))
-        for out, srcs, fn, spec in ready:
-            if spec is not None:
-                continue
-            new = fn()
-            if isinstance(out, torch.Tensor):
-                if new.shape != out.shape:
-                    raise RuntimeError("refresh_memo: a derived tensor changed shape %s -> %s; the batch structure is "
-                                       "different, not just its contents" % (tuple(out.shape), tuple(new.shape)))
-                out.copy_(new)
-        ids = {id(e) for e in ready}
-        for e in ready:
-            if isinstance(e[0], torch.Tensor):
-                waiting.discard(e[0].data_ptr())
-        todo = [e for e in todo if id(e) not in ids]
-
-
-_LAST_REFRESHED = []
-
-
-def last_refreshed_keys():
-    """Keys of the memo entries derived DIRECTLY from the `sources` of the last refresh_memo(sources=...) call."""
-    return list(_LAST_REFRESHED)
-
-
-def restamp_memo(keys):
-    """Re-key memo entries to the CURRENT version counters of their sources and return the new keys.  For a caller that has
-    just refreshed exactly these entries in place by other means - a replayed hipGraph of refresh_memo - and then moved the
-    sources' version counters (hero_amd.loader.StaticBatchFeeder.commit): the entries ARE current, and a later lookup - an
-    eager step, or the capture of another step graph - must find them instead of rebuilding beside them."""
-    out = []
-    for k in keys:
-        e = _MEMO.pop(k, None)
-        if e is None:
+    src = {t.data_ptr() for t in sources or ()}
+    level_of = {}                                              # output address -> level of the entry redone into it
+    levels = []
+    for e in sorted(_MEMO.values(), key=lambda e: e.seq):
+        ptrs = [t.data_ptr() for t in e.sources]
+        if id(e.out) in skip_ids or (sources is not None and not any(p in src or p in level_of for p in ptrs)):
             continue
-        nk = (k[0], k[1]) + tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype) for t in e[1])
-        _MEMO[nk] = e
-        out.append(nk)
-    return out
+        n = 1 + max([level_of.get(p, 0) for p in ptrs] + [0])
+        if isinstance(e.out, torch.Tensor):
+            level_of[e.out.data_ptr()] = n
+        if n > len(levels):
+            levels.append([])
+        levels[n - 1].append(e)
+    done = []
+    for todo in levels:
+        spec = [e for e in todo if e.spec is not None]
+        built = [e for e in todo if e.spec is None]
+        for i in range(0, len(spec), 16):
+            part = [L.Derive(L.ptr(e.sources[0]), L.ptr(e.out), e.out.numel(), *e.spec) for e in spec[i:i + 16]]
+            L.check(L.lib().hero_derive_multi((L.Derive * len(part))(*part), len(part), L.stream()))
+        for e in built:
+            new = e.fn()
+            if isinstance(e.out, torch.Tensor):
+                if new.shape != e.out.shape:
+                    raise RuntimeError("refresh_memo: a derived tensor changed shape %s -> %s; the batch structure is "
+                                       "different, not just its contents" % (tuple(e.out.shape), tuple(new.shape)))
+                e.out.copy_(new)
+        done += spec + built
+    return done
+
+
+def restamp_memo(entries):
+    """Re-key memo entries (refresh_memo's return value, in its order) to the CURRENT version counters of their sources,
+    keeping their creation numbers.  For a caller that has just refreshed these entries in place by other means - a replayed
+    hipGraph of refresh_memo - and then moved the sources' version counters (hero_amd.loader.StaticBatchFeeder.commit): the
+    entries ARE current, and a later lookup - an eager step, or the capture of another step graph - must find them."""
+    for e in entries:
+        if _MEMO.get(e.key) is e:                              # not dropped (or replaced) since
+            del _MEMO[e.key]
+            e.key = _memo_key(e.tag, e.extra, e.sources)
+            _MEMO[e.key] = e
 
 
 def as_mask_add(mask, S, Lq):

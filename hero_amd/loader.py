@@ -175,7 +175,7 @@ class StaticBatchFeeder:
         if self.dc.f_v_feats is None:
             self.static["f_v_feats"] = host_batch["f_v_feats"].to(self.device)
         self.static.update(self.dc.batch_entries())
-        self.static["_static_buffers"] = True        # TrainStep: padded formulation only (the pack plan is host-derived)
+        self.static["_static_buffers"] = True        # TrainStep: never a host-derived pack plan (padded, or the static plan below)
         # TWO staging sets, used alternately: the copy stream fills one while the commit of the previous batch reads the
         # other, so the only ordering the copy stream needs - "the commit that read this set two batches ago is done" -
         # is checked on the HOST (Event.synchronize, already satisfied in steady state).  A stream-side
@@ -195,7 +195,7 @@ class StaticBatchFeeder:
         self.stage_order = [{}, {}]
         self._order_ok = [False, False]
         self._versioned = None
-        self._memo_keys = []
+        self._memo_entries = []   # the memo entries the commit graphs redo (capture())
         self._want_graph = capture_commit
         self.plan = None
         if packed_rows:
@@ -224,10 +224,19 @@ class StaticBatchFeeder:
             raise ValueError("StaticBatchFeeder needs vfeat_dim % 4 == 0 (f_v_feats is gathered on the device)")
         if len(self._ready) >= 2:
             raise RuntimeError("StaticBatchFeeder: two batches are already prefetched; commit() one first")
+        lens = {k: torch.as_tensor(host_batch["lengths"][k], dtype=torch.int32).reshape(-1) for k in self.dc._in_off}
+        for k, (o, n) in self.dc._in_off.items():
+            if lens[k].numel() > n or (k in ("sub_nfrm", "sub_ntok", "vid_nfrm") and lens[k].numel() != n):
+                raise ValueError("StaticBatchFeeder: %s has %d entries (capacity %d)" % (k, lens[k].numel(), n))
         s = self._fill
+        self._consumed[s].synchronize()                                  # host-side; never recorded -> returns at once
+        if self.plan is not None:                    # the pack plan of THIS batch, from its host masks (numpy, ~0.2 ms)
+            from .model.layers import BertEncoder
+            BertEncoder.fill_static_plan(self._pin_plan[s].numpy(), self.plan,
+                                         [host_batch["f_attn_masks"].numpy(), host_batch["query_attn_masks"].numpy()])
+        # validated: from here on nothing raises, a batch that does not fit has left the feeder as it was
         self._fill ^= 1
         self._ready.append(s)
-        self._consumed[s].synchronize()                                  # host-side; never recorded -> returns at once
         if self.skip_h2d:                                                # lab switch (tools/lab/feedprobe.py): everything but the transfers
             self._landed[s].record(self.copy_stream)
             return
@@ -236,11 +245,8 @@ class StaticBatchFeeder:
                 self.stage[s][k].copy_(host_batch[k], non_blocking=True)
             flat = self._pin_len[s]                           # one pinned image of the input buffer, one H2D copy
             flat.zero_()
-            for k, (o, n) in self.dc._in_off.items():
-                src = torch.as_tensor(host_batch["lengths"][k], dtype=torch.int32).reshape(-1)
-                if src.numel() > n or (k in ("sub_nfrm", "sub_ntok", "vid_nfrm") and src.numel() != n):
-                    raise ValueError("StaticBatchFeeder: %s has %d entries (capacity %d)" % (k, src.numel(), n))
-                flat[o:o + src.numel()] = src
+            for k, (o, _) in self.dc._in_off.items():
+                flat[o:o + lens[k].numel()] = lens[k]
             self.stage_len[s].copy_(flat, non_blocking=True)
             # Segment orders of the id tensors (embedding-gradient scatter): a stable argsort of <= 10 k ids is ~0.3 ms of numpy
             # on a host that has ~6 ms of slack per step; on the device it was a one-workgroup radix sort inside every commit
@@ -250,10 +256,7 @@ class StaticBatchFeeder:
                 self._pin_order[s][k].copy_(o)
                 self.stage_order[s][k].copy_(self._pin_order[s][k], non_blocking=True)
             self._order_ok[s] = bool(self._orders)
-            if self.plan is not None:                # the pack plan of THIS batch, from its host masks (numpy, ~0.2 ms)
-                from .model.layers import BertEncoder
-                BertEncoder.fill_static_plan(self._pin_plan[s].numpy(), self.plan,
-                                             [host_batch["f_attn_masks"].numpy(), host_batch["query_attn_masks"].numpy()])
+            if self.plan is not None:
                 self.stage_plan[s].copy_(self._pin_plan[s], non_blocking=True)
             self._landed[s].record(self.copy_stream)
 
@@ -266,7 +269,7 @@ class StaticBatchFeeder:
             out.copy_(self.stage_order[s][k])
         if self.plan is not None:
             self.plan_flat.copy_(self.stage_plan[s])
-        HF.refresh_memo([t for t in self.static.values() if torch.is_tensor(t)], skip_outputs=[o for _, o, _ in self._orders])
+        return HF.refresh_memo([t for t in self.static.values() if torch.is_tensor(t)], skip_outputs=[o for _, o, _ in self._orders])
 
     def commit(self):
         """Make the oldest prefetched batch the current one: on the compute stream, staging -> static buffers, then
@@ -284,7 +287,7 @@ class StaticBatchFeeder:
             torch._C._increment_version(self._versioned)       # takes an ITERABLE of tensors (a bare tensor is iterated row by row)
             # ... but the entries the commit graph has just refreshed in place ARE current: re-key them, so that whoever looks
             # them up next (an eager step, the capture of another bucket's step graphs) finds them instead of rebuilding
-            self._memo_keys = HF.restamp_memo(self._memo_keys)
+            HF.restamp_memo(self._memo_entries)
         else:
             self._commit_body(s)
         self._consumed[s].record(cur)
@@ -309,9 +312,8 @@ class StaticBatchFeeder:
         for s in range(2):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._commit_body(s)
+                self._memo_entries = self._commit_body(s)    # every memo entry the commit graphs keep current
             self._graph[s] = g
-        self._memo_keys = HF.last_refreshed_keys()           # the memo entries the commit graphs keep current
         self._versioned = [t for t in self.static.values() if torch.is_tensor(t)] + [t for t in self.dc.frame_map]
         torch.cuda.synchronize(self.device)
 

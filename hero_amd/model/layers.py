@@ -6,6 +6,7 @@ State-dict keys are identical to the reference (separate query/key/value Linear 
 `nn.Dropout` children are kept as configuration holders (utils/misc.py:set_dropout rewrites `.p`);
 the dropout itself is applied inside the HIP kernels by a counter-based RNG.
 """
+import numpy as np
 import torch
 from torch import nn
 
@@ -250,32 +251,23 @@ class BertEncoder(nn.Module):
     @staticmethod
     def _pack_plan(mask_list, lens, max_len=64):
         """Row maps between the padded layout (groups stacked, row = position) and the packed one
-        (masked positions removed, sequences back to back).  None when (almost) every position is
-        valid.  One small device->host read per distinct batch; cached on the mask tensors."""
+        (masked positions removed, sequences back to back): a static plan (below) of exactly the valid rows, no pad
+        rows.  None when (almost) every position is valid.  One small device->host read per distinct batch; cached on
+        the mask tensors.  lens: positions per group (the masks' sizes)."""
         key = tuple((m.data_ptr(), m._version, tuple(m.shape)) for m in mask_list) + (max_len,)
         hit = BertEncoder._PLANS.get(key)
         if hit is not None:
             return hit[0]
-        dev = mask_list[0].device
-        flat = torch.cat([(m != 0).reshape(-1) for m in mask_list]).cpu()
-        total = flat.numel()
+        flat = torch.cat([(m != 0).reshape(-1) for m in mask_list]).cpu().numpy()
+        masks = [g.reshape(m.shape) for g, m in zip(np.split(flat, np.cumsum(lens)[:-1]), mask_list)]
         valid = int(flat.sum())
+        lmax = max([int(m.sum(1).max()) for m in masks if m.shape[0]] + [0])
         plan = None
-        counts = torch.cat([(m != 0).sum(1).reshape(-1) for m in mask_list]).cpu()
-        lmax = int(counts.max()) if counts.numel() else 0
-        if 0 < valid < 0.9 * total and lmax <= max_len:    # the variable-length attention kernels' limit
-            gather = torch.nonzero(flat, as_tuple=False).reshape(-1).to(torch.int32)
-            inverse = torch.full((total,), -1, dtype=torch.int32)
-            inverse[gather.long()] = torch.arange(valid, dtype=torch.int32)
-            off = torch.zeros(counts.numel() + 1, dtype=torch.int32)
-            off[1:] = torch.cumsum(counts, 0).to(torch.int32)
-            inv, back, r0 = [], [], 0
-            for n in lens:                                   # per group: padded -> packed and packed -> padded
-                inv.append(inverse[r0:r0 + n].contiguous().to(dev))
-                g = gather - r0
-                back.append(torch.where((g >= 0) & (g < n), g, torch.full_like(g, -1)).to(dev))
-                r0 += n
-            plan = (gather.to(dev), inverse.to(dev), inv, back, off.to(dev), int(counts.numel()), lmax)
+        if 0 < valid < 0.9 * flat.size and lmax <= max_len:    # the variable-length attention kernels' limit
+            lay = BertEncoder.static_plan_layout([m.shape for m in masks], valid, valid, lmax)
+            buf = np.zeros(lay["size"], dtype=np.int32)
+            BertEncoder.fill_static_plan(buf, lay, masks)
+            plan = BertEncoder._plan_views(torch.from_numpy(buf).to(mask_list[0].device), lay)
         if len(BertEncoder._PLANS) > 64:
             BertEncoder._PLANS.clear()
         BertEncoder._PLANS[key] = (plan, mask_list)          # keep the masks alive: ids stay unique
@@ -316,9 +308,8 @@ class BertEncoder(nn.Module):
     @staticmethod
     def fill_static_plan(flat, lay, masks):
         """Write the plan of one batch into `flat` (a numpy int32 array of lay['size'] elements: pinned host memory).
-        masks: one 0/1 array [S, L] per group, already padded to the layout's group shapes.  Same maps as `_pack_plan`
-        (valid positions in row-major order, groups back to back), + the pad rows.  Returns the number of valid rows."""
-        import numpy as np
+        masks: one 0/1 array [S, L] per group, already padded to the layout's group shapes.  The maps: valid positions in
+        row-major order, groups back to back, + the pad rows.  Returns the number of valid rows."""
         cap, chunk = lay["rows_cap"], BertEncoder.PAD_CHUNK
         valid_flat = np.concatenate([np.asarray(m).reshape(-1) != 0 for m in masks])
         counts = np.concatenate([(np.asarray(m) != 0).sum(1).reshape(-1) for m in masks]).astype(np.int64)
@@ -355,16 +346,22 @@ class BertEncoder(nn.Module):
         return valid
 
     @staticmethod
-    def register_static_plan(masks, flat, lay):
-        """flat: the DEVICE int32 buffer (lay['size'] elements) a feeder refreshes; masks: the device mask tensors of the
-        groups, in forward_multi's order - the plan is found by their addresses (their contents / versions change per batch)."""
+    def _plan_views(flat, lay):
+        """The plan tuple (gather, inverse, per-group inverse, per-group back, offsets, n_seq, lmax) as views of the int32
+        tensor `flat` laid out by static_plan_layout."""
         v = lambda name: flat[lay[name][0]:lay[name][0] + lay[name][1]]      # noqa: E731
         inverse = v("inverse")
         inv, r0 = [], 0
         for S, L_ in lay["groups"]:
             inv.append(inverse[r0:r0 + S * L_])
             r0 += S * L_
-        plan = (v("gather"), inverse, inv, [v("back%d" % g) for g in range(len(lay["groups"]))], v("off"), lay["n_seq"], lay["lmax"])
+        return (v("gather"), inverse, inv, [v("back%d" % g) for g in range(len(lay["groups"]))], v("off"), lay["n_seq"], lay["lmax"])
+
+    @staticmethod
+    def register_static_plan(masks, flat, lay):
+        """flat: the DEVICE int32 buffer (lay['size'] elements) a feeder refreshes; masks: the device mask tensors of the
+        groups, in forward_multi's order - the plan is found by their addresses (their contents / versions change per batch)."""
+        plan = BertEncoder._plan_views(flat, lay)
         BertEncoder._STATIC_PLANS[tuple(m.data_ptr() for m in masks)] = (plan, list(masks), lay)
         return plan
 

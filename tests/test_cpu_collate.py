@@ -275,11 +275,11 @@ def test_static_pack_plan_is_the_dynamic_plan_plus_pad_rows():
         BE.fill_static_plan(flat, dict(lay, rows_cap=valid - 1), [m.numpy() for m in masks])      # more valid rows than the capacity
 
 
-def test_refresh_memo_redoes_chained_entries_in_dependency_order():
+def test_refresh_memo_redoes_chained_entries_in_dependency_order_and_returns_them():
     """functional.refresh_memo (what a feeder's commit runs after new data landed in the static batch): entries derived from
-    OTHER entries are redone after them whatever the order of the memo table - round 6 found a (query, video) pair mask
-    (a builder entry) whose fp32 cast (an entry of its own) stayed one batch behind; restamp_memo moves re-keyed entries to
-    the end of the table, so table order is not dependency order either."""
+    OTHER entries are redone after them - round 6 found a (query, video) pair mask (a builder entry) whose fp32 cast (an
+    entry of its own) stayed one batch behind - and every entry redone is returned, the chained ones included (what a
+    feeder restamps after a replay)."""
     from hero_amd import functional as HF
     HF.reset_caches()
     a = torch.arange(6, dtype=torch.int64)
@@ -288,15 +288,53 @@ def test_refresh_memo_redoes_chained_entries_in_dependency_order():
     m2 = HF.memo("t2", (m1,), lambda: m1 + 1)
     m3 = HF.memo("t3", (m2, a), lambda: m2 * a)
     mo = HF.memo("to", (other,), lambda: other * 7)
-    k1 = [k for k in HF._MEMO if k[0] == "t1"]
-    HF.restamp_memo(k1)                                      # t1 now sits BEHIND its dependants in the table
-    assert [k[0] for k in HF._MEMO][-1] == "t1"
     a.copy_(torch.tensor([5, 4, 3, 2, 1, 0]))
     other.fill_(2)
-    HF.refresh_memo(sources=[a])
+    done = HF.refresh_memo(sources=[a])
     assert torch.equal(m1, a * 2) and torch.equal(m2, a * 2 + 1) and torch.equal(m3, (a * 2 + 1) * a)
     assert torch.equal(mo, torch.full((3,), 7))              # not derived from `a`: left alone
-    assert sorted(k[0] for k in HF.last_refreshed_keys()) == ["t1", "t3"]        # the DIRECT dependants (what a feeder restamps)
+    assert [e.tag for e in done] == ["t1", "t2", "t3"] and [e.out for e in done] == [m1, m2, m3]
     HF.refresh_memo()
     assert torch.equal(mo, torch.full((3,), 14))
+    HF.reset_caches()
+
+
+def test_restamped_memo_entry_keeps_its_place_in_the_refresh_order():
+    """functional.restamp_memo re-keys an entry (it moves to the end of the memo table), but the entry keeps its creation
+    number: a later refresh_memo still redoes it before the entries derived from it."""
+    from hero_amd import functional as HF
+    HF.reset_caches()
+    a = torch.arange(6, dtype=torch.int64)
+    m1 = HF.memo("t1", (a,), lambda: a * 2)
+    m2 = HF.memo("t2", (m1,), lambda: m1 + 1)
+    m3 = HF.memo("t3", (m2, a), lambda: m2 * a)
+    root = [e for e in HF.refresh_memo(sources=[a]) if e.tag == "t1"]
+    torch._C._increment_version([a])
+    HF.restamp_memo(root)
+    assert list(HF._MEMO.values())[-1].tag == "t1"           # the root now sits BEHIND its dependants in the table
+    a.copy_(torch.tensor([5, 4, 3, 2, 1, 0]))
+    HF.refresh_memo(sources=[a])
+    assert torch.equal(m1, a * 2) and torch.equal(m2, a * 2 + 1) and torch.equal(m3, (a * 2 + 1) * a)
+    a.fill_(3)
+    HF.refresh_memo()
+    assert torch.equal(m1, a * 2) and torch.equal(m2, a * 2 + 1) and torch.equal(m3, (a * 2 + 1) * a)
+    HF.reset_caches()
+
+
+def test_restamp_memo_keeps_an_entry_derived_from_another_entry_current():
+    """After a feeder's commit graph has redone the entries refresh_memo returned and the feeder has moved its sources'
+    version counters, restamp_memo makes ALL of them current again - also an entry whose source is another entry's output
+    (its version moved when that output was rewritten): a lookup finds it instead of rebuilding beside it."""
+    from hero_amd import functional as HF
+    HF.reset_caches()
+    a = torch.arange(6, dtype=torch.int64)
+    m1 = HF.memo("t1", (a,), lambda: a * 2)
+    m2 = HF.memo("t2", (m1,), lambda: m1 + 1)
+    done = HF.refresh_memo(sources=[a])
+    torch._C._increment_version([a])
+    HF.restamp_memo(done)
+    calls = []
+    assert HF.memo("t2", (m1,), lambda: calls.append("t2") or m1 + 1) is m2
+    assert HF.memo("t1", (a,), lambda: calls.append("t1") or a * 2) is m1
+    assert calls == []
     HF.reset_caches()

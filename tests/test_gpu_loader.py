@@ -372,6 +372,64 @@ def test_static_pack_plan_at_bench_size_equals_the_dynamic_plan():
         HF.clear_weight_cache()
 
 
+def test_static_feeder_prefetch_rejects_a_batch_and_stays_as_it_was():
+    """StaticBatchFeeder.prefetch validates before it changes anything: a batch with a subtitle row of 65 valid positions,
+    fed to a feeder whose static pack plan has the attention length class 64, raises ValueError and leaves the staging
+    state untouched - the next valid batch commits and trains exactly like an eager run over the same batches."""
+    import hero_amd
+    from hero_amd import functional as HF, synth
+    from hero_amd.loader import BucketedBatchFeeder, StaticBatchFeeder, batch_dims, pad_batch, pin_batch
+    from hero_amd.model.layers import BertEncoder
+    from hero_amd.step import TrainStep
+    from hero_amd.utils.misc import set_dropout
+    from tests.util import load_tiny, to_dev
+    hero_amd.set_compute_dtype(torch.float32)
+    good = _batches(2)
+    gen = torch.Generator().manual_seed(90)
+    subs = [[(list(range(4)), 61)] + [(list(range(4 + 2 * i, 6 + 2 * i)), 5) for i in range(7)],
+            [(list(range(2 * i, 2 * i + 2)), 4) for i in range(8)]]
+    bad = synth.video_batch(subs, [32, 24], 96, 160, gen, max_frames=32)
+    bad.update(synth.query_batch(2, [12, 6], 160, gen))
+    bad["targets"] = torch.tensor([[1, 3], [2, 5]])
+    bad["q_vidx"] = torch.arange(2)
+    assert int(bad["f_attn_masks"].sum(1).max()) == 65
+    bucket = BucketedBatchFeeder.derive_buckets([batch_dims(h) for h in good + [bad]], n_buckets=1, row_quantum=16)[0]
+    good, bad = [pad_batch(h, bucket) for h in good], pad_batch(bad, bucket)
+
+    def fresh():
+        HF.set_grad_sink(None)
+        HF.clear_weight_cache()
+        model, _, _ = load_tiny("cuda")
+        model.train()
+        set_dropout(model, 0.0)
+        return model
+
+    try:
+        opts = dict(learning_rate=1e-3, warmup_steps=2, num_train_steps=100)
+        ts = TrainStep(fresh(), opts=opts)
+        want = [float(ts.micro_step(to_dev({k: v for k, v in p.items() if k != "lengths"}, "cuda"))) for p in good]
+        HF.set_grad_sink(None)
+
+        ts = TrainStep(fresh(), opts=opts)
+        feeder = StaticBatchFeeder(pin_batch(good[0]), "cuda", capture_commit=False, packed_rows=bucket["rows"],
+                                   min_rows=bucket["min_rows"], frm_capacity=bucket["frm"])
+        assert feeder.plan["lmax"] == 64
+        got = [float(ts.micro_step(feeder.static))]
+        fill = feeder._fill
+        with pytest.raises(ValueError, match="attention class is 64"):
+            feeder.prefetch(pin_batch(bad))
+        assert feeder._fill == fill and feeder._ready == []
+        feeder.prefetch(pin_batch(good[1]))
+        b = feeder.commit()
+        got.append(float(ts.micro_step(b)))
+        np.testing.assert_allclose(got, want, rtol=2e-4, atol=1e-5)
+        assert torch.equal(b["f_attn_masks"].cpu(), good[1]["f_attn_masks"])
+    finally:
+        BertEncoder._STATIC_PLANS.clear()
+        HF.set_grad_sink(None)
+        hero_amd.set_compute_dtype(torch.bfloat16)
+
+
 def test_feeder_rejects_other_shapes():
     from hero_amd.loader import StaticBatchFeeder, pin_batch
     from hero_amd.synth import make_batch
