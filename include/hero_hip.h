@@ -471,6 +471,9 @@ int hero_rownorm_bwd(const HeroRowNorm* a, hero_stream_t stream);
 /*   dqn[m,:]  = sum_n g*mask[n,arg]*cn[n,arg,:];   dcn[n,arg,:] += g*mask*qn[m,:]  for          */
 /* n in [n0, n0+n_own) (a data-parallel rank only needs its own videos' rows; dcn is            */
 /* [n_own*L, D] and is fully written).                                                          */
+/* Tie rule: arg[m,n] is the FIRST frame l that attains the maximum (numpy.argmax; a fully       */
+/* masked video has every frame at exactly -1e4, so arg = 0 and mask[n,0] = 0 stops the          */
+/* gradient).  The backward sends the whole gradient of a pair to that one frame.                */
 typedef struct HeroScoreMax {
   const float* s;         /* [M, N*L], row stride ld_s >= N*L                                   */
   const float* mask;      /* [N, L] 0/1                                                         */
@@ -501,6 +504,9 @@ int hero_score_max_bwd(const HeroScoreMax* a, hero_stream_t stream);
 /* w = 1, or with hard negatives hard_w for the `pool` largest negatives of that row and easy_w  */
 /* for the rest.  ds_ctx / ds_q = gradients of mean(loss_ctx_rows) / mean(loss_q_rows) w.r.t. s  */
 /* (both fully written).                                                                        */
+/* Tie rule of the hard-negative ranking: descending by value, equal values in index order (a    */
+/* stable descending sort): rank(c) = #{c2 : s[c2] > s[c] or (s[c2] == s[c] and c2 < c)} over    */
+/* the negatives of the row (index = video) / column (index = query); rank < pool is "hard".     */
 typedef struct HeroRankLoss {
   const float* s;         /* [nq, nv]                                                           */
   float* loss_ctx_rows;   /* [nq]                                                               */
@@ -520,6 +526,9 @@ int hero_rank_loss(const HeroRankLoss* a, hero_stream_t stream);
 /* st/ed = Conv1d(1,1,K,pad=K/2,no bias)(sim), mask_logits, cross-entropy against targets[b,0/1] */
 /* (ignore_index -1, mean over the valid rows of each).  loss_rows[b] = ce_st[b]/n_st +           */
 /* ce_ed[b]/n_ed (sum over b = the reference's loss_st_ed).                                      */
+/* Every entry of `targets` must be -1 or in [0, L): the kernels index the logits with it        */
+/* UNCHECKED (a masked frame is allowed as a target, a frame outside the video is not).  A       */
+/* column whose targets are all -1 divides by zero, as the reference's mean does.                */
 typedef struct HeroStEd {
   const float* q2;        /* [B, D] video_query_linear(modularized query)                       */
   const void* ctx;        /* [B, L, D] dtype: frame embeddings                                  */
