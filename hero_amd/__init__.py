@@ -5,5 +5,6 @@ runs in hand-written HIP kernels behind a C ABI (include/hero_hip.h, hero_amd/li
 """
 from .functional import (advance_seed, compute_dtype, manual_seed,  # noqa: F401
                          notify_weights_updated, set_compute_dtype)
+from .retrieval import CorpusIndex, encode_corpus, search, search_torch  # noqa: F401
 
 __version__ = "0.1.0"

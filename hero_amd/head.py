@@ -2,8 +2,9 @@
 (include/hero_hip.h "VSM / VCMR task head"; reference: model/pretrain.py:62-292,
 model/encoder.py:460-471).  hero_amd.model.pretrain.HeroForPretraining uses them when the
 configuration is the training one (all in-batch negatives, hinge / lse, matched query-video pairs);
-every other configuration keeps the PyTorch formulation in that module, which is also what the
-parity tests compare these nodes against."""
+every other training configuration keeps the PyTorch formulation in that module, which is also what the
+parity tests compare these nodes against.  Inference over a whole corpus (eval_vcmr.py) has its own forward-only
+kernels: hero_amd/retrieval.py."""
 import ctypes as C
 
 import torch

@@ -1,8 +1,10 @@
 """VSM / VCMR task head (reference: model/pretrain.py).
 
-The encoders run on the HIP kernels; the head itself is a handful of small fp32 ops on
-(Nq, L, Nv)-sized score tensors (einsum, Conv1d k=5, sort, hinge) that stay PyTorch-ROCm calls
-(SURVEY.md §8 row H2).  Cross-GPU negatives use torch.distributed (RCCL) instead of Horovod.
+The encoders run on the HIP kernels.  The head's training configuration runs on the hero_* head kernels
+(hero_amd/head.py), full-corpus inference (eval_vcmr.py) on the retrieval kernels (hero_amd/retrieval.py); the
+PyTorch formulation in this module (einsum, Conv1d k=5, sort, hinge on (Nq, L, Nv)-sized score tensors) is what every
+other configuration uses and what both are tested against.  Cross-GPU negatives use torch.distributed (RCCL) instead
+of Horovod.
 """
 import random
 from collections import defaultdict

@@ -39,6 +39,8 @@ const char* hero_last_error(void);
  * (shadow, shadow_dtype; it is passed as an ARRAY, so the stride changed), HeroGemmEpilogue + 16 bytes (colsum_partial,
  * split_stride), HeroScoreMax + 8 bytes (gc_scale, gq_scale), HeroStEd.pad_ became g_scale - plus round 6: the three
  * scales are plain multipliers (the "0 means 1" sentinel is gone: pass 1.0f for "no weight"), hero_abi_struct_bytes().
+ * Still 3: the retrieval entry points hero_topk_rows, hero_st_ed_probs and hero_moment_topk were ADDED later (plain pointer /
+ * scalar arguments, no struct) - a backward-compatible addition, no struct moved, so the version stays.
  * INTEGRATION.md section 2 lists the breaks per version. */
 #define HERO_ABI_VERSION 3
 int hero_abi_version(void);
@@ -555,6 +557,31 @@ typedef struct HeroStEd {
 size_t hero_st_ed_bwd_workspace_bytes(int B);
 int hero_st_ed_fwd(const HeroStEd* a, hero_stream_t stream);
 int hero_st_ed_bwd(const HeroStEd* a, hero_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Full-corpus moment retrieval (eval_vcmr.py:232-323, 327-338; utils/tvr_eval_utils.py:95-129, */
+/* 237-260): plain pointer / scalar arguments only, no struct.  Both selections are exact (the  */
+/* same multiset of scores as a full sort), bit-reproducible, and break ties by the lower index. */
+/* ------------------------------------------------------------------------------------------ */
+/* The k largest of every row of scores [M, N] (row stride ld), best first: val [M, k] fp32, idx [M, k] int32.  alpha != 0:
+ * val = exp(alpha * score), selected on the score (eval_vcmr.py:266-269: exp(q2c_alpha * s), torch.topk); alpha == 0: val is
+ * the score.  Equal scores: lower index first.  k > N: the remaining slots are val 0, idx -1.  N <= 65536, k <= 128. */
+int hero_topk_rows(const float* scores, int M, int N, int ld, int k, float alpha, float* val, int* idx, hero_stream_t stream);
+/* Start / end probabilities of selected (query, video) pairs (eval_vcmr.py:232-238, model/pretrain.py:96-110 cross branch).
+ * sim [Nq, >= Nv * L] fp32 (row stride ld_sim): sim[q, v * L + l] = <video_query_linear(q), ctx[v, l]>, a GEMM output;
+ * mask [Nv, L] 0/1 fp32; sel [Nq, K] int32 video indices.  For each (q, j): the L similarities of video sel[q, j], both
+ * convolutions (odd, stride 1, `taps` <= 15, zero padding taps / 2) over the WHOLE row - positions beyond the video's
+ * length included, as the reference's convolution sees them - then mask_logits and a softmax over L.  st_prob, ed_prob:
+ * [Nq, K, L] fp32.  sel[q, j] outside [0, Nv) gives a row of zeros.  L <= 1024. */
+int hero_st_ed_probs(const float* sim, long long ld_sim, const float* mask, const int* sel, const float* w_st, const float* w_ed, int Nq,
+                     int Nv, int K, int L, int taps, float* st_prob, float* ed_prob, hero_stream_t stream);
+/* The top_n moments of every query (eval_vcmr.py:284-323).  st_prob, ed_prob [Nq, K, L], w [Nq, K] fp32, all >= 0.  Candidates:
+ * every (j, m, n) with min_l <= n - m < max_l and n < L - the ones of generate_min_max_length_mask; score = st[q, j, m] *
+ * w[q, j] * ed[q, j, n].  score [Nq, top_n] fp32 best first, flat [Nq, top_n] int32 = (j * L + m) * L + n.  Equal scores: lower
+ * flat index first.  Fewer than top_n candidates: score 0, flat -1 in the remaining slots.  The [Nq, K, L, L] products are never
+ * stored.  K = 1 with w = 1 is the single-video case (SVMR).  L <= 256, K <= 128, top_n <= 1024. */
+int hero_moment_topk(const float* st_prob, const float* ed_prob, const float* w, int Nq, int K, int L, int min_l, int max_l, int top_n,
+                     float* score, int* flat, hero_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Softmax cross-entropy over wide logit rows (pre-training heads, BASELINE configs[3]):        */
