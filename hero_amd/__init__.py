@@ -5,6 +5,7 @@ runs in hand-written HIP kernels behind a C ABI (include/hero_hip.h, hero_amd/li
 """
 from .functional import (advance_seed, compute_dtype, manual_seed,  # noqa: F401
                          notify_weights_updated, set_compute_dtype)
-from .retrieval import CorpusIndex, encode_corpus, search, search_torch  # noqa: F401
+from .retrieval import (CorpusIndex, RecallMeter, encode_corpus, k_first_hit, k_moment_nms, postprocess, postprocess_host,  # noqa: F401
+                        search, search_torch)
 
 __version__ = "0.1.0"

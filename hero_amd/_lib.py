@@ -25,7 +25,7 @@ EXPORTS = [
     "hero_query_pool_fwd", "hero_query_pool_bwd", "hero_rownorm_fwd", "hero_rownorm_bwd", "hero_score_max_fwd",
     "hero_score_max_bwd", "hero_rank_loss", "hero_sums_scaled", "hero_st_ed_fwd", "hero_st_ed_bwd", "hero_st_ed_bwd_workspace_bytes",
     "hero_cross_entropy_fwd", "hero_cross_entropy_bwd",
-    "hero_topk_rows", "hero_st_ed_probs", "hero_moment_topk",
+    "hero_topk_rows", "hero_st_ed_probs", "hero_moment_topk", "hero_moment_nms", "hero_first_hit",
     "hero_collate_subs", "hero_collate_clip_mask", "hero_collate_frame_map", "hero_collate_gather_feats", "hero_derive_multi",
     "hero_comm_available", "hero_comm_unique_id", "hero_comm_init", "hero_comm_destroy", "hero_comm_rank", "hero_comm_world",
     "hero_comm_allreduce_buckets", "hero_comm_broadcast", "hero_comm_allgather", "hero_comm_allgather_var",
@@ -262,6 +262,8 @@ def lib():
         L.hero_topk_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hero_st_ed_probs.argtypes = [C.c_void_p, C.c_longlong] + [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 3
         L.hero_moment_topk.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 3
+        L.hero_moment_nms.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 3
+        L.hero_first_hit.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.hero_collate_subs.argtypes = [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]
         L.hero_collate_gather_feats.argtypes = [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p]
         L.hero_derive_multi.argtypes = [C.POINTER(Derive), C.c_int, C.c_void_p]

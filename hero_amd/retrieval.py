@@ -19,10 +19,19 @@ The result dictionary (device tensors, no host synchronisation; K = min(max_vcmr
     svmr_scores  fp32  [Nq, N]   st * ed of the N best moments inside the ground-truth video        (:241-258, 327-338)
     svmr_st / svmr_ed  int32 [Nq, N]
 
-Slots without a candidate (fewer than N in-band moments) hold score 0 and index -1.  Seconds, NMS, JSON and metrics stay with
-the caller."""
+Slots without a candidate (fewer than N in-band moments) hold score 0 and index -1.
+
+What follows a search is on the device too (hero_moment_nms, hero_first_hit; no host synchronisation before `compute`):
+
+    post = postprocess(out, vfeat_interval=1.5, nms_thd=0.5, max_after_nms=100)    # seconds, temporal NMS, truncation (:345-348, 396-400, 458-478)
+    meter.update(post, gt_vidx, gt_ts, desc_type)                                    # RecallMeter: hit counts of R@K at IoU thresholds
+    metrics = meter.compute()                                                        # the dictionary of eval_retrieval, one synchronisation
+
+`postprocess_host` is the reference's post-processing restated on the host (utils/tvr_eval_utils.py:35-92, 132-234): what
+`postprocess` takes beyond N = 1024, and the speed baseline.  Writing the prediction JSON stays with the caller."""
 import ctypes as C
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -85,6 +94,50 @@ def k_moment_topk(st_prob, ed_prob, w, min_l, max_l, top_n):
     L.check(L.lib().hero_moment_topk(L.ptr(st_prob), L.ptr(ed_prob), L.ptr(w), Nq, K, Lc, int(min_l), int(max_l), int(top_n),
                                      L.ptr(score), L.ptr(flat), L.stream()))
     return score, flat
+
+
+def k_moment_nms(video, st, ed, thd, per_video_cap=100, max_after=None):
+    """video, st, ed int32 [Nq, N] (frame indices, ed inclusive, rows best first, -1 = vacant) -> (keep [Nq, max_after] int32:
+    positions of the survivors of the greedy temporal NMS, ascending, -1 in unused slots; count [Nq] int32).  include/hero_hip.h."""
+    _need_cuda(video, st, ed)
+    for t in (video, st, ed):
+        if t.dim() != 2 or t.dtype != torch.int32 or not t.is_contiguous() or t.shape != video.shape:
+            raise ValueError("k_moment_nms: video, st and ed must be contiguous int32 [Nq, N] tensors of one shape")
+    Nq, N = video.shape
+    max_after = N if max_after is None else int(max_after)
+    keep = torch.empty((Nq, max(max_after, 0)), dtype=torch.int32, device=video.device)
+    count = torch.empty((Nq,), dtype=torch.int32, device=video.device)
+    L.check(L.lib().hero_moment_nms(L.ptr(video), L.ptr(st), L.ptr(ed), Nq, N, float(thd), int(per_video_cap), max_after, L.ptr(keep),
+                                    L.ptr(count), L.stream()))
+    return keep, count
+
+
+def k_first_hit(video, gt_video, st=None, ed=None, gt_ts=None, interval=1.5, thds=None, n_pred=None):
+    """video (, st, ed) int32 [Nq, >= n_pred] with contiguous rows, gt_video int32 [Nq], gt_ts fp32 [Nq, 2] seconds, thds fp32 [T]
+    on the device -> first [Nq, T + 1] int32: rank of the first prediction in the ground-truth video (column 0) and of the first
+    one there with IoU >= thds[t] (column 1 + t) among the first n_pred columns; n_pred where there is none."""
+    _need_cuda(video, gt_video, st, ed, gt_ts, thds)
+    if (st is None) != (ed is None):
+        raise ValueError("k_first_hit: st and ed are given together or not at all")
+    for t in (video, st, ed):
+        if t is not None and (t.dim() != 2 or t.dtype != torch.int32 or t.stride(1) != 1 or t.shape != video.shape or t.stride(0) != video.stride(0)):
+            raise ValueError("k_first_hit: video, st and ed must be int32 [Nq, P] tensors of one shape and row stride, rows contiguous")
+    Nq, cols = video.shape
+    if gt_video.dtype != torch.int32 or gt_video.shape != (Nq,) or not gt_video.is_contiguous():
+        raise ValueError("k_first_hit: gt_video must be a contiguous int32 [Nq] tensor")
+    T = 0 if thds is None else int(thds.numel())
+    if T:
+        if thds.dtype != torch.float32 or not thds.is_contiguous():
+            raise ValueError("k_first_hit: thds must be a contiguous fp32 tensor")
+        if st is None or gt_ts is None or gt_ts.dtype != torch.float32 or gt_ts.shape != (Nq, 2) or not gt_ts.is_contiguous():
+            raise ValueError("k_first_hit: IoU thresholds need st, ed and a contiguous fp32 gt_ts [Nq, 2]")
+    n_pred = cols if n_pred is None else min(int(n_pred), cols)
+    first = torch.empty((Nq, T + 1), dtype=torch.int32, device=video.device)
+    ld = video.stride(0) if Nq > 1 else cols
+    L.check(L.lib().hero_first_hit(video.data_ptr(), None if st is None else st.data_ptr(), None if ed is None else ed.data_ptr(), Nq, n_pred, ld,
+                                   L.ptr(gt_video), L.ptr(gt_ts) if T else None, float(interval), L.ptr(thds) if T else None, T, L.ptr(first),
+                                   L.stream()))
+    return first
 
 
 def _unravel(flat, length):
@@ -291,3 +344,248 @@ def search_torch(index, model, query_input_ids, query_pos_ids, query_attn_masks,
         _, m, n = _unravel(flat, Lc)
         out["svmr_scores"], out["svmr_st"], out["svmr_ed"] = score, m, n
     return out
+
+
+# --------------------------------------------------------------------------------------------- #
+# after the search: seconds, temporal NMS, truncation, recall
+# --------------------------------------------------------------------------------------------- #
+MOMENT_TASKS = ("vcmr", "svmr")
+
+
+def _gather_survivors(out, task, keep, count, interval, A):
+    """keep [Nq, <= A] positions (-1 = unused) -> the TASK_nms_* tensors, padded to A columns."""
+    if keep.shape[1] < A:
+        keep = F.pad(keep, (0, A - keep.shape[1]), value=-1)
+    none = keep < 0
+    at = keep.clamp(min=0).long()
+    minus = torch.full_like(keep, -1)
+
+    def take(x, empty):
+        return torch.where(none, empty, torch.gather(x, 1, at))
+
+    zero = torch.zeros((), dtype=torch.float32, device=keep.device)
+    post = {task + "_nms_scores": take(out[task + "_scores"], zero)}
+    if task == "vcmr":
+        post["vcmr_nms_video"] = take(out["vcmr_video"], minus)
+    st, ed = take(out[task + "_st"], minus), take(out[task + "_ed"], minus)
+    post[task + "_nms_st"], post[task + "_nms_ed"] = st, ed
+    post[task + "_nms_st_sec"] = torch.where(none, zero, st.to(torch.float32) * interval)                 # eval_vcmr.py:396-397
+    post[task + "_nms_ed_sec"] = torch.where(none, zero, (ed + 1).to(torch.float32) * interval)           # :345-348, 398-400
+    post[task + "_nms_count"] = count
+    return post
+
+
+def _first_columns(st, A):
+    """No NMS (nms_thd == -1, eval_vcmr.py:458): the first A columns as they are."""
+    N = st.shape[1]
+    col = torch.arange(min(A, N), dtype=torch.int32, device=st.device).unsqueeze(0)
+    keep = torch.where(st[:, :min(A, N)] >= 0, col, torch.full_like(col, -1))
+    return keep, (keep >= 0).sum(1).to(torch.int32)
+
+
+def _carry_video_lists(out, post):
+    for k in ("vr_scores", "vr_indices"):               # the VR lists need no post-processing: RecallMeter finds them here
+        if k in out:
+            post[k] = out[k]
+    return post
+
+
+@torch.no_grad()
+def postprocess(out, *, vfeat_interval=1.5, nms_thd=0.5, max_after_nms=100, per_video_cap=100):
+    """Seconds, temporal NMS and truncation of a result dictionary of `search` / `search_torch`, on the device, without a host
+    synchronisation.  For TASK in vcmr, svmr (whichever `out` holds), with A = max_after_nms:
+
+        TASK_nms_scores  fp32  [Nq, A]   the survivors of the greedy NMS (hero_moment_nms; include/hero_hip.h), best first
+        vcmr_nms_video   int32 [Nq, A]
+        TASK_nms_st / TASK_nms_ed          int32 [Nq, A]   frame indices
+        TASK_nms_st_sec / TASK_nms_ed_sec  fp32  [Nq, A]   st * vfeat_interval / (ed + 1) * vfeat_interval (eval_vcmr.py:345-348, 396-400)
+        TASK_nms_count   int32 [Nq]
+
+    Vacant slots hold score 0, index -1 and seconds 0.  nms_thd == -1: no NMS, the first A columns (eval_vcmr.py:458).
+    per_video_cap = 100 is the reference's quirk: at most 100 survivors per video, whatever max_after_nms is (its inner
+    function never gets max_after_nms, utils/tvr_eval_utils.py:159-160, 229-230).  vr_scores / vr_indices are carried over
+    unchanged.  More than 1024 candidates per row go to `postprocess_host`."""
+    A = int(max_after_nms)
+    if A < 1:
+        raise ValueError("postprocess: max_after_nms must be >= 1")
+    tasks = [t for t in MOMENT_TASKS if t + "_scores" in out]
+    if any(out[t + "_st"].shape[1] > MAX_N for t in tasks):
+        return postprocess_host(out, vfeat_interval=vfeat_interval, nms_thd=nms_thd, max_after_nms=max_after_nms, per_video_cap=per_video_cap)
+    post = {}
+    for task in tasks:
+        st, ed = out[task + "_st"], out[task + "_ed"]
+        _need_cuda(st, ed, out[task + "_scores"])
+        if nms_thd == -1:
+            keep, count = _first_columns(st, A)
+        else:
+            video = out["vcmr_video"] if task == "vcmr" else st.clamp(min=-1, max=0)       # one video: group 0, -1 where vacant
+            keep, count = k_moment_nms(video.contiguous(), st.contiguous(), ed.contiguous(), nms_thd, per_video_cap, min(A, st.shape[1]))
+        post.update(_gather_survivors(out, task, keep, count, float(vfeat_interval), A))
+    return _carry_video_lists(out, post)
+
+
+def nms_rows_host(video, st, ed, thd, per_video_cap, max_after, interval=1.5):
+    """The reference's NMS (utils/tvr_eval_utils.py:35-92 inside :132-175 / :214-234) restated per row in Python: video, st, ed
+    integer arrays [Nq, N], rows best first, -1 = vacant.  A candidate falls iff an earlier SURVIVOR of its video overlaps it
+    with IoU > thd (IoU of the spans in seconds, Python floats, "union" = the hull); a video keeps at most per_video_cap; the
+    first max_after survivors of the row are the result.  -> (keep [Nq, max_after] int32, count [Nq] int32)."""
+    video, st, ed = (np.asarray(x) for x in (video, st, ed))
+    Nq, N = st.shape
+    sec0 = (st.astype(np.float32) * np.float32(interval)).tolist()
+    sec1 = ((ed + 1).astype(np.float32) * np.float32(interval)).tolist()
+    vid, vacant = video.tolist(), ((video < 0) | (st < 0)).tolist()
+    keep = np.full((Nq, max_after), -1, dtype=np.int32)
+    count = np.zeros((Nq,), dtype=np.int32)
+    for q in range(Nq):
+        survivors = {}                      # video -> [(start, end)] of its survivors
+        n = 0
+        for i in range(N):
+            if n >= max_after:
+                break
+            if vacant[q][i]:
+                continue
+            mine = survivors.setdefault(vid[q][i], [])
+            if len(mine) >= per_video_cap:
+                continue
+            a0, a1 = sec0[q][i], sec1[q][i]
+            for b0, b1 in mine:
+                hull = max(a1, b1) - min(a0, b0)
+                if (max(0.0, min(a1, b1) - max(a0, b0)) / hull if hull != 0 else 0.0) > thd:
+                    break
+            else:
+                mine.append((a0, a1))
+                keep[q, n] = i
+                n += 1
+        count[q] = n
+    return keep, count
+
+
+@torch.no_grad()
+def postprocess_host(out, *, vfeat_interval=1.5, nms_thd=0.5, max_after_nms=100, per_video_cap=100):
+    """`postprocess` on the host: the reference's algorithm in Python / numpy (`nms_rows_host`), any number of candidates, CPU or
+    device tensors in (device tensors are copied: this synchronises), tensors on the input's device out.  The device path
+    agrees with it bit for bit wherever frame index * vfeat_interval is exact in fp32 (1.5, 2, ...: then the IoU of seconds
+    and the IoU of frame counts are the same rational number)."""
+    A = int(max_after_nms)
+    if A < 1:
+        raise ValueError("postprocess_host: max_after_nms must be >= 1")
+    post = {}
+    for task in (t for t in MOMENT_TASKS if t + "_scores" in out):
+        st, ed = out[task + "_st"], out[task + "_ed"]
+        if nms_thd == -1:
+            keep, count = _first_columns(st, A)
+        else:
+            st_h, ed_h = st.cpu().numpy(), ed.cpu().numpy()
+            video = out["vcmr_video"].cpu().numpy() if task == "vcmr" else np.clip(st_h, -1, 0)
+            keep, count = nms_rows_host(video, st_h, ed_h, float(nms_thd), int(per_video_cap), min(A, st.shape[1]), float(vfeat_interval))
+            keep, count = torch.from_numpy(keep).to(st.device), torch.from_numpy(count).to(st.device)
+        post.update(_gather_survivors(out, task, keep, count, float(vfeat_interval), A))
+    return _carry_video_lists(out, post)
+
+
+class RecallMeter:
+    """R@K at IoU thresholds of VCMR and SVMR and R@K of VR, accumulated on the device over query batches: the metrics of
+    eval_retrieval (utils/tvr_standalone_eval.py:86-283) without its per-query matrices.
+
+        meter = RecallMeter()
+        for each query batch:  meter.update(postprocess(index.search(...)), gt_vidx, gt_ts, desc_type)     # no host synchronisation
+        meter.compute()  ->  {"VCMR": {"0.5-r1": ..}, "SVMR": {..}, "VR": {"r1": ..}, "VCMR_by_type": {"v-0.5-r1": .., "desc_type_ratio": ..}, ..}
+
+    A query counts for R@K at a threshold when hero_first_hit's rank of its first correct prediction is below K.  In the
+    reference's SVMR branch ranks are counted among the predictions in the ground-truth video; every SVMR prediction is in that
+    video, so this is the plain rank.  Only single-timestamp ground truth (TVR, How2R) is covered: the DiDeMo branch of the
+    reference (>= 4 timestamps, two of which must overlap) is not.  Pass `device` to allocate the counters at construction
+    (needed before capturing `update` in a graph); otherwise the first update allocates them."""
+
+    TASKS = ("VCMR", "SVMR", "VR")
+    TYPES = ("v", "t", "vt")
+
+    def __init__(self, iou_thds=(0.5, 0.7), topks=(1, 5, 10, 100), max_pred_per_query=100, vfeat_interval=1.5, device=None):
+        self.iou_thds, self.topks = tuple(float(t) for t in iou_thds), tuple(int(k) for k in topks)
+        if len(self.iou_thds) > 8:
+            raise ValueError("RecallMeter: at most 8 IoU thresholds")
+        self.max_pred_per_query, self.vfeat_interval = int(max_pred_per_query), float(vfeat_interval)
+        self.hits = self.n = None
+        self.typed = False
+        if device is not None:
+            self._allocate(torch.device(device))
+
+    def _allocate(self, device):
+        T, K = len(self.iou_thds), len(self.topks)
+        self.hits = torch.zeros((3, 4, T + 1, K), dtype=torch.int64, device=device)        # task, (all, v, t, vt), column of first_hit, K
+        self.n = torch.zeros((3, 4), dtype=torch.int64, device=device)
+        self._thds = torch.tensor(self.iou_thds, dtype=torch.float32, device=device)
+        self._topks = torch.tensor(self.topks, dtype=torch.int32, device=device)
+        self._types = torch.arange(3, device=device).view(1, 3)
+
+    def reset(self):
+        if self.hits is not None:
+            self.hits.zero_()
+            self.n.zero_()
+        self.typed = False
+
+    def add_first(self, task, first, n_pred, desc_type=None):
+        """Accumulate first-hit ranks [Nq, T + 1] (hero_first_hit's output; `n_pred` = none) of one task; any device."""
+        if self.hits is None:
+            self._allocate(first.device)
+        ti = self.TASKS.index(task)
+        hit = first.unsqueeze(-1) < self._topks.clamp(max=int(n_pred)).view(1, 1, -1)                  # [Nq, T + 1, K]; rank n_pred = no hit
+        self.hits[ti, 0] += hit.sum(0)
+        self.n[ti, 0] += first.shape[0]
+        if desc_type is not None:
+            of_type = desc_type.view(-1, 1).to(self._types.dtype) == self._types                             # [Nq, 3]
+            self.hits[ti, 1:] += (of_type.view(-1, 3, 1, 1) & hit.unsqueeze(1)).sum(0)
+            self.n[ti, 1:] += of_type.sum(0)
+            self.typed = True
+
+    @torch.no_grad()
+    def update(self, out_or_post, gt_vidx, gt_ts=None, desc_type=None):
+        """One query batch.  out_or_post: a dictionary of `postprocess` (TASK_nms_* keys, preferred) and / or of `search`; VR is read
+        from vr_indices.  gt_vidx int [Nq]; gt_ts fp32 [Nq, 2] seconds (without it only VR is counted); desc_type optional int [Nq],
+        0 / 1 / 2 = v / t / vt.  Only the first max_pred_per_query predictions count.  Enqueues kernels, never waits for them."""
+        d = out_or_post
+        gt = gt_vidx.reshape(-1).to(torch.int32).contiguous()
+        _need_cuda(gt, gt_ts, desc_type)
+        if self.hits is None:
+            self._allocate(gt.device)
+        ts = None if gt_ts is None else gt_ts.to(torch.float32).reshape(-1, 2).contiguous()
+        for task in MOMENT_TASKS:
+            pre = task + "_nms_" if task + "_nms_st" in d else task + "_"
+            if pre + "st" not in d or ts is None:
+                continue
+            st, ed = d[pre + "st"], d[pre + "ed"]
+            video = d[pre + "video"] if task == "vcmr" else torch.where(st >= 0, gt.view(-1, 1), torch.full_like(st, -1))
+            first = k_first_hit(video, gt, st, ed, ts, self.vfeat_interval, self._thds if self.iou_thds else None, self.max_pred_per_query)
+            self.add_first(task.upper(), first, min(self.max_pred_per_query, st.shape[1]), desc_type)
+        if "vr_indices" in d:
+            vi = d["vr_indices"]
+            first = k_first_hit(vi, gt, n_pred=self.max_pred_per_query)
+            first = first.expand(-1, len(self.iou_thds) + 1)                      # VR has one column; the counters are one shape
+            self.add_first("VR", first, min(self.max_pred_per_query, vi.shape[1]), desc_type)
+
+    def compute(self):
+        """The one synchronisation: the nested dictionary of eval_retrieval with its keys and its rounding, round(100 * x, 2)."""
+        if self.hits is None:
+            return {}
+        hits, n = self.hits.cpu().numpy(), self.n.cpu().numpy()
+
+        def pct(a, b):
+            with np.errstate(divide="ignore", invalid="ignore"):
+                return float(round(np.float64(a) / np.float64(b) * 100, 2))         # numpy's rounding, as get_rounded_percentage applies it
+
+        def table(ti, row, prefix):
+            if self.TASKS[ti] == "VR":
+                return {"%sr%d" % (prefix, k): pct(hits[ti, row, 0, j], n[ti, row]) for j, k in enumerate(self.topks)}
+            return {"%s%s-r%d" % (prefix, thd, k): pct(hits[ti, row, 1 + t, j], n[ti, row])
+                    for t, thd in enumerate(self.iou_thds) for j, k in enumerate(self.topks)}
+
+        present = [ti for ti in range(3) if n[ti, 0] > 0]
+        res = {self.TASKS[ti]: table(ti, 0, "") for ti in present}
+        if self.typed:
+            for ti in present:
+                by = {}
+                for c, name in enumerate(self.TYPES):
+                    by.update(table(ti, 1 + c, name + "-"))
+                by["desc_type_ratio"] = "v {} t {} vt {}".format(*[pct(n[ti, 1 + c], n[ti, 0]) for c in range(3)])
+                res[self.TASKS[ti] + "_by_type"] = by
+        return res

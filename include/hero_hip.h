@@ -41,6 +41,7 @@ const char* hero_last_error(void);
  * scales are plain multipliers (the "0 means 1" sentinel is gone: pass 1.0f for "no weight"), hero_abi_struct_bytes().
  * Still 3: the retrieval entry points hero_topk_rows, hero_st_ed_probs and hero_moment_topk were ADDED later (plain pointer /
  * scalar arguments, no struct) - a backward-compatible addition, no struct moved, so the version stays.
+ * Still 3: hero_moment_nms and hero_first_hit (what follows a search: NMS and recall ranks) were ADDED the same way.
  * INTEGRATION.md section 2 lists the breaks per version. */
 #define HERO_ABI_VERSION 3
 int hero_abi_version(void);
@@ -582,6 +583,32 @@ int hero_st_ed_probs(const float* sim, long long ld_sim, const float* mask, cons
  * stored.  K = 1 with w = 1 is the single-video case (SVMR).  L <= 256, K <= 128, top_n <= 1024. */
 int hero_moment_topk(const float* st_prob, const float* ed_prob, const float* w, int Nq, int K, int L, int min_l, int max_l, int top_n,
                      float* score, int* flat, hero_stream_t stream);
+/* Greedy temporal NMS of sorted candidate rows (utils/tvr_eval_utils.py:35-92 temporal_non_maximum_suppression, :132-175
+ * filter_vcmr_by_nms, :214-234 post_processing_svmr_nms).  video, st, ed int32 [Nq, N]: FRAME indices, ed inclusive, rows in
+ * descending score order (hero_moment_topk's order; scores are not read); video < 0 or st < 0 marks a vacant slot, which is
+ * never kept and suppresses nothing.  Candidates of one video form a group (single-video rows: any one value >= 0).  The row is
+ * walked in order: a candidate that is still alive and whose group has kept fewer than per_video_cap is kept and kills
+ * every later candidate of its group whose IoU with it is STRICTLY greater than thd; the walk stops after max_after
+ * survivors - the first max_after survivors in row order are the reference's sorted(...)[:max_after_nms].
+ * per_video_cap is the reference's quirk, kept: it never hands its max_after_nms to the inner function, whose default of
+ * 100 therefore always applies PER VIDEO (:35-36, 159-160, 229-230); pass 100 to reproduce it.
+ * IoU is the reference's on the half-open frame spans [st, ed + 1): inter = max(0, min(ed) + 1 - max(st)), "union" =
+ * max(ed) + 1 - min(st) (the hull), inter / union as a float64 division compared with thd as a double.  The reference divides
+ * seconds = frames * vfeat_interval; where those products are exact (1.5, 2: every interval of its configs) both quotients
+ * are the same rational correctly rounded, so no interval is needed and exact ties agree (3/5 at thd 0.6 survives).
+ * keep int32 [Nq, max_after]: positions in the input row of the survivors, ascending, -1 in unused slots; count int32 [Nq].
+ * One launch, no workspace, no atomics, bit-reproducible.  1 <= N <= 1024, 1 <= max_after <= N. */
+int hero_moment_nms(const int* video, const int* st, const int* ed, int Nq, int N, double thd, int per_video_cap, int max_after, int* keep,
+                    int* count, hero_stream_t stream);
+/* Rank of the first correct prediction of every query (utils/tvr_standalone_eval.py:86-257 eval_by_task_type, without its
+ * per-query matrices).  video, st, ed int32 [Nq, P] with row stride ld (st and ed may both be NULL: video retrieval, then T
+ * must be 0); gt_video int32 [Nq]; gt_ts fp32 [Nq, 2] seconds; thds fp32 [T] on the device, 0 <= T <= 8.
+ * first int32 [Nq, T + 1]: column 0 = first position whose video == gt_video; column 1 + t = first position with a video
+ * match AND IoU >= thds[t]; P where there is none.  Vacant slots (video < 0 or st < 0) never match.  IoU in fp32 as
+ * compute_temporal_iou_batch: prediction seconds float(st) * interval and float(ed + 1) * interval, "union" = max(end) -
+ * min(start), 0 where that is 0, compared iou >= thd in fp32.  Single-timestamp ground truth only (TVR, How2R). */
+int hero_first_hit(const int* video, const int* st, const int* ed, int Nq, int P, int ld, const int* gt_video, const float* gt_ts, float interval,
+                   const float* thds, int T, int* first, hero_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Softmax cross-entropy over wide logit rows (pre-training heads, BASELINE configs[3]):        */
