@@ -6,6 +6,8 @@ Host half - same names, inputs and outputs as the reference, so a reference Data
     video_collate   video_collate + get_gather_index     data/data.py:406-471, 504-512
     query_collate   query_collate                        data/vcmr.py:120-137
     vcmr_collate    vcmr_collate                         data/vcmr.py:140-159
+    videoqa_item    VideoQaDataset.__getitem__           data/videoQA.py:62-121 (one question)
+    video_qa_collate  video_qa_collate                   data/videoQA.py:155-182 (pinned by tests/golden/case_videoqa.npz)
 They are written over LENGTH arrays (one allocation per output, no pad_sequence / per-row python tensors) and also
 return the handful of int32 length arrays (`batch["lengths"]`) from which the device half rebuilds every index tensor.
 
@@ -148,6 +150,50 @@ def vcmr_collate(inputs):
     batch["vids"] = vids
     where = {v: i for i, v in enumerate(vids)}
     batch["q_vidx"] = torch.tensor([where[q[2]] for q in qs], dtype=torch.long)
+    return batch
+
+
+def videoqa_item(video, question, answers, target, ts, sep=2, frame_interval=1.5, vid=None):
+    """One question about one video -> VideoQaDataset.__getitem__'s 6-tuple (data/videoQA.py:62-121).
+    video: a video_item tuple; question / answers: token id lists (5 answers for TVQA, 4 for How2QA); target: index of the
+    right answer or None; ts: [start s, end s], the reference's "start-end" string, or None.  Every answer gets its own copy
+    of the video whose subtitles carry `[sep] question [sep] answer` behind their tokens (mask extended by ones)."""
+    ids, feats, masks, clip, clip_mask, n_subs, sub2frames = video
+    last = clip.shape[0] - 1
+    if ts is None:
+        ts_target = torch.tensor([-1, -1], dtype=torch.long)
+    else:
+        try:
+            if isinstance(ts, str):
+                ts = [float(t) for t in ts.split("-")[:2]]
+            ts_target = torch.tensor(st_ed_label(ts, last, frame_interval), dtype=torch.long)
+        except Exception:                                         # data/videoQA.py:149-150: an unreadable stamp is a missing label
+            ts_target = torch.tensor([-1, -1], dtype=torch.long)
+    copies, qa_ids, qa_masks = [], [], []
+    for ans in answers:
+        qa = torch.tensor([sep] + list(question) + [sep] + list(ans), dtype=torch.long)
+        ones = torch.ones_like(qa)
+        qa_ids.append(qa)
+        qa_masks.append(ones)
+        copies.append(([torch.cat((t, qa)) for t in ids], feats, [torch.cat((m, ones)) for m in masks],
+                       clip, clip_mask, n_subs, sub2frames))
+    return (copies, qa_ids, qa_masks, [vid], [torch.tensor([-1 if target is None else target], dtype=torch.long)], [ts_target])
+
+
+def video_qa_collate(inputs):
+    """list of videoqa_item tuples -> the reference's batch (data/videoQA.py:155-182): video_collate over every answer copy
+    (question-major, A copies each), `targets` (Nv, 1), `ts_targets` (Nv, 2) with -1 for a missing label, and the padded
+    `[sep] q [sep] a` rows qa_input_ids / qa_pos_ids / qa_attn_masks (txt_input_collate, data/data.py:474-484)."""
+    copies = [c for it in inputs for c in it[0]]
+    qa_ids = [t for it in inputs for t in it[1]]
+    qa_masks = [t for it in inputs for t in it[2]]
+    batch = video_collate(copies)
+    Lqa = max(t.shape[0] for t in qa_ids)
+    batch["targets"] = torch.stack([t for it in inputs for t in it[4]])
+    batch["ts_targets"] = torch.stack([t for it in inputs for t in it[5]])
+    batch["qa_input_ids"] = _pad_rows(qa_ids, Lqa, PAD_ID, torch.long)
+    batch["qa_pos_ids"] = torch.arange(Lqa, dtype=torch.long).clamp_(max=MAX_POS).unsqueeze(0)
+    batch["qa_attn_masks"] = _pad_rows(qa_masks, Lqa, 0, torch.long)
     return batch
 
 

@@ -5,3 +5,4 @@ from .encoder import (CrossModalTrm, QueryFeatEncoder, RobertaModelConfig,  # no
 from .model import HeroModel, HierarchicalVlModel, VideoModelConfig, VideoPreTrainedModel  # noqa: F401
 from .pretrain import HeroForPretraining  # noqa: F401
 from .vcmr import HeroForVcmr  # noqa: F401
+from .videoQA import HeroForVideoQA  # noqa: F401

@@ -24,6 +24,11 @@ TVR_OPTS = dict(  # config/train-tvr-8gpu.json
     learning_rate=1e-4, lr_mul=1.0, weight_decay=0.01, optim="adamw", betas=[0.9, 0.98],
     grad_norm=1.0, warmup_steps=500, num_train_steps=5000, gradient_accumulation_steps=2,
     train_batch_size=32, dropout=0.1, lw_neg_q=8.0, lw_neg_ctx=8.0, lw_st_ed=0.01, margin=0.1)
+TVQA_OPTS = dict(  # config/train-tvqa-8gpu.json: pass as `opts` with task='tvqa' / 'how2qa'
+    learning_rate=5e-5, lr_mul=10.0, weight_decay=0.01, optim="adamw", betas=[0.9, 0.98],
+    grad_norm=1.0, warmup_steps=1000, num_train_steps=10000, gradient_accumulation_steps=2,
+    train_batch_size=4, dropout=0.1, lw_st_ed=0.4)
+QA_TASKS = ("tvqa", "how2qa")
 
 
 def qkv_groups(model):
@@ -83,6 +88,10 @@ class TrainStep:
         self.opts = SimpleNamespace(**{**TVR_OPTS, **(opts or {})})
         self.task = task
         self.optimizer = build_optimizer(model, self.opts)
+        if task in QA_TASKS:          # _set_lr / _fill_lr scale groups 0 and 1: optim/misc.py:17-22 puts the task head there
+            head = {id(p) for n, p in model.named_parameters() if p.requires_grad and "v_encoder" not in n}
+            if {id(p) for g in self.optimizer.param_groups[:2] for p in g["params"]} != head:
+                raise RuntimeError("TrainStep: build_optimizer no longer puts the task head's parameters in groups 0 and 1")
         self.arena = D.GradArena(list(model.parameters()), bucket_bytes=bucket_bytes,
                                  groups=qkv_groups(model), static_usage=static_usage,
                                  compress=grad_compress if D.collectives_active() else None)
@@ -123,7 +132,10 @@ class TrainStep:
             out = self.model(batch, task=task or self.task, compute_loss=True)
             # 'tvr' / 'vsm': (loss_st_ed, loss_neg_ctx, loss_neg_q) summed (train_vcmr.py:216-226, pretrain.py:283-290);
             # 'mlm' / 'mfm-nce' / 'fom': one loss tensor
-            loss = (out[0] + out[1] + out[2]) if isinstance(out, (tuple, list)) else out
+            if (task or self.task) in QA_TASKS:       # (qa_loss, temporal_loss), train_videoQA.py:157-166
+                loss = out[0] + self.opts.lw_st_ed * out[1]
+            else:
+                loss = (out[0] + out[1] + out[2]) if isinstance(out, (tuple, list)) else out
             if loss.dim() > 0:                       # train_vcmr.py:226 `.mean()` of per-GPU losses; a 0-dim loss is its own mean
                 loss = loss.mean()
             loss.backward()
@@ -147,7 +159,16 @@ class TrainStep:
         lr = get_lr_sched(self.global_step, self.opts)
         for g in self.optimizer.param_groups:
             g["lr"] = lr                               # train_vcmr.py:248-249 (all groups)
+        if self.task in QA_TASKS:                      # train_videoQA.py:185-190: the task head's two groups keep lr_mul
+            for g in self.optimizer.param_groups[:2]:
+                g["lr"] = lr * self.opts.lr_mul
         return lr
+
+    def _fill_lr(self, lr):
+        """The device-side learning rates the captured optimiser step reads (one per parameter group)."""
+        self._lr_t.fill_(lr)
+        if self.task in QA_TASKS and self.opts.lr_mul != 1.0:
+            self._lr_t[:2].fill_(lr * self.opts.lr_mul)
 
     # ---- eager -------------------------------------------------------------------------------------
     def micro_step(self, batch, task=None, eager=False):
@@ -190,7 +211,7 @@ class TrainStep:
                 self._fwd_bwd(batch, task)
                 if (i + 1) % accum == 0:
                     lr = self._set_lr()
-                    self._lr_t.fill_(lr)
+                    self._fill_lr(lr)
                     self._optimise(device_state=True)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
@@ -218,7 +239,7 @@ class TrainStep:
         loss = self._fwd_bwd(batch, task)
         self.micro += 1
         if boundary:
-            self._lr_t.fill_(self._set_lr())
+            self._fill_lr(self._set_lr())
             self._optimise(device_state=True)
         return loss
 
@@ -310,7 +331,7 @@ class TrainStep:
         self.micro += 1
         self.counts["replayed"] += 1
         if boundary:
-            self._lr_t.fill_(self._set_lr())        # stream-ordered scalar fill (no pinned-buffer race)
+            self._fill_lr(self._set_lr())        # stream-ordered scalar fill (no pinned-buffer race)
             gb.replay()
             return loss_b
         ga.replay()

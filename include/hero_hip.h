@@ -42,6 +42,7 @@ const char* hero_last_error(void);
  * Still 3: the retrieval entry points hero_topk_rows, hero_st_ed_probs and hero_moment_topk were ADDED later (plain pointer /
  * scalar arguments, no struct) - a backward-compatible addition, no struct moved, so the version stays.
  * Still 3: hero_moment_nms and hero_first_hit (what follows a search: NMS and recall ranks) were ADDED the same way.
+ * Still 3: hero_qa_pool_fwd and hero_qa_pool_bwd (the video-QA head) were ADDED the same way.
  * INTEGRATION.md section 2 lists the breaks per version. */
 #define HERO_ABI_VERSION 3
 int hero_abi_version(void);
@@ -451,6 +452,23 @@ typedef struct HeroQueryPool {
 } HeroQueryPool;
 int hero_query_pool_fwd(const HeroQueryPool* a, hero_stream_t stream);
 int hero_query_pool_bwd(const HeroQueryPool* a, hero_stream_t stream);
+
+/* Video-QA head (HeroForVideoQA.get_modularized_video, model/videoQA.py:36-59): two attention pools over the frame   */
+/* rows of the A answer copies of each video, from ONE read of the rows for both score vectors.                     */
+/*   x [Nv * A, Lt, D] dtype: the encoder output, read in place - rows l < L of every sequence are frames, the QA  */
+/*   token rows behind them are not touched.  mask [Nv * A, L] 0/1 fp32.  w_qa, w_se [D] fp32.                     */
+/*   s_qa = <x, w_qa>, s_se = <x, w_se>, both through mask_logits (s * m + (1 - m) * -1e4);                        */
+/*   att_qa = softmax over l -> qa_pooled [Nv, A, D];  att_se = softmax over a -> se_pooled [Nv, L, D]; both        */
+/*   attention tables are [Nv, A, L] fp32 and are what the backward reads.  A masked frame has att_se = 1 / A.     */
+/* Backward: dx [Nv * A, Lt, D] dtype is written WHOLE (rows >= L as zeros: no memset by the caller); dw_qa, dw_se  */
+/* are [Nv, D] per-video shares, OVERWRITTEN - the caller sums the rows in a fixed order (no fp atomics).          */
+/* Envelope: 1 <= A <= 8, 1 <= L <= 256, L <= Lt <= 512, D % 4 == 0, D <= 1024; outside it HERO_ERR_ARG.           */
+/* Plain arguments, no struct: a backward-compatible addition, HERO_ABI_VERSION stays.                              */
+int hero_qa_pool_fwd(const void* x, const float* mask, const float* w_qa, const float* w_se, float* qa_pooled, float* se_pooled,
+                     float* att_qa, float* att_se, int Nv, int A, int L, int Lt, int D, int dtype, hero_stream_t stream);
+int hero_qa_pool_bwd(const void* x, const float* mask, const float* w_qa, const float* w_se, const float* att_qa, const float* att_se,
+                     const float* dqa, const float* dse, void* dx, float* dw_qa, float* dw_se,
+                     int Nv, int A, int L, int Lt, int D, int dtype, hero_stream_t stream);
 
 /* F.normalize(x, dim=-1, eps) (model/pretrain.py:370-371): y = x / max(||x||_2, eps).           */
 /* rnorm[r] = 1/max(||x_r||, eps), negated when the clamp was active (backward then skips the   */
