@@ -29,22 +29,18 @@ using namespace attn;
 
 namespace {
 
-// out^T[dt][nt] (head dim x lane-owned row) -> out[row][h*64 + d], rows < L
+// Output tiles go through an LDS head tile the wave owns and no longer reads (attn_mfma.h: stage_tileT / store_rows32):
+// stage_headT  out^T[dt][nt] (head dim x lane-owned row) -> tile[row][d], the bf16 bits st_bf4 would have stored
+// store_head   behind a wave_sync_lds: tile rows < L -> out[row][h*64 + d], 16 bytes per lane, whole 128-byte row segments
 template <int NB>
-__device__ __forceinline__ void store_headT(bf16_t* __restrict__ dst, int ld, int L, const f32x16_t (&acc)[2][NB], int lane) {
-  const int half = lane >> 5, l31 = lane & 31;
+__device__ __forceinline__ void stage_headT(bf16_t* tile, const f32x16_t (&acc)[2][NB], int lane) {
 #pragma unroll
-  for (int nt = 0; nt < NB; ++nt) {
-    const int row = 32 * nt + l31;
-    if (row < L) {
+  for (int nt = 0; nt < NB; ++nt) stage_tileT(tile + 32 * nt * RS, acc[0][nt], acc[1][nt], lane);
+}
+template <int NB>
+__device__ __forceinline__ void store_head(bf16_t* __restrict__ dst, int ld, int L, const bf16_t* tile, int lane) {
 #pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          st_bf4(dst + (size_t)row * ld + 32 * dt + 8 * q + 4 * half, acc[dt][nt][4 * q], acc[dt][nt][4 * q + 1],
-                 acc[dt][nt][4 * q + 2], acc[dt][nt][4 * q + 3]);
-    }
-  }
+  for (int nt = 0; nt < NB; ++nt) store_rows32(dst, ld, L, 32 * nt, tile + 32 * nt * RS, lane);
 }
 
 // CLS (packed batches whose longest sequence needs NB = 2): 0 = every sequence, 1 = only sequences of <= 32 rows (run by
@@ -180,7 +176,7 @@ __device__ __forceinline__ void fwd_stage(const FwdIn<NB>& in, bf16_t* Vs, int l
 }
 
 template <int NB>
-__device__ __forceinline__ void fwd_compute(const HeroAttn& a, const FwdIn<NB>& in, const bf16_t* Vs, const DropCtx& drop, int lane) {
+__device__ __forceinline__ void fwd_compute(const HeroAttn& a, const FwdIn<NB>& in, bf16_t* Vs, const DropCtx& drop, int lane) {
   const int half = lane >> 5, l31 = lane & 31;
   const int s = in.s, h = in.h, row0 = in.row0, L = in.L;
   const int Lm = a.L, Lp = (Lm + 3) & ~3;
@@ -277,8 +273,12 @@ __device__ __forceinline__ void fwd_compute(const HeroAttn& a, const FwdIn<NB>& 
     }
   }
   {
+    // ctx leaves through the V tile: its transposed fragments are in registers (vf) since before the softmax.  The caller's
+    // wave_sync_lds in front of the next pair's fwd_stage covers the reads of store_head.
     const HeadLay hl = head_lay(a, h);
-    store_headT<NB>(static_cast<bf16_t*>(a.ctx) + (size_t)row0 * hl.ldc + hl.c, hl.ldc, L, cx, lane);
+    stage_headT<NB>(Vs, cx, lane);
+    wave_sync_lds();
+    store_head<NB>(static_cast<bf16_t*>(a.ctx) + (size_t)row0 * hl.ldc + hl.c, hl.ldc, L, Vs, lane);
   }
 }
 
@@ -531,11 +531,14 @@ __device__ __forceinline__ void bwd_compute(const HeroAttn& a, const BwdIn<NB>& 
           gq[dt][it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[dt][jt][ks], pack8(&ds[jt][8 * ks]), gq[dt][it], 0, 0, 0);
     }
   }
-  store_headT<NB>(dq, ld, L, gq, lane);
+  // dQ leaves through the K tile: its row fragments (RC) and transposed fragments (kf) were read before the loop above.  The
+  // sync that publishes P and dS to the wave publishes the staged dQ as well.
+  stage_headT<NB>(Ks, gq, lane);
 
   // ---- dV^T = dO^T P_dropped, dK^T = Q^T dS: contraction over the queries, k-slot e of step ks <-> query
   //      32 it + 16 ks + 8 half + e for both operands (two transpose reads of 4 rows each)
   wave_sync_lds();
+  store_head<NB>(dq, ld, L, Ks, lane);
   f32x16_t gv[2][NB], gk[2][NB];
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
@@ -565,8 +568,13 @@ __device__ __forceinline__ void bwd_compute(const HeroAttn& a, const BwdIn<NB>& 
         }
       }
     }
-  store_headT<NB>(dqrow + hl.k, ld, L, gk, lane);
-  store_headT<NB>(dqrow + hl.v, ld, L, gv, lane);
+  // dK through the Q tile, dV through the dO tile: the last transposed reads of both are done (tr_frag waits for its data).
+  // The next pair's bwd_stage sits behind the caller's wave_sync_lds.
+  stage_headT<NB>(Qs, gk, lane);
+  stage_headT<NB>(Os, gv, lane);
+  wave_sync_lds();
+  store_head<NB>(dqrow + hl.k, ld, L, Qs, lane);
+  store_head<NB>(dqrow + hl.v, ld, L, Os, lane);
 }
 
 template <int NB, int WPB, bool RC, int CLS, int PPW, bool M4>       // second bound: at least two waves per SIMD (<= 256 registers) for the multi-pair kernels
@@ -674,6 +682,9 @@ __global__ __launch_bounds__(128, 2) void attn_mfma_fwd2_kernel(HeroAttn a) {
         const int r0 = 32 * jt + 16 * ks + 4 * half;
         vf[dt][jt][ks] = tr_frag(tr_addr(Vs, RS * 2, r0, dt, lane), tr_addr(Vs, RS * 2, r0 + 8, dt, lane));
       }
+  __syncthreads();                                       // both waves hold their V^T fragments: rows [32 w, 32 w + 32) of the tile now
+                                                         // belong to wave w, which stages its ctx rows there (here, next to the first
+                                                         // barrier, the two waves arrive together and no store is in flight yet)
   const int i = 32 * w + l31;
   float p[2][16];
   float mx = -3.0e38f;
@@ -738,7 +749,9 @@ __global__ __launch_bounds__(128, 2) void attn_mfma_fwd2_kernel(HeroAttn a) {
       for (int ks = 0; ks < 2; ++ks)
         cx[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[dt][jt][ks], pack8(&p[jt][8 * ks]), cx[dt], 0, 0, 0);
   }
-  store_tileT(static_cast<bf16_t*>(a.ctx) + (size_t)row0 * D + h * 64, D, L, w, cx, lane);
+  stage_tileT(Vs + 32 * w * RS, cx[0], cx[1], lane);
+  wave_sync_lds();
+  store_rows32(static_cast<bf16_t*>(a.ctx) + (size_t)row0 * D + h * 64, D, L, 32 * w, Vs + 32 * w * RS, lane);
 }
 
 template <bool RC, int CLS, bool M4>
@@ -836,6 +849,7 @@ __global__ __launch_bounds__(128, 2) void attn_mfma_bwd2_kernel(HeroAttn a) {
       }
   __syncthreads();                                       // B: both waves are done with the K tile - P may overwrite it
   bf16_t* dq = static_cast<bf16_t*>(a.dqkv) + (size_t)row0 * ld + h * 64;
+  f32x16_t gq[2];                                        // dQ^T of query tile w: kept until all four tiles are free (after barrier D)
   {
     const float* prow = RC ? nullptr : a.probs + ((size_t)(s * a.H + h) * Lm + min(i, L - 1)) * Lm;
     const uint64_t drow = ((uint64_t)(s * a.H + h) * Lm + i) * (uint64_t)Lp;
@@ -900,7 +914,6 @@ __global__ __launch_bounds__(128, 2) void attn_mfma_bwd2_kernel(HeroAttn a) {
       for (int q = 0; q < 4; ++q)
         st_bf4(Sl + i * PS + 32 * jt + 8 * q + 4 * half, ds[jt][4 * q], ds[jt][4 * q + 1], ds[jt][4 * q + 2], ds[jt][4 * q + 3]);
     }
-    f32x16_t gq[2];
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) {
 #pragma unroll
@@ -911,7 +924,6 @@ __global__ __launch_bounds__(128, 2) void attn_mfma_bwd2_kernel(HeroAttn a) {
         for (int ks = 0; ks < 2; ++ks)
           gq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[dt][jt][ks], pack8(&ds[jt][8 * ks]), gq[dt], 0, 0, 0);
     }
-    store_tileT(dq, ld, L, w, gq, lane);
   }
   __syncthreads();                                       // C: P and dS of all 64 queries are in the LDS
   // ---- phase 2, key tile w: dV^T = dO^T P_dropped, dK^T = Q^T dS over the 64 queries
@@ -939,8 +951,17 @@ __global__ __launch_bounds__(128, 2) void attn_mfma_bwd2_kernel(HeroAttn a) {
         gk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[dt], sf, gk[dt], 0, 0, 0);
       }
     }
-  store_tileT(dq + D, ld, L, w, gk, lane);
-  store_tileT(dq + 2 * D, ld, L, w, gv, lane);
+  // Every tile is an operand of both waves until here (P and dS of all queries, Q and dO of all rows), so no tile is free when
+  // dQ is ready: the three outputs are staged together behind one more barrier, each wave in rows [32 w, 32 w + 32) of a tile
+  // (dQ in the P tile, dK in the Q tile, dV in the dO tile).
+  __syncthreads();                                       // D: both waves are done with P, dS, Q and dO
+  stage_tileT(Pl + 32 * w * RS, gq[0], gq[1], lane);
+  stage_tileT(Qs + 32 * w * RS, gk[0], gk[1], lane);
+  stage_tileT(Os + 32 * w * RS, gv[0], gv[1], lane);
+  wave_sync_lds();
+  store_rows32(dq, ld, L, 32 * w, Pl + 32 * w * RS, lane);
+  store_rows32(dq + D, ld, L, 32 * w, Qs + 32 * w * RS, lane);
+  store_rows32(dq + 2 * D, ld, L, 32 * w, Os + 32 * w * RS, lane);
 }
 
 static bool mask_by_fours(const HeroAttn& a) { return !a.mask || ((a.L & 3) == 0 && ((uintptr_t)a.mask & 15) == 0); }

@@ -332,9 +332,17 @@ __global__ __launch_bounds__(64 * NB) void attn_long_bwd_dkv_kernel(HeroAttn a) 
       }
     }
   }
+  // dK, then dV, leave through the wave-private P | dS tiles (2 x 32 x PS elements >= one [32][RS] head tile) as 16-byte row
+  // segments (attn_mfma.h: stage_tileT / store_rows32); the loop's last transposed reads of them are done.
+  static_assert(2 * 32 * PS >= 32 * RS, "the P | dS tiles hold one staged output tile");
   bf16_t* dq = static_cast<bf16_t*>(a.dqkv) + (size_t)c.row0 * c.ld + c.h * 64;
-  store_tileT(dq + c.D, c.ld, c.L, jt, gk, lane);
-  store_tileT(dq + 2 * c.D, c.ld, c.L, jt, gv, lane);
+  stage_tileT(Pl, gk[0], gk[1], lane);
+  wave_sync_lds();
+  store_rows32(dq + c.D, c.ld, c.L, 32 * jt, Pl, lane);
+  wave_sync_lds();
+  stage_tileT(Pl, gv[0], gv[1], lane);
+  wave_sync_lds();
+  store_rows32(dq + 2 * c.D, c.ld, c.L, 32 * jt, Pl, lane);
 }
 
 template <int NB>

@@ -93,7 +93,37 @@ __device__ __forceinline__ void stage_tile_wg(const bf16_t* __restrict__ src, in
   }
 }
 
-// one 32-row tile of out^T[dt] (head dim x lane-owned row) -> out[row][d], rows < L
+// Output tiles leave through the LDS.  Straight from the accumulator layout (store_tileT below) one store instruction scatters
+// 64 x 8 bytes over 32 rows of the [M, 3 D] tensor, 16 instructions per 32-row tile; staged, the same bytes leave as 4
+// instructions of 16 bytes per lane, eight lanes per 128-byte head segment of a row - the map the operand loads use.
+//
+// stage_tileT: one 32-row tile of out^T[dt] (head dim x lane-owned row) -> 32 rows of an LDS head tile [row][RS] that the wave
+// owns and no longer reads.  The conversion is st_bf4's (same rounding of the same values): the bits that reach memory are
+// those of the direct store.
+__device__ __forceinline__ void stage_tileT(bf16_t* rows, const f32x16_t& a0, const f32x16_t& a1, int lane) {
+  bf16_t* p = rows + (lane & 31) * RS + 4 * (lane >> 5);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    st_bf4(p + 8 * q, a0[4 * q], a0[4 * q + 1], a0[4 * q + 2], a0[4 * q + 3]);
+    st_bf4(p + 32 + 8 * q, a1[4 * q], a1[4 * q + 1], a1[4 * q + 2], a1[4 * q + 3]);
+  }
+}
+// store_rows32: those 32 LDS rows (after a wave_sync_lds) -> out[row0 + r][0 .. 63], r < 32, only rows row0 + r < L.  Straight-line:
+// four LDS reads, then four stores predicated per lane (no wave-uniform branch around the group).
+__device__ __forceinline__ void store_rows32(bf16_t* __restrict__ dst, int ld, int L, int row0, const bf16_t* rows, int lane) {
+  const int c = (lane & 7) * 8, r8 = lane >> 3;
+  uint4 v[4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) v[it] = *reinterpret_cast<const uint4*>(rows + (it * 8 + r8) * RS + c);
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int r = row0 + it * 8 + r8;
+    if (r < L) *reinterpret_cast<uint4*>(dst + (size_t)r * ld + c) = v[it];
+  }
+}
+
+// one 32-row tile of out^T[dt] (head dim x lane-owned row) -> out[row][d], rows < L, straight from the accumulator layout: for
+// the kernels whose waves own no LDS tile to stage through (attention_mfma_long.hip: forward and dQ pass)
 __device__ __forceinline__ void store_tileT(bf16_t* __restrict__ dst, int ld, int L, int tile, const f32x16_t (&acc)[2], int lane) {
   const int half = lane >> 5, row = 32 * tile + (lane & 31);
   if (row < L) {
