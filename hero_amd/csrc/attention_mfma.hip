@@ -1,7 +1,9 @@
 // Short-sequence (L <= 64) masked multi-head self-attention on the matrix cores, bf16, head size 64.
 //
-// One WAVE owns one (sequence, head).  All five products of attention are 32x32x16 bf16 MFMAs on
-// the head's (padded) 32- or 64-row tiles, everything between them stays in registers:
+// One WAVE owns one 32-row query tile of a (sequence, head) pair: the whole pair for L <= 32 (attn_mfma_fwd_kernel /
+// attn_mfma_bwd_kernel), half of it for 32 < L <= 64 (attn_mfma_fwd2_kernel / attn_mfma_bwd2_kernel: two waves per pair).  All
+// five products of attention are 32x32x16 bf16 MFMAs on the head's (padded) 32-row tiles, everything between them stays in
+// registers:
 //
 //   forward   S^T = K Q^T        A = K rows, B = Q rows: 16-byte fragment loads straight from HBM
 //             softmax over keys  in the accumulator layout of S^T: lane <-> query, 16 keys per
@@ -14,6 +16,11 @@
 //             dQ^T = K^T dS^T    as ctx^T
 //             dV^T = dO^T P, dK^T = Q^T dS   contraction over queries: P and dS go through LDS
 //                                once ([query][key] bf16) and come back as transposed fragments
+//
+// What happens to a query row between the products (softmax, probability store, dropout, dS) and the products fed from
+// registers are the per-tile bodies of attn_mfma.h, shared by the one- and two-wave kernels (NK = 1 / 2 key tiles): the kernels
+// here differ in who loads and stages what, not in the arithmetic - same MFMAs on the same operands in the same order, the
+// same bits.  One exception: the one-wave forward keeps its own copy of the row body (fwd_compute says why).
 //
 // The fp32-VALU kernels this replaces (attention.hip, kept for the f32 parity mode and L > 64)
 // issue ~5000 wave instructions per head; this one ~400, which moves short-sequence attention
@@ -29,52 +36,26 @@ using namespace attn;
 
 namespace {
 
-// Output tiles go through an LDS head tile the wave owns and no longer reads (attn_mfma.h: stage_tileT / store_rows32):
-// stage_headT  out^T[dt][nt] (head dim x lane-owned row) -> tile[row][d], the bf16 bits st_bf4 would have stored
-// store_head   behind a wave_sync_lds: tile rows < L -> out[row][h*64 + d], 16 bytes per lane, whole 128-byte row segments
-template <int NB>
-__device__ __forceinline__ void stage_headT(bf16_t* tile, const f32x16_t (&acc)[2][NB], int lane) {
-#pragma unroll
-  for (int nt = 0; nt < NB; ++nt) stage_tileT(tile + 32 * nt * RS, acc[0][nt], acc[1][nt], lane);
-}
-template <int NB>
-__device__ __forceinline__ void store_head(bf16_t* __restrict__ dst, int ld, int L, const bf16_t* tile, int lane) {
-#pragma unroll
-  for (int nt = 0; nt < NB; ++nt) store_rows32(dst, ld, L, 32 * nt, tile + 32 * nt * RS, lane);
-}
-
-// CLS (packed batches whose longest sequence needs NB = 2): 0 = every sequence, 1 = only sequences of <= 32 rows (run by
-// the NB = 1 kernel), 2 = only the longer ones (NB = 2 kernel).  A ragged TVR batch has 8-48 rows per subtitle: with one
-// NB = 2 launch every (sequence, head) pair paid for a 64 x 64 tile at one wave per SIMD - 70 / 110 us per layer forward /
-// backward against 16 / 23 us for the same rows at 24 per sequence (profiles/r03_kernel_stats_D2r.csv).
+// CLS, the length class a launch owns: 0 = every sequence, 1 = only sequences of <= 32 rows (one-wave kernels), 2 = only the
+// longer ones (two-wave kernels).  A packed batch whose longest sequence has more than 32 rows runs as one launch of each
+// class.  A ragged TVR batch has 8-48 rows per subtitle: as ONE launch on 64-row tiles every (sequence, head) pair paid for a
+// 64 x 64 tile at one wave per SIMD - 70 / 110 us per layer forward / backward against 16 / 23 us for the same rows at 24 per
+// sequence (profiles/r03_kernel_stats_D2r.csv).
 //
-// Round 5 - PPW pairs per wave, software-pipelined.  Rounds 2-4 gave every (sequence, head) pair a wave of its own:
-// 6144 pairs on 256 CUs x 12-16 resident waves = 1.5 rounds of waves (forward) / 3 rounds (backward, 8 waves per CU
-// by LDS), each round one exposed chain scalar loads -> global loads -> LDS -> MFMAs -> stores: 20 / 36 us per launch
-// where the bytes need 13.6 / 27 at 5.5 TB/s.  Now a wave walks PPW pairs (pair = wave + k * number of waves, so
-// concurrently running waves still touch neighbouring heads of the same rows) and ISSUES the global loads of pair
-// k + 1 before it computes pair k: at most two pairs' operands are in registers, the straight-line code lets the
-// compiler count vmcnt exactly (VMEM operations of a wave complete in order), and the launch is one full round of waves.
-// The arithmetic of a pair is unchanged (same MFMAs on the same operands, same order): results are bit-identical.
+// PPW pairs per wave, software-pipelined (one-wave kernels).  With a wave per pair, 6144 pairs on 256 CUs x 12-16 resident
+// waves are 1.5 rounds of waves (forward) / 3 rounds (backward, 8 waves per CU by LDS), each round one exposed chain scalar
+// loads -> global loads -> LDS -> MFMAs -> stores: 20 / 36 us per launch where the bytes need 13.6 / 27 at 5.5 TB/s.  A wave
+// walks PPW pairs (pair = wave + k * number of waves, so concurrently running waves still touch neighbouring heads of the
+// same rows) and ISSUES the global loads of pair k + 1 before it computes pair k: at most two pairs' operands are in
+// registers, the straight-line code lets the compiler count vmcnt exactly (VMEM operations of a wave complete in order), and
+// the launch is one full round of waves.  Issuing the next pair's loads only once this pair's have landed was measured and
+// is no better (profiles/r05_attn_ab.txt); so were per-head operand panels instead of the fused projection's rows
+// (profiles/r06_attn_layout_ab.txt).
 
 // wave-uniform coordinates of a (sequence, head) pair; all of a wave's pairs are resolved at the kernel start (scalar loads
 // issued together - resolved later, behind wave-uniform branches, the sequence bounds became vector loads with a wait each)
 struct PairCoord { int s, h, row0, L; bool on; };
 
-// Where head h's Q / K / V (and ctx / dctx) columns live.  Product layout: the fused projection's rows [M, 3 * D] (Q | K | V,
-// head h at columns h * 64) and [M, D].  -DHERO_ATTN_LAB_HEADMAJOR (tools/lab/attn_layout_ab.py, round 6): per-head PANELS
-// [3][H][M][64] / [H][M][64] with M = S * L rows (unpacked launches only) - the layout VERDICT r5 #2 asked to price before
-// the QKV GEMM epilogue and the dgrad / wgrad loaders are taught to write / read it.
-struct HeadLay { int ld, ldc; size_t q, k, v, c; };
-__device__ __forceinline__ HeadLay head_lay(const HeroAttn& a, int h) {
-  [[maybe_unused]] const int D = a.H * 64;
-#ifdef HERO_ATTN_LAB_HEADMAJOR
-  const size_t P = (size_t)a.S * a.L * 64;
-  return {64, 64, (size_t)h * P, (size_t)(a.H + h) * P, (size_t)(2 * a.H + h) * P, (size_t)h * P};
-#else
-  return {3 * D, D, (size_t)h * 64, (size_t)D + h * 64, (size_t)2 * D + h * 64, (size_t)h * 64};
-#endif
-}
 template <int CLS>
 __device__ __forceinline__ PairCoord pair_coord(const HeroAttn& a, int pair) {
   const int P = a.S * a.H;
@@ -88,13 +69,13 @@ __device__ __forceinline__ PairCoord pair_coord(const HeroAttn& a, int pair) {
   return c;
 }
 
-// additive key mask of this lane's 16 keys per key tile (accumulator layout: 4 runs of 4 consecutive keys).  Part of a
-// pair's load set - loaded inside the compute phase it forced a wait for EVERYTHING older, the next pair's prefetch included
-// (VMEM operations complete in order).  Four 16-byte loads when the row stride allows it, else 16 scalar ones.
+// additive key mask of this lane's 16 keys per key tile (accumulator layout: 4 runs of 4 consecutive keys), NK key tiles.
+// Part of a pair's load set - loaded inside the compute phase it forced a wait for EVERYTHING older, the next pair's prefetch
+// included (VMEM operations complete in order).  Four 16-byte loads when the row stride allows it, else 16 scalar ones.
 // M4: rows of a.mask are 16-byte aligned multiples of 4 floats - decided by the LAUNCHER (template parameter): a run-time
 // choice between the two load sets is a join, and the compiler made the wave wait for the loads at the join.
-template <int NB, bool M4>
-__device__ __forceinline__ void load_mask(const HeroAttn& a, const PairCoord& c, float (&mk)[NB][16], int lane) {
+template <int NK, bool M4>
+__device__ __forceinline__ void load_mask(const HeroAttn& a, const PairCoord& c, float (&mk)[NK][16], int lane) {
   const int half = lane >> 5, Lm = a.L, L = c.L > 0 ? c.L : 1;
   // No mask: the loads still happen (from the start of qkv, always mapped) and a select zeroes the values - an `if (!a.mask)`
   // around the loads is a join of two definitions, and the compiler waits for the loads right there (before the join's copies).
@@ -102,7 +83,7 @@ __device__ __forceinline__ void load_mask(const HeroAttn& a, const PairCoord& c,
   const float* row = has ? a.mask + (size_t)c.s * Lm : reinterpret_cast<const float*>(a.qkv);
   if constexpr (M4) {
 #pragma unroll
-    for (int jt = 0; jt < NB; ++jt)
+    for (int jt = 0; jt < NK; ++jt)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int j0 = 32 * jt + 8 * q + 4 * half;          // a run past the row (j0 >= Lm >= L) is never used: any in-row address will do
@@ -111,7 +92,7 @@ __device__ __forceinline__ void load_mask(const HeroAttn& a, const PairCoord& c,
       }
   } else {
 #pragma unroll
-    for (int jt = 0; jt < NB; ++jt)
+    for (int jt = 0; jt < NK; ++jt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float v = row[has ? min(32 * jt + acc_row(r, half), L - 1) : 0];
@@ -120,22 +101,56 @@ __device__ __forceinline__ void load_mask(const HeroAttn& a, const PairCoord& c,
   }
 }
 
+// forward, query row i = 32 * (query tile) + (lane & 31) of pair (s, h) against NK key tiles: softmax of the scores sc, row
+// statistics / probabilities saved for the backward, dropout, ctx^T = V^T P^T from the V^T fragments vf
+template <int NK>
+__device__ __forceinline__ void fwd_row(const HeroAttn& a, int s, int h, int L, int i, const f32x16_t (&sc)[NK], const float (&mk)[NK][16],
+                                        const bf16x8_t (&vf)[2][NK][2], const DropCtx& drop, f32x16_t (&cx)[2], int half) {
+  const int Lm = a.L, Lp = (Lm + 3) & ~3;
+  float p[NK][16];
+  float mx, inv;
+  softmax_rows<NK>(sc, mk, a.scale, L, half, p, mx, inv);
+  if (a.stats && half == 0 && i < L)                 // what the backward needs to rebuild this row of P from q, k
+    *reinterpret_cast<float2*>(a.stats + ((size_t)(s * a.H + h) * Lm + i) * 2) = make_float2(mx, inv);
+  float* prow = a.probs ? a.probs + ((size_t)(s * a.H + h) * Lm + min(i, L - 1)) * Lm : nullptr;
+  const uint64_t drow = ((uint64_t)(s * a.H + h) * Lm + i) * (uint64_t)Lp;
+#pragma unroll
+  for (int jt = 0; jt < NK; ++jt) emit_probs(p[jt], inv, prow, i, Lm, L, jt, half, drop, drow);
+  tr_mfma<NK>(vf, p, cx);
+}
+
+// backward, the same query row: its probabilities (RC: rebuilt from the scores sc and the saved statistics st, else the saved
+// ones), dS from dP^T = dp, P_dropped and dS to row i of the [query][key] LDS tiles Pl / Sl (row stride PS elements),
+// dQ^T = K^T dS^T from the K^T fragments kf
+template <int NK, bool RC>
+__device__ __forceinline__ void bwd_row(const HeroAttn& a, int s, int h, int L, int i, const f32x16_t (&dp)[NK], const f32x16_t (&sc)[NK],
+                                        const float (&mk)[NK][16], const float2& st, const bf16x8_t (&kf)[2][NK][2], bf16_t* Pl, bf16_t* Sl,
+                                        int PS, const DropCtx& drop, f32x16_t (&gq)[2], int half) {
+  const int Lm = a.L, Lp = (Lm + 3) & ~3;
+  const float* prow = RC ? nullptr : a.probs + ((size_t)(s * a.H + h) * Lm + min(i, L - 1)) * Lm;
+  const uint64_t drow = ((uint64_t)(s * a.H + h) * Lm + i) * (uint64_t)Lp;
+  float pr[NK][16], ds[NK][16];
+  probs_row<NK, RC>(sc, mk, st, a.scale, prow, Lm, L, i < L ? 1.f : 0.f, half, pr);
+  ds_row<NK>(dp, pr, a.scale, drop, drow, half, Pl + i * PS, Sl + i * PS, ds);
+  tr_mfma<NK>(kf, ds, gq);
+}
+
+// ---- one wave per pair (L <= 32)
+
 // what a pair's global loads deliver (registers) + its wave-uniform coordinates
-template <int NB>
 struct FwdIn {
-  bf16x8_t kf[NB][4], qf[NB][4];
-  uint4 vr[4 * NB];
-  float mk[NB][16];
+  bf16x8_t kf[4], qf[4];
+  uint4 vr[4];
+  float mk[1][16];
   int s, h, row0, L;
   bool on;
 };
 
-template <int NB, bool M4>
-__device__ __forceinline__ void fwd_issue(const HeroAttn& a, const PairCoord& pcd, FwdIn<NB>& in, int lane) {
+template <bool M4>
+__device__ __forceinline__ void fwd_issue(const HeroAttn& a, const PairCoord& pcd, FwdIn& in, int lane) {
   const int half = lane >> 5, l31 = lane & 31;
   const int s = pcd.s, h = pcd.h;
-  const HeadLay hl = head_lay(a, h);
-  const int ld = hl.ld;
+  const int D = a.H * 64, ld = 3 * D;
   const int row0 = pcd.row0, L = pcd.L;
   in.s = s; in.h = h; in.row0 = row0; in.L = L; in.on = pcd.on;
   // A pair this launch does not own (the other length class of a packed batch, or past the end) is not computed; its loads
@@ -143,31 +158,28 @@ __device__ __forceinline__ void fwd_issue(const HeroAttn& a, const PairCoord& pc
   // i.e. no prefetch at all - but all go to row 0 of the tensor (one cache line per operand), selected without a branch.
   const int Lc = pcd.on ? L : 1;
   const bf16_t* rowp = static_cast<const bf16_t*>(a.qkv) + (size_t)(pcd.on ? row0 : 0) * ld;
-  const bf16_t* qp = rowp + hl.q;
-  const bf16_t* kp = rowp + hl.k;
-  const bf16_t* vp = rowp + hl.v;
+  const bf16_t* qp = rowp + (size_t)h * 64;
+  const bf16_t* kp = rowp + ((size_t)D + h * 64);
+  const bf16_t* vp = rowp + ((size_t)2 * D + h * 64);
   const int c = (lane & 7) * 8;
 #pragma unroll
-  for (int it = 0; it < 4 * NB; ++it) {
+  for (int it = 0; it < 4; ++it) {
     const int r = it * 8 + (lane >> 3);
     in.vr[it] = *reinterpret_cast<const uint4*>(vp + (size_t)min(r, Lc - 1) * ld + c);
   }
 #pragma unroll
-  for (int t = 0; t < NB; ++t)
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      in.kf[t][ks] = gfrag(kp, ld, 32 * t + l31, Lc, ks, half);
-      in.qf[t][ks] = gfrag(qp, ld, 32 * t + l31, Lc, ks, half);
-    }
-  load_mask<NB, M4>(a, pcd, in.mk, lane);
+  for (int ks = 0; ks < 4; ++ks) {
+    in.kf[ks] = gfrag(kp, ld, l31, Lc, ks, half);
+    in.qf[ks] = gfrag(qp, ld, l31, Lc, ks, half);
+  }
+  load_mask<1, M4>(a, pcd, in.mk, lane);
 }
 
-// V rows -> the wave's LDS tile [32 NB][RS], rows >= L zeroed (stage_tile's second half)
-template <int NB>
-__device__ __forceinline__ void fwd_stage(const FwdIn<NB>& in, bf16_t* Vs, int lane) {
+// V rows -> the wave's LDS tile [32][RS], rows >= L zeroed
+__device__ __forceinline__ void fwd_stage(const FwdIn& in, bf16_t* Vs, int lane) {
   const int c = (lane & 7) * 8;
 #pragma unroll
-  for (int it = 0; it < 4 * NB; ++it) {
+  for (int it = 0; it < 4; ++it) {
     const int r = it * 8 + (lane >> 3);
     uint4 t = in.vr[it];
     if (r >= in.L) t = make_uint4(0u, 0u, 0u, 0u);
@@ -175,62 +187,56 @@ __device__ __forceinline__ void fwd_stage(const FwdIn<NB>& in, bf16_t* Vs, int l
   }
 }
 
-template <int NB>
-__device__ __forceinline__ void fwd_compute(const HeroAttn& a, const FwdIn<NB>& in, bf16_t* Vs, const DropCtx& drop, int lane) {
+__device__ __forceinline__ void fwd_compute(const HeroAttn& a, const FwdIn& in, bf16_t* Vs, const DropCtx& drop, int lane) {
   const int half = lane >> 5, l31 = lane & 31;
   const int s = in.s, h = in.h, row0 = in.row0, L = in.L;
   const int Lm = a.L, Lp = (Lm + 3) & ~3;
-  // ---- S^T[jt][it] = K Q^T
-  f32x16_t sc[NB][NB];
+  // ---- S^T = K Q^T
+  f32x16_t sc;
 #pragma unroll
-  for (int jt = 0; jt < NB; ++jt)
+  for (int e = 0; e < 16; ++e) sc[e] = 0.f;
 #pragma unroll
-    for (int it = 0; it < NB; ++it) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) sc[jt][it][e] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) sc[jt][it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(in.kf[jt][ks], in.qf[it][ks], sc[jt][it], 0, 0, 0);
-    }
-  const float (&mk)[NB][16] = in.mk;                   // additive key mask of this lane's keys (loaded with the pair's operands)
-  // V^T fragments: k-slot e of step ks <-> key 32 jt + 16 ks + 4 half + (e & 3) + 8 (e >> 2), i.e. the
-  // keys this lane holds in accumulator registers 8 ks .. 8 ks + 7
-  bf16x8_t vf[2][NB][2];
+  for (int ks = 0; ks < 4; ++ks) sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(in.kf[ks], in.qf[ks], sc, 0, 0, 0);
+  const float (&mk)[16] = in.mk[0];                    // additive key mask of this lane's keys (loaded with the pair's operands)
+  // V^T fragments: k-slot e of step ks <-> key 16 ks + 4 half + (e & 3) + 8 (e >> 2), i.e. the keys this lane holds in
+  // accumulator registers 8 ks .. 8 ks + 7
+  bf16x8_t vf[2][2];
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-    for (int jt = 0; jt < NB; ++jt)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int r0 = 32 * jt + 16 * ks + 4 * half;
-        vf[dt][jt][ks] = tr_frag(tr_addr(Vs, RS * 2, r0, dt, lane), tr_addr(Vs, RS * 2, r0 + 8, dt, lane));
-      }
+    for (int ks = 0; ks < 2; ++ks) {
+      const int r0 = 16 * ks + 4 * half;
+      vf[dt][ks] = tr_frag(tr_addr(Vs, RS * 2, r0, dt, lane), tr_addr(Vs, RS * 2, r0 + 8, dt, lane));
+    }
 
-  f32x16_t cx[2][NB];
+  f32x16_t cx[2];
+  // The row body below is this kernel's own copy of what fwd_row (softmax_rows / emit_probs / tr_mfma) and tr_frags hold for
+  // the two-wave kernel, and it stands in a ONE-TRIP loop, on purpose.  Both were tried the plain way: with the body (or only
+  // the V^T gather above) behind the shared functions, or with the same text outside a loop, the compiler awaits the four
+  // key-mask loads one by one (s_waitcnt vmcnt(3), 2, 1, 0 right behind the staging) where this form waits vmcnt(1) and, 30
+  // instructions later, vmcnt(0) - and the launch of the bench batch is 0.2 - 0.3 us (2 %) slower
+  // (profiles/attn_refactor_ab.txt).  Same operations per element as fwd_row: a change to the softmax goes to both.
 #pragma unroll
-  for (int it = 0; it < NB; ++it) {
-    const int i = 32 * it + l31;
-    float p[NB][16];
+  for (int it = 0; it < 1; ++it) {
+    const int i = 32 * it + l31;                     // it = 0
+    float p[16];
     float mx = -3.0e38f;
 #pragma unroll
-    for (int jt = 0; jt < NB; ++jt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int j = 32 * jt + acc_row(r, half);
-        const float v = j < L ? fmaf(sc[jt][it][r], a.scale, mk[jt][r]) : -3.0e38f;
-        p[jt][r] = v;
-        mx = fmaxf(mx, v);
-      }
+    for (int r = 0; r < 16; ++r) {
+      const int j = acc_row(r, half);
+      const float v = j < L ? fmaf(sc[r], a.scale, mk[r]) : -3.0e38f;
+      p[r] = v;
+      mx = fmaxf(mx, v);
+    }
     mx = fmaxf(mx, xhalf(mx));
     float sum = 0.f;
 #pragma unroll
-    for (int jt = 0; jt < NB; ++jt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int j = 32 * jt + acc_row(r, half);
-        const float e = j < L ? __expf(p[jt][r] - mx) : 0.f;
-        p[jt][r] = e;
-        sum += e;
-      }
+    for (int r = 0; r < 16; ++r) {
+      const int j = acc_row(r, half);
+      const float e = j < L ? __expf(p[r] - mx) : 0.f;
+      p[r] = e;
+      sum += e;
+    }
     sum += xhalf(sum);
     const float inv = 1.f / sum;
     if (a.stats && half == 0 && i < L)                 // what the backward needs to rebuild this row of P from q, k
@@ -238,51 +244,45 @@ __device__ __forceinline__ void fwd_compute(const HeroAttn& a, const FwdIn<NB>& 
     float* prow = a.probs ? a.probs + ((size_t)(s * a.H + h) * Lm + min(i, L - 1)) * Lm : nullptr;
     const uint64_t drow = ((uint64_t)(s * a.H + h) * Lm + i) * (uint64_t)Lp;
 #pragma unroll
-    for (int jt = 0; jt < NB; ++jt)
+    for (int q = 0; q < 4; ++q) {
+      const int j0 = 8 * q + 4 * half;
+      float4 m = make_float4(1.f, 1.f, 1.f, 1.f);
+      if (drop.on()) m = drop.mask4((drow + j0) >> 2);
+      const float mm[4] = {m.x, m.y, m.z, m.w};
+      float pr4[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int j0 = 32 * jt + 8 * q + 4 * half;
-        float4 m = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (drop.on()) m = drop.mask4((drow + j0) >> 2);
-        const float mm[4] = {m.x, m.y, m.z, m.w};
-        float pr4[4];
+      for (int e = 0; e < 4; ++e) {
+        pr4[e] = p[4 * q + e] * inv;
+        p[4 * q + e] = pr4[e] * mm[e];
+      }
+      if (prow && i < L) {
+        if ((Lm & 3) == 0 && j0 + 3 < L) {
+          *reinterpret_cast<float4*>(prow + j0) = make_float4(pr4[0], pr4[1], pr4[2], pr4[3]);   // one 16-byte store per run of 4 columns
+        } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          pr4[e] = p[jt][4 * q + e] * inv;
-          p[jt][4 * q + e] = pr4[e] * mm[e];
-        }
-        if (prow && i < L) {
-          if ((Lm & 3) == 0 && j0 + 3 < L) {
-            *reinterpret_cast<float4*>(prow + j0) = make_float4(pr4[0], pr4[1], pr4[2], pr4[3]);   // one 16-byte store per run of 4 columns
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (j0 + e < L) prow[j0 + e] = pr4[e];
-          }
+          for (int e = 0; e < 4; ++e)
+            if (j0 + e < L) prow[j0 + e] = pr4[e];
         }
       }
+    }
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) {
 #pragma unroll
-      for (int e = 0; e < 16; ++e) cx[dt][it][e] = 0.f;
+      for (int e = 0; e < 16; ++e) cx[dt][e] = 0.f;
 #pragma unroll
-      for (int jt = 0; jt < NB; ++jt)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-          cx[dt][it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[dt][jt][ks], pack8(&p[jt][8 * ks]), cx[dt][it], 0, 0, 0);
+      for (int ks = 0; ks < 2; ++ks)
+        cx[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[dt][ks], pack8(&p[8 * ks]), cx[dt], 0, 0, 0);
     }
   }
-  {
-    // ctx leaves through the V tile: its transposed fragments are in registers (vf) since before the softmax.  The caller's
-    // wave_sync_lds in front of the next pair's fwd_stage covers the reads of store_head.
-    const HeadLay hl = head_lay(a, h);
-    stage_headT<NB>(Vs, cx, lane);
-    wave_sync_lds();
-    store_head<NB>(static_cast<bf16_t*>(a.ctx) + (size_t)row0 * hl.ldc + hl.c, hl.ldc, L, Vs, lane);
-  }
+  // ctx leaves through the V tile (attn_mfma.h: stage_tileT / store_rows32): its transposed fragments are in registers (vf)
+  // since before the softmax.  The caller's wave_sync_lds in front of the next pair's fwd_stage covers the reads of the store.
+  const int D = a.H * 64;
+  stage_tileT(Vs, cx[0], cx[1], lane);
+  wave_sync_lds();
+  store_rows32(static_cast<bf16_t*>(a.ctx) + (size_t)row0 * D + (size_t)h * 64, D, L, 0, Vs, lane);
 }
 
-template <int NB, int WPB, int CLS, int PPW, bool M4>       // second bound: waves per SIMD the two-pair kernel must fit (<= 168 registers)
+template <int WPB, int CLS, int PPW, bool M4>       // second bound: waves per SIMD the two-pair kernel must fit (<= 168 registers)
 __global__ __launch_bounds__(64 * WPB, (PPW == 2 ? 3 : 1)) void attn_mfma_fwd_kernel(HeroAttn a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -291,87 +291,71 @@ __global__ __launch_bounds__(64 * WPB, (PPW == 2 ? 3 : 1)) void attn_mfma_fwd_ke
   const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * WPB + wave), nw = gridDim.x * WPB;
   if (wid >= a.S * a.H) return;                        // wave-uniform; no workgroup barriers below
   DropCtx drop(a.dropout);
-  bf16_t* Vs = reinterpret_cast<bf16_t*>(smem) + wave * (32 * NB * RS);
+  bf16_t* Vs = reinterpret_cast<bf16_t*>(smem) + wave * (32 * RS);
   // two named register sets, explicit steps (an array of structs indexed by the unrolled loop counter ended up in scratch)
   const PairCoord c0 = pair_coord<CLS>(a, wid), c1 = pair_coord<CLS>(a, PPW > 1 ? wid + nw : wid),
                   c2 = pair_coord<CLS>(a, PPW > 2 ? wid + 2 * nw : wid);
-  FwdIn<NB> A, B;
-#ifdef HERO_ATTN_LATE_ISSUE          // lab (tools/lab/attn_ab.py): the next pair's loads are issued once this pair's have landed
-  constexpr bool LATE = true;
-#else
-  constexpr bool LATE = false;
-#endif
-  fwd_issue<NB, M4>(a, c0, A, lane);
-  if (PPW > 1 && !LATE) fwd_issue<NB, M4>(a, c1, B, lane);                 // next pair's loads fly during this pair
-  fwd_stage<NB>(A, Vs, lane);
+  FwdIn A, B;
+  fwd_issue<M4>(a, c0, A, lane);
+  if (PPW > 1) fwd_issue<M4>(a, c1, B, lane);          // next pair's loads fly during this pair
+  fwd_stage(A, Vs, lane);
   wave_sync_lds();
-  if (PPW > 1 && LATE) fwd_issue<NB, M4>(a, c1, B, lane);
-  if (A.on) fwd_compute<NB>(a, A, Vs, drop, lane);
+  if (A.on) fwd_compute(a, A, Vs, drop, lane);
   if (PPW > 1) {
-    if (PPW > 2) fwd_issue<NB, M4>(a, c2, A, lane);
+    if (PPW > 2) fwd_issue<M4>(a, c2, A, lane);
     wave_sync_lds();                                   // the previous pair's transpose reads of the tile are done
-    fwd_stage<NB>(B, Vs, lane);
+    fwd_stage(B, Vs, lane);
     wave_sync_lds();
-    if (B.on) fwd_compute<NB>(a, B, Vs, drop, lane);
+    if (B.on) fwd_compute(a, B, Vs, drop, lane);
   }
   if (PPW > 2) {
     wave_sync_lds();
-    fwd_stage<NB>(A, Vs, lane);
+    fwd_stage(A, Vs, lane);
     wave_sync_lds();
-    if (A.on) fwd_compute<NB>(a, A, Vs, drop, lane);
+    if (A.on) fwd_compute(a, A, Vs, drop, lane);
   }
 }
 
-template <int NB>
 struct BwdIn {
-  uint4 kr[4 * NB], qr[4 * NB], orw[4 * NB];           // K, Q, dO rows as loaded (16 B per lane per 8 rows)
-  bf16x8_t vf[NB][4];                                  // V row fragments, straight from global memory
-  float mk[NB][16];                                    // RC: additive key mask of this lane's keys
-  float2 st[NB];                                       // RC: saved row maximum and 1 / row sum of this lane's query rows
+  uint4 kr[4], qr[4], orw[4];                          // K, Q, dO rows as loaded (16 B per lane per 8 rows)
+  bf16x8_t vf[4];                                      // V row fragments, straight from global memory
+  float mk[1][16];                                     // RC: additive key mask of this lane's keys
+  float2 st;                                           // RC: saved row maximum and 1 / row sum of this lane's query row
   int s, h, row0, L;
   bool on;
 };
 
-template <int NB, bool RC, bool M4>
-__device__ __forceinline__ void bwd_issue(const HeroAttn& a, const PairCoord& pcd, BwdIn<NB>& in, int lane) {
+template <bool RC, bool M4>
+__device__ __forceinline__ void bwd_issue(const HeroAttn& a, const PairCoord& pcd, BwdIn& in, int lane) {
   const int half = lane >> 5, l31 = lane & 31;
-  const int s = pcd.s, h = pcd.h;
-  const HeadLay hl = head_lay(a, h);
-  const int ld = hl.ld, D = hl.ldc;
-  const int row0 = pcd.row0, L = pcd.L;
-  in.s = s; in.h = h; in.row0 = row0; in.L = L; in.on = pcd.on;
-  const int Lc = pcd.on ? L : 1;                         // not owned: every load goes to row 0 (see fwd_issue)
-  const bf16_t* rowp = static_cast<const bf16_t*>(a.qkv) + (size_t)(pcd.on ? row0 : 0) * ld;
-  const bf16_t* qp = rowp + hl.q;
-  const bf16_t* kp = rowp + hl.k;
-  const bf16_t* vp = rowp + hl.v;
-  const bf16_t* op = static_cast<const bf16_t*>(a.dctx) + (size_t)(pcd.on ? row0 : 0) * D + hl.c;
+  const int D = a.H * 64, ld = 3 * D;
+  in.s = pcd.s; in.h = pcd.h; in.row0 = pcd.row0; in.L = pcd.L; in.on = pcd.on;
+  const int Lc = pcd.on ? pcd.L : 1;                     // not owned: every load goes to row 0 (see fwd_issue)
+  const bf16_t* qp = static_cast<const bf16_t*>(a.qkv) + (size_t)(pcd.on ? pcd.row0 : 0) * ld + pcd.h * 64;
+  const bf16_t* kp = qp + D;
+  const bf16_t* vp = qp + 2 * D;
+  const bf16_t* op = static_cast<const bf16_t*>(a.dctx) + (size_t)(pcd.on ? pcd.row0 : 0) * D + pcd.h * 64;
   const int c = (lane & 7) * 8;
 #pragma unroll
-  for (int it = 0; it < 4 * NB; ++it) {
+  for (int it = 0; it < 4; ++it) {
     const int r = min(it * 8 + (lane >> 3), Lc - 1);
     in.kr[it] = *reinterpret_cast<const uint4*>(kp + (size_t)r * ld + c);
     in.qr[it] = *reinterpret_cast<const uint4*>(qp + (size_t)r * ld + c);
     in.orw[it] = *reinterpret_cast<const uint4*>(op + (size_t)r * D + c);
   }
 #pragma unroll
-  for (int t = 0; t < NB; ++t)
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) in.vf[t][ks] = gfrag(vp, ld, 32 * t + l31, Lc, ks, half);
+  for (int ks = 0; ks < 4; ++ks) in.vf[ks] = gfrag(vp, ld, l31, Lc, ks, half);
   if constexpr (RC) {
-    load_mask<NB, M4>(a, pcd, in.mk, lane);
-#pragma unroll
-    for (int it = 0; it < NB; ++it)
-      in.st[it] = *reinterpret_cast<const float2*>(a.stats + ((size_t)(s * a.H + h) * a.L + min(32 * it + l31, Lc - 1)) * 2);
+    load_mask<1, M4>(a, pcd, in.mk, lane);
+    in.st = *reinterpret_cast<const float2*>(a.stats + ((size_t)(pcd.s * a.H + pcd.h) * a.L + min(l31, Lc - 1)) * 2);
   }
 }
 
-template <int NB>
-__device__ __forceinline__ void bwd_stage(const BwdIn<NB>& in, bf16_t* Ks, bf16_t* Qs, bf16_t* Os, int lane) {
+__device__ __forceinline__ void bwd_stage(const BwdIn& in, bf16_t* Ks, bf16_t* Qs, bf16_t* Os, int lane) {
   const int c = (lane & 7) * 8;
   const uint4 z = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
-  for (int it = 0; it < 4 * NB; ++it) {
+  for (int it = 0; it < 4; ++it) {
     const int r = it * 8 + (lane >> 3);
     uint4 k4 = in.kr[it], q4 = in.qr[it], o4 = in.orw[it];     // by value: a select between two uint4 objects takes their
     if (r >= in.L) { k4 = z; q4 = z; o4 = z; }                 // addresses and parks the whole register set in scratch
@@ -381,252 +365,107 @@ __device__ __forceinline__ void bwd_stage(const BwdIn<NB>& in, bf16_t* Ks, bf16_
   }
 }
 
-template <int NB, bool RC>       // RC: no saved probabilities - rebuilt from q, k and the saved row statistics
-__device__ __forceinline__ void bwd_compute(const HeroAttn& a, const BwdIn<NB>& in, bf16_t* Ks, const DropCtx& drop, int lane) {
-  constexpr int R = 32 * NB;
-  constexpr int PS = R + 8;                              // [query][key] bf16 row stride (elements)
-  const int half = lane >> 5, l31 = lane & 31;
-  const int s = in.s, h = in.h, row0 = in.row0, L = in.L;
-  const HeadLay hl = head_lay(a, h);
-  const int ld = hl.ld;
-  const int Lm = a.L, Lp = (Lm + 3) & ~3;
-  bf16_t* Qs = Ks + R * RS;
-  bf16_t* Os = Qs + R * RS;
-  bf16_t* Pl = Os + R * RS;                              // dropped probabilities [i][j]
-  bf16_t* Sl = Pl + R * PS;                              // dS [i][j]
+constexpr int PS1 = 40;                                  // one-wave backward: [query][key] bf16 row stride (elements) of the P / dS tiles
+constexpr int BWD_WAVE_BYTES = 3 * 32 * RS * 2 + 2 * 32 * PS1 * 2;      // K, Q, dO head tiles + P, dS
 
-  // ---- dP^T[jt][it] = V dO^T (dP w.r.t. the DROPPED probabilities)
-  f32x16_t dp[NB][NB];
+template <bool RC>       // RC: no saved probabilities - rebuilt from q, k and the saved row statistics
+__device__ __forceinline__ void bwd_compute(const HeroAttn& a, const BwdIn& in, bf16_t* Ks, const DropCtx& drop, int lane) {
+  const int half = lane >> 5, l31 = lane & 31;
+  const int L = in.L, D = a.H * 64, ld = 3 * D;
+  bf16_t* Qs = Ks + 32 * RS;
+  bf16_t* Os = Qs + 32 * RS;
+  bf16_t* Pl = Os + 32 * RS;                             // dropped probabilities [i][j]
+  bf16_t* Sl = Pl + 32 * PS1;                            // dS [i][j]
+
+  // ---- dP^T = V dO^T (dP w.r.t. the DROPPED probabilities)
+  f32x16_t dp[1];
   {
+    bf16x8_t of[4];
 #pragma unroll
-    for (int it = 0; it < NB; ++it) {
-      bf16x8_t of[4];
+    for (int ks = 0; ks < 4; ++ks) of[ks] = lfrag(Os, l31, ks, half);
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) of[ks] = lfrag(Os, 32 * it + l31, ks, half);
+    for (int e = 0; e < 16; ++e) dp[0][e] = 0.f;
 #pragma unroll
-      for (int jt = 0; jt < NB; ++jt) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) dp[jt][it][e] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) dp[jt][it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(in.vf[jt][ks], of[ks], dp[jt][it], 0, 0, 0);
-      }
-    }
+    for (int ks = 0; ks < 4; ++ks) dp[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(in.vf[ks], of[ks], dp[0], 0, 0, 0);
   }
-  // Without saved probabilities: S^T = K Q^T again, from the staged tiles - the same MFMAs on the same operands as the
-  // forward's, then the same scale / mask / exp / normalise with the saved row maximum and 1 / row sum: bit-identical P.
-  constexpr bool recompute = RC;
-  f32x16_t sc[RC ? NB : 1][RC ? NB : 1];
-  const float (&mk)[NB][16] = in.mk;
+  // Without saved probabilities: S^T = K Q^T again, from the staged tiles (probs_row)
+  f32x16_t sc[1];
   if constexpr (RC) {
+    bf16x8_t qf[4];
 #pragma unroll
-    for (int it = 0; it < NB; ++it) {
-      bf16x8_t qf[4];
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = lfrag(Qs, l31, ks, half);
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) qf[ks] = lfrag(Qs, 32 * it + l31, ks, half);
+    for (int e = 0; e < 16; ++e) sc[0][e] = 0.f;
 #pragma unroll
-      for (int jt = 0; jt < NB; ++jt) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sc[jt][it][e] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-          sc[jt][it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lfrag(Ks, 32 * jt + l31, ks, half), qf[ks], sc[jt][it], 0, 0, 0);
-      }
-    }
+    for (int ks = 0; ks < 4; ++ks)
+      sc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lfrag(Ks, l31, ks, half), qf[ks], sc[0], 0, 0, 0);
   }
   // K^T fragments for dQ (same key <-> k-slot assignment as the forward's V^T)
-  bf16x8_t kf[2][NB][2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int jt = 0; jt < NB; ++jt)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int r0 = 32 * jt + 16 * ks + 4 * half;
-        kf[dt][jt][ks] = tr_frag(tr_addr(Ks, RS * 2, r0, dt, lane), tr_addr(Ks, RS * 2, r0 + 8, dt, lane));
-      }
+  bf16x8_t kf[2][1][2];
+  tr_frags<1>(Ks, kf, half, lane);
 
-  bf16_t* dqrow = static_cast<bf16_t*>(a.dqkv) + (size_t)row0 * ld;
-  bf16_t* dq = dqrow + hl.q;
-  f32x16_t gq[2][NB];
-#pragma unroll
-  for (int it = 0; it < NB; ++it) {
-    const int i = 32 * it + l31;
-    const float* prow = recompute ? nullptr : a.probs + ((size_t)(s * a.H + h) * Lm + min(i, L - 1)) * Lm;
-    const uint64_t drow = ((uint64_t)(s * a.H + h) * Lm + i) * (uint64_t)Lp;
-    float pr[NB][16], ds[NB][16];
-    // The saved probabilities of this lane's 16 accumulator slots are 4 runs of 4 consecutive columns: four 16-byte
-    // loads when the row stride allows it, used UNCONDITIONALLY (masked by a multiplication).  Written as
-    // `(i < L && j < L) ? prow[j] : 0` the compiler sank each of the 16 scalar loads into its own conditional block,
-    // each followed by s_waitcnt vmcnt(0): 16 serial round trips per 32-row block.
-    const float rowok = i < L ? 1.f : 0.f;
-    if constexpr (RC) {
-      const float2 st = in.st[it];
-#pragma unroll
-      for (int jt = 0; jt < NB; ++jt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = 32 * jt + acc_row(r, half);
-          const float v = j < L ? fmaf(sc[jt][it][r], a.scale, mk[jt][r]) : -3.0e38f;
-          const float e = j < L ? __expf(v - st.x) : 0.f;
-          pr[jt][r] = e * st.y * rowok;
-        }
-    } else if ((Lm & 3) == 0) {
-#pragma unroll
-      for (int jt = 0; jt < NB; ++jt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int j0 = 32 * jt + 8 * q + 4 * half;
-          const float4 v = *reinterpret_cast<const float4*>(prow + min(j0, Lm - 4));
-          pr[jt][4 * q + 0] = v.x * (j0 + 0 < L ? rowok : 0.f);
-          pr[jt][4 * q + 1] = v.y * (j0 + 1 < L ? rowok : 0.f);
-          pr[jt][4 * q + 2] = v.z * (j0 + 2 < L ? rowok : 0.f);
-          pr[jt][4 * q + 3] = v.w * (j0 + 3 < L ? rowok : 0.f);
-        }
-    } else {
-#pragma unroll
-      for (int jt = 0; jt < NB; ++jt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = 32 * jt + acc_row(r, half);
-          pr[jt][r] = prow[min(j, L - 1)] * (j < L ? rowok : 0.f);
-        }
-    }
-    float delta = 0.f;
-#pragma unroll
-    for (int jt = 0; jt < NB; ++jt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int j0 = 32 * jt + 8 * q + 4 * half;
-        float4 m = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (drop.on()) m = drop.mask4((drow + j0) >> 2);
-        const float mm[4] = {m.x, m.y, m.z, m.w};
-        float pd[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float g = dp[jt][it][4 * q + e] * mm[e];       // dP w.r.t. the softmax output
-          ds[jt][4 * q + e] = g;
-          delta = fmaf(g, pr[jt][4 * q + e], delta);
-          pd[e] = pr[jt][4 * q + e] * mm[e];
-        }
-        st_bf4(Pl + i * PS + j0, pd[0], pd[1], pd[2], pd[3]);
-      }
-    delta += xhalf(delta);
-#pragma unroll
-    for (int jt = 0; jt < NB; ++jt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ds[jt][r] = pr[jt][r] * (ds[jt][r] - delta) * a.scale;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        st_bf4(Sl + i * PS + 32 * jt + 8 * q + 4 * half, ds[jt][4 * q], ds[jt][4 * q + 1], ds[jt][4 * q + 2], ds[jt][4 * q + 3]);
-    }
-    // dQ^T[dt][it] = K^T dS^T, B straight from the registers
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) gq[dt][it][e] = 0.f;
-#pragma unroll
-      for (int jt = 0; jt < NB; ++jt)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-          gq[dt][it] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[dt][jt][ks], pack8(&ds[jt][8 * ks]), gq[dt][it], 0, 0, 0);
-    }
-  }
-  // dQ leaves through the K tile: its row fragments (RC) and transposed fragments (kf) were read before the loop above.  The
+  bf16_t* dq = static_cast<bf16_t*>(a.dqkv) + (size_t)in.row0 * ld + in.h * 64;
+  f32x16_t gq[2];
+  bwd_row<1, RC>(a, in.s, in.h, L, l31, dp, sc, in.mk, in.st, kf, Pl, Sl, PS1, drop, gq, half);
+  // dQ leaves through the K tile: its row fragments (RC) and transposed fragments (kf) were read before bwd_row.  The
   // sync that publishes P and dS to the wave publishes the staged dQ as well.
-  stage_headT<NB>(Ks, gq, lane);
+  stage_tileT(Ks, gq[0], gq[1], lane);
 
-  // ---- dV^T = dO^T P_dropped, dK^T = Q^T dS: contraction over the queries, k-slot e of step ks <-> query
-  //      32 it + 16 ks + 8 half + e for both operands (two transpose reads of 4 rows each)
+  // ---- dV^T = dO^T P_dropped, dK^T = Q^T dS: contraction over the queries
   wave_sync_lds();
-  store_head<NB>(dq, ld, L, Ks, lane);
-  f32x16_t gv[2][NB], gk[2][NB];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int jt = 0; jt < NB; ++jt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { gv[dt][jt][e] = 0.f; gk[dt][jt][e] = 0.f; }
-#pragma unroll
-  for (int it = 0; it < NB; ++it)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int r0 = 32 * it + 16 * ks + 8 * half;
-      bf16x8_t of[2], qf[2];
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        of[dt] = tr_frag(tr_addr(Os, RS * 2, r0, dt, lane), tr_addr(Os, RS * 2, r0 + 4, dt, lane));
-        qf[dt] = tr_frag(tr_addr(Qs, RS * 2, r0, dt, lane), tr_addr(Qs, RS * 2, r0 + 4, dt, lane));
-      }
-#pragma unroll
-      for (int jt = 0; jt < NB; ++jt) {
-        const bf16x8_t pf = tr_frag(tr_addr(Pl, PS * 2, r0, jt, lane), tr_addr(Pl, PS * 2, r0 + 4, jt, lane));
-        const bf16x8_t sf = tr_frag(tr_addr(Sl, PS * 2, r0, jt, lane), tr_addr(Sl, PS * 2, r0 + 4, jt, lane));
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          gv[dt][jt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(of[dt], pf, gv[dt][jt], 0, 0, 0);
-          gk[dt][jt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[dt], sf, gk[dt][jt], 0, 0, 0);
-        }
-      }
-    }
+  store_rows32(dq, ld, L, 0, Ks, lane);
+  f32x16_t gv[2], gk[2];
+  dkv_mfma<1>(Os, Qs, Pl, Sl, PS1, 0, gv, gk, half, lane);
   // dK through the Q tile, dV through the dO tile: the last transposed reads of both are done (tr_frag waits for its data).
   // The next pair's bwd_stage sits behind the caller's wave_sync_lds.
-  stage_headT<NB>(Qs, gk, lane);
-  stage_headT<NB>(Os, gv, lane);
+  stage_tileT(Qs, gk[0], gk[1], lane);
+  stage_tileT(Os, gv[0], gv[1], lane);
   wave_sync_lds();
-  store_head<NB>(dqrow + hl.k, ld, L, Qs, lane);
-  store_head<NB>(dqrow + hl.v, ld, L, Os, lane);
+  store_rows32(dq + D, ld, L, 0, Qs, lane);
+  store_rows32(dq + 2 * D, ld, L, 0, Os, lane);
 }
 
-template <int NB, int WPB, bool RC, int CLS, int PPW, bool M4>       // second bound: at least two waves per SIMD (<= 256 registers) for the multi-pair kernels
+template <int WPB, bool RC, int CLS, int PPW, bool M4>       // second bound: at least two waves per SIMD (<= 256 registers) for the multi-pair kernels
 __global__ __launch_bounds__(64 * WPB, (PPW > 1 ? 2 : 1)) void attn_mfma_bwd_kernel(HeroAttn a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int R = 32 * NB;
-  constexpr int WAVE_BYTES = 3 * R * RS * 2 + 2 * R * (R + 8) * 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * WPB + wave), nw = gridDim.x * WPB;      // uniform: scalar loads (see the forward kernel)
   if (wid >= a.S * a.H) return;
   DropCtx drop(a.dropout);
-  bf16_t* Ks = reinterpret_cast<bf16_t*>(smem + wave * WAVE_BYTES);
+  bf16_t* Ks = reinterpret_cast<bf16_t*>(smem + wave * BWD_WAVE_BYTES);
   const PairCoord c0 = pair_coord<CLS>(a, wid), c1 = pair_coord<CLS>(a, PPW > 1 ? wid + nw : wid),
                   c2 = pair_coord<CLS>(a, PPW > 2 ? wid + 2 * nw : wid);
-  BwdIn<NB> A, B;
-  bf16_t* Qs = Ks + R * RS;
-  bf16_t* Os = Qs + R * RS;
-#ifdef HERO_ATTN_LATE_ISSUE
-  constexpr bool LATE = true;
-#else
-  constexpr bool LATE = false;
-#endif
-  bwd_issue<NB, RC, M4>(a, c0, A, lane);
-  if (PPW > 1 && !LATE) bwd_issue<NB, RC, M4>(a, c1, B, lane);             // next pair's loads fly during this pair
-  bwd_stage<NB>(A, Ks, Qs, Os, lane);
+  BwdIn A, B;
+  bf16_t* Qs = Ks + 32 * RS;
+  bf16_t* Os = Qs + 32 * RS;
+  bwd_issue<RC, M4>(a, c0, A, lane);
+  if (PPW > 1) bwd_issue<RC, M4>(a, c1, B, lane);      // next pair's loads fly during this pair
+  bwd_stage(A, Ks, Qs, Os, lane);
   wave_sync_lds();
-  if (PPW > 1 && LATE) bwd_issue<NB, RC, M4>(a, c1, B, lane);
-  if (A.on) bwd_compute<NB, RC>(a, A, Ks, drop, lane);
+  if (A.on) bwd_compute<RC>(a, A, Ks, drop, lane);
   if (PPW > 1) {
-    if (PPW > 2) bwd_issue<NB, RC, M4>(a, c2, A, lane);
+    if (PPW > 2) bwd_issue<RC, M4>(a, c2, A, lane);
     wave_sync_lds();                                   // the previous pair's reads of the tiles are done
-    bwd_stage<NB>(B, Ks, Qs, Os, lane);
+    bwd_stage(B, Ks, Qs, Os, lane);
     wave_sync_lds();
-    if (B.on) bwd_compute<NB, RC>(a, B, Ks, drop, lane);
+    if (B.on) bwd_compute<RC>(a, B, Ks, drop, lane);
   }
   if (PPW > 2) {
     wave_sync_lds();
-    bwd_stage<NB>(A, Ks, Qs, Os, lane);
+    bwd_stage(A, Ks, Qs, Os, lane);
     wave_sync_lds();
-    if (A.on) bwd_compute<NB, RC>(a, A, Ks, drop, lane);
+    if (A.on) bwd_compute<RC>(a, A, Ks, drop, lane);
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// 64-row class (32 < L <= 64), round 5: TWO waves per (sequence, head) pair.  The one-wave kernels above hold a 64 x 64
-// problem in one wave: 270-340 registers = one wave per SIMD, four pairs in flight per CU, 28 / 50 us per layer forward /
-// backward on the ragged TVR batch (profiles/r04_kernel_stats_D2r.csv) - a third of its sequences.  Here wave w of a pair
-// owns QUERY tile w for everything that is per query (S^T, softmax, ctx / dP, dS, dQ) and KEY tile w for the two products
-// that contract over the queries (dK, dV); K / Q / dO / V are staged once per pair, half the rows by each wave; workgroup
-// barriers separate the phases.  Same MFMAs on the same operands in the same order as the one-wave kernels: bit-identical
-// results.  One pair per workgroup (128 threads); the backward's P tile reuses the K tile's LDS once both waves have read it
-// (37 KB per pair: four pairs = eight waves per CU).
+// 64-row class (32 < L <= 64): TWO waves per (sequence, head) pair.  One wave holding a 64 x 64 problem needed 270-340
+// registers = one wave per SIMD, four pairs in flight per CU, 28 / 50 us per layer forward / backward on the ragged TVR batch
+// (profiles/r04_kernel_stats_D2r.csv) - a third of its sequences.  Here wave w of a pair owns QUERY tile w for everything that
+// is per query (S^T, softmax, ctx / dP, dS, dQ) and KEY tile w for the two products that contract over the queries (dK, dV);
+// K / Q / dO / V are staged once per pair, half the rows by each wave; workgroup barriers separate the phases.  One pair per
+// workgroup (128 threads); the backward's P tile reuses the K tile's LDS once both waves have read it (37 KB per pair: four
+// pairs = eight waves per CU).
 // ------------------------------------------------------------------------------------------------------------------
 template <int CLS, bool M4>
 __global__ __launch_bounds__(128, 2) void attn_mfma_fwd2_kernel(HeroAttn a) {
@@ -635,7 +474,6 @@ __global__ __launch_bounds__(128, 2) void attn_mfma_fwd2_kernel(HeroAttn a) {
   const PairCoord pc = pair_coord<CLS>(a, __builtin_amdgcn_readfirstlane(blockIdx.x));
   if (!pc.on) return;                                   // uniform across the WORKGROUP (both waves share the pair): no barrier is skipped by one wave only
   const int s = pc.s, h = pc.h, row0 = pc.row0, L = pc.L, D = a.H * 64, ld = 3 * D;
-  const int Lm = a.L, Lp = (Lm + 3) & ~3;
   DropCtx drop(a.dropout);
   bf16_t* Vs = reinterpret_cast<bf16_t*>(smem);
   const bf16_t* qp = static_cast<const bf16_t*>(a.qkv) + (size_t)row0 * ld + h * 64;
@@ -673,82 +511,12 @@ __global__ __launch_bounds__(128, 2) void attn_mfma_fwd2_kernel(HeroAttn a) {
   }
   __syncthreads();                                       // the V tile is staged (both halves)
   bf16x8_t vf[2][2][2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int r0 = 32 * jt + 16 * ks + 4 * half;
-        vf[dt][jt][ks] = tr_frag(tr_addr(Vs, RS * 2, r0, dt, lane), tr_addr(Vs, RS * 2, r0 + 8, dt, lane));
-      }
+  tr_frags<2>(Vs, vf, half, lane);
   __syncthreads();                                       // both waves hold their V^T fragments: rows [32 w, 32 w + 32) of the tile now
                                                          // belong to wave w, which stages its ctx rows there (here, next to the first
                                                          // barrier, the two waves arrive together and no store is in flight yet)
-  const int i = 32 * w + l31;
-  float p[2][16];
-  float mx = -3.0e38f;
-#pragma unroll
-  for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int j = 32 * jt + acc_row(r, half);
-      const float v = j < L ? fmaf(sc[jt][r], a.scale, mk[jt][r]) : -3.0e38f;
-      p[jt][r] = v;
-      mx = fmaxf(mx, v);
-    }
-  mx = fmaxf(mx, xhalf(mx));
-  float sum = 0.f;
-#pragma unroll
-  for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int j = 32 * jt + acc_row(r, half);
-      const float e = j < L ? __expf(p[jt][r] - mx) : 0.f;
-      p[jt][r] = e;
-      sum += e;
-    }
-  sum += xhalf(sum);
-  const float inv = 1.f / sum;
-  if (a.stats && half == 0 && i < L)
-    *reinterpret_cast<float2*>(a.stats + ((size_t)(s * a.H + h) * Lm + i) * 2) = make_float2(mx, inv);
-  float* prow = a.probs ? a.probs + ((size_t)(s * a.H + h) * Lm + min(i, L - 1)) * Lm : nullptr;
-  const uint64_t drow = ((uint64_t)(s * a.H + h) * Lm + i) * (uint64_t)Lp;
-#pragma unroll
-  for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int j0 = 32 * jt + 8 * q + 4 * half;
-      float4 m = make_float4(1.f, 1.f, 1.f, 1.f);
-      if (drop.on()) m = drop.mask4((drow + j0) >> 2);
-      const float mm[4] = {m.x, m.y, m.z, m.w};
-      float pr4[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        pr4[e] = p[jt][4 * q + e] * inv;
-        p[jt][4 * q + e] = pr4[e] * mm[e];
-      }
-      if (prow && i < L) {
-        if ((Lm & 3) == 0 && j0 + 3 < L) {
-          *reinterpret_cast<float4*>(prow + j0) = make_float4(pr4[0], pr4[1], pr4[2], pr4[3]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (j0 + e < L) prow[j0 + e] = pr4[e];
-        }
-      }
-    }
   f32x16_t cx[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) cx[dt][e] = 0.f;
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        cx[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[dt][jt][ks], pack8(&p[jt][8 * ks]), cx[dt], 0, 0, 0);
-  }
+  fwd_row<2>(a, s, h, L, 32 * w + l31, sc, mk, vf, drop, cx, half);
   stage_tileT(Vs + 32 * w * RS, cx[0], cx[1], lane);
   wave_sync_lds();
   store_rows32(static_cast<bf16_t*>(a.ctx) + (size_t)row0 * D + h * 64, D, L, 32 * w, Vs + 32 * w * RS, lane);
@@ -762,7 +530,7 @@ __global__ __launch_bounds__(128, 2) void attn_mfma_bwd2_kernel(HeroAttn a) {
   const PairCoord pc = pair_coord<CLS>(a, __builtin_amdgcn_readfirstlane(blockIdx.x));
   if (!pc.on) return;                                   // uniform across the workgroup
   const int s = pc.s, h = pc.h, row0 = pc.row0, L = pc.L, D = a.H * 64, ld = 3 * D;
-  const int Lm = a.L, Lp = (Lm + 3) & ~3;
+  const int Lm = a.L;
   DropCtx drop(a.dropout);
   bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);
   bf16_t* Qs = Ks + R * RS;
@@ -838,119 +606,15 @@ __global__ __launch_bounds__(128, 2) void attn_mfma_bwd2_kernel(HeroAttn a) {
   }
   // K^T fragments for dQ (same key <-> k-slot assignment as the forward's V^T)
   bf16x8_t kf[2][2][2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int r0 = 32 * jt + 16 * ks + 4 * half;
-        kf[dt][jt][ks] = tr_frag(tr_addr(Ks, RS * 2, r0, dt, lane), tr_addr(Ks, RS * 2, r0 + 8, dt, lane));
-      }
+  tr_frags<2>(Ks, kf, half, lane);
   __syncthreads();                                       // B: both waves are done with the K tile - P may overwrite it
   bf16_t* dq = static_cast<bf16_t*>(a.dqkv) + (size_t)row0 * ld + h * 64;
   f32x16_t gq[2];                                        // dQ^T of query tile w: kept until all four tiles are free (after barrier D)
-  {
-    const float* prow = RC ? nullptr : a.probs + ((size_t)(s * a.H + h) * Lm + min(i, L - 1)) * Lm;
-    const uint64_t drow = ((uint64_t)(s * a.H + h) * Lm + i) * (uint64_t)Lp;
-    float pr[2][16], ds[2][16];
-    const float rowok = i < L ? 1.f : 0.f;
-    if constexpr (RC) {
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = 32 * jt + acc_row(r, half);
-          const float v = j < L ? fmaf(sc[jt][r], a.scale, mk[jt][r]) : -3.0e38f;
-          const float e = j < L ? __expf(v - st.x) : 0.f;
-          pr[jt][r] = e * st.y * rowok;
-        }
-    } else if ((Lm & 3) == 0) {
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int j0 = 32 * jt + 8 * q + 4 * half;
-          const float4 v = *reinterpret_cast<const float4*>(prow + min(j0, Lm - 4));
-          pr[jt][4 * q + 0] = v.x * (j0 + 0 < L ? rowok : 0.f);
-          pr[jt][4 * q + 1] = v.y * (j0 + 1 < L ? rowok : 0.f);
-          pr[jt][4 * q + 2] = v.z * (j0 + 2 < L ? rowok : 0.f);
-          pr[jt][4 * q + 3] = v.w * (j0 + 3 < L ? rowok : 0.f);
-        }
-    } else {
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = 32 * jt + acc_row(r, half);
-          pr[jt][r] = prow[min(j, L - 1)] * (j < L ? rowok : 0.f);
-        }
-    }
-    float delta = 0.f;
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int j0 = 32 * jt + 8 * q + 4 * half;
-        float4 m = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (drop.on()) m = drop.mask4((drow + j0) >> 2);
-        const float mm[4] = {m.x, m.y, m.z, m.w};
-        float pd[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float g = dp[jt][4 * q + e] * mm[e];
-          ds[jt][4 * q + e] = g;
-          delta = fmaf(g, pr[jt][4 * q + e], delta);
-          pd[e] = pr[jt][4 * q + e] * mm[e];
-        }
-        st_bf4(Pl + i * PS + j0, pd[0], pd[1], pd[2], pd[3]);
-      }
-    delta += xhalf(delta);
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ds[jt][r] = pr[jt][r] * (ds[jt][r] - delta) * a.scale;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        st_bf4(Sl + i * PS + 32 * jt + 8 * q + 4 * half, ds[jt][4 * q], ds[jt][4 * q + 1], ds[jt][4 * q + 2], ds[jt][4 * q + 3]);
-    }
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) gq[dt][e] = 0.f;
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-          gq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[dt][jt][ks], pack8(&ds[jt][8 * ks]), gq[dt], 0, 0, 0);
-    }
-  }
+  bwd_row<2, RC>(a, s, h, L, i, dp, sc, mk, st, kf, Pl, Sl, PS, drop, gq, half);
   __syncthreads();                                       // C: P and dS of all 64 queries are in the LDS
   // ---- phase 2, key tile w: dV^T = dO^T P_dropped, dK^T = Q^T dS over the 64 queries
   f32x16_t gv[2], gk[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { gv[dt][e] = 0.f; gk[dt][e] = 0.f; }
-#pragma unroll
-  for (int it = 0; it < 2; ++it)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int r0 = 32 * it + 16 * ks + 8 * half;
-      bf16x8_t of[2], qf[2];
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        of[dt] = tr_frag(tr_addr(Os, RS * 2, r0, dt, lane), tr_addr(Os, RS * 2, r0 + 4, dt, lane));
-        qf[dt] = tr_frag(tr_addr(Qs, RS * 2, r0, dt, lane), tr_addr(Qs, RS * 2, r0 + 4, dt, lane));
-      }
-      const bf16x8_t pf = tr_frag(tr_addr(Pl, PS * 2, r0, w, lane), tr_addr(Pl, PS * 2, r0 + 4, w, lane));
-      const bf16x8_t sf = tr_frag(tr_addr(Sl, PS * 2, r0, w, lane), tr_addr(Sl, PS * 2, r0 + 4, w, lane));
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        gv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(of[dt], pf, gv[dt], 0, 0, 0);
-        gk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[dt], sf, gk[dt], 0, 0, 0);
-      }
-    }
+  dkv_mfma<2>(Os, Qs, Pl, Sl, PS, w, gv, gk, half, lane);
   // Every tile is an operand of both waves until here (P and dS of all queries, Q and dO of all rows), so no tile is free when
   // dQ is ready: the three outputs are staged together behind one more barrier, each wave in rows [32 w, 32 w + 32) of a tile
   // (dQ in the P tile, dK in the Q tile, dV in the dO tile).
@@ -991,23 +655,22 @@ static int cu_count() {
   return v > 0 ? v : 256;
 }
 
-template <int NB, int WPB, int CLS, int PPW, bool M4>
+template <int WPB, int CLS, int PPW, bool M4>
 int launch_ppw(const HeroAttn& a, bool bwd, hipStream_t s) {
-  constexpr int R = 32 * NB;
   const int pairs = a.S * a.H;
   const int waves = (pairs + PPW - 1) / PPW;
   const int grid = (waves + WPB - 1) / WPB;
   if (bwd) {
-    const size_t lds = (size_t)WPB * (3 * R * RS * 2 + 2 * R * (R + 8) * 2);
+    const size_t lds = (size_t)WPB * BWD_WAVE_BYTES;
     if (lds > 65536) {
-      HERO_ENSURE_LDS((&attn_mfma_bwd_kernel<NB, WPB, false, CLS, PPW, M4>), lds, "attn_mfma_bwd_kernel");
-      HERO_ENSURE_LDS((&attn_mfma_bwd_kernel<NB, WPB, true, CLS, PPW, M4>), lds, "attn_mfma_bwd_kernel");
+      HERO_ENSURE_LDS((&attn_mfma_bwd_kernel<WPB, false, CLS, PPW, M4>), lds, "attn_mfma_bwd_kernel");
+      HERO_ENSURE_LDS((&attn_mfma_bwd_kernel<WPB, true, CLS, PPW, M4>), lds, "attn_mfma_bwd_kernel");
     }
-    if (a.probs) hipLaunchKernelGGL((attn_mfma_bwd_kernel<NB, WPB, false, CLS, PPW, M4>), dim3(grid), dim3(64 * WPB), lds, s, a);
-    else hipLaunchKernelGGL((attn_mfma_bwd_kernel<NB, WPB, true, CLS, PPW, M4>), dim3(grid), dim3(64 * WPB), lds, s, a);
+    if (a.probs) hipLaunchKernelGGL((attn_mfma_bwd_kernel<WPB, false, CLS, PPW, M4>), dim3(grid), dim3(64 * WPB), lds, s, a);
+    else hipLaunchKernelGGL((attn_mfma_bwd_kernel<WPB, true, CLS, PPW, M4>), dim3(grid), dim3(64 * WPB), lds, s, a);
   } else {
-    const size_t lds = (size_t)WPB * R * RS * 2;
-    hipLaunchKernelGGL((attn_mfma_fwd_kernel<NB, WPB, CLS, PPW, M4>), dim3(grid), dim3(64 * WPB), lds, s, a);
+    const size_t lds = (size_t)WPB * 32 * RS * 2;
+    hipLaunchKernelGGL((attn_mfma_fwd_kernel<WPB, CLS, PPW, M4>), dim3(grid), dim3(64 * WPB), lds, s, a);
   }
   return check_launch(bwd ? "hero_attention_bwd(mfma)" : "hero_attention_fwd(mfma)");
 }
@@ -1029,9 +692,9 @@ int launch_m(const HeroAttn& a, bool bwd, hipStream_t s) {
   // waves that drew two or three owned pairs become the tail (ragged TVR batch, backward: 47 us with three pairs per wave on a
   // box where one pair per wave took ~40) - they keep one pair per wave as well.
   const int ppw = g_force_ppw ? g_force_ppw : ((!bwd || CLS != 0) ? 1 : (pairs > 2 * slots ? 3 : (pairs > slots ? 2 : 1)));
-  if (ppw == 3) return launch_ppw<1, WPB, CLS, 3, M4>(a, bwd, s);
-  if (ppw == 2) return launch_ppw<1, WPB, CLS, 2, M4>(a, bwd, s);
-  return launch_ppw<1, WPB, CLS, 1, M4>(a, bwd, s);
+  if (ppw == 3) return launch_ppw<WPB, CLS, 3, M4>(a, bwd, s);
+  if (ppw == 2) return launch_ppw<WPB, CLS, 2, M4>(a, bwd, s);
+  return launch_ppw<WPB, CLS, 1, M4>(a, bwd, s);
 }
 template <int WPB, int CLS>
 int launch(const HeroAttn& a, bool bwd, hipStream_t s) {

@@ -136,7 +136,6 @@ __global__ __launch_bounds__(64 * NB) void attn_long_fwd_kernel(HeroAttn a) {
 
   DropCtx drop(a.dropout);
   float* prow = a.probs ? a.probs + ((size_t)(c.s * a.H + c.h) * c.Lm + min(i, c.L - 1)) * c.Lm : nullptr;
-  const bool vec = (c.Lm & 3) == 0;
   const uint64_t drow = ((uint64_t)(c.s * a.H + c.h) * c.Lm + i) * (uint64_t)c.Lp;
   f32x16_t cx[2];
 #pragma unroll
@@ -146,28 +145,7 @@ __global__ __launch_bounds__(64 * NB) void attn_long_fwd_kernel(HeroAttn a) {
 #pragma unroll
   for (int jt = 0; jt < NB; ++jt) {
     if (jt < c.njt) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int j0 = 32 * jt + 8 * q + 4 * half;
-        float4 m = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (drop.on()) m = drop.mask4((drow + j0) >> 2);
-        const float mm[4] = {m.x, m.y, m.z, m.w};
-        float pr[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          pr[e] = p[jt][4 * q + e] * inv;
-          p[jt][4 * q + e] = pr[e] * mm[e];
-        }
-        if (prow && i < c.L) {
-          if (vec && j0 + 3 < c.L) {
-            *reinterpret_cast<float4*>(prow + j0) = make_float4(pr[0], pr[1], pr[2], pr[3]);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (j0 + e < c.L) prow[j0 + e] = pr[e];
-          }
-        }
-      }
+      emit_probs(p[jt], inv, prow, i, c.Lm, c.L, jt, half, drop, drow);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const int r0 = 32 * jt + 16 * ks + 4 * half;

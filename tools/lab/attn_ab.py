@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Short-sequence attention launches of the bench batch (512 sequences x 24 rows x 12 heads incl. the query group as one
 packed launch; mask, dropout 0.1, row statistics) under 1 / 2 / 3 pairs per wave (hero_attention_force_ppw), hipGraph timing.
-Run once per library build (HERO_HIP_LIB): product, and the -DHERO_ATTN_LATE_ISSUE variant (next pair's loads issued after
-this pair's have landed).  `old` as argv[1]: a tree without the hook (round 4) - one timing."""
+Run once per library build (HERO_HIP_LIB).  `old` as argv[1]: a tree without the hook (round 4) - one timing.
+profiles/r05_attn_ab.txt also holds a late-issue variant (next pair's loads issued after this pair's have landed): that switch
+left the kernels once it was measured; it builds from commit b82a06e or earlier."""
 import os, sys, time
 sys.path.insert(0, os.getcwd())
 import torch

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """VERDICT r5 #2, first lever, priced before it is built: would the short-sequence attention kernels stream faster from per-head
 PANELS ([3][H][M][64] / [H][M][64]) than from the fused projection's rows ([M, 3 x 768]: 128-byte pieces at a 4608-byte stride)?
-The same kernels, compiled twice (product / -DHERO_ATTN_LAB_HEADMAJOR: only the address arithmetic differs; random operands, so
-the numbers are the same work either way), on the bench batch's launch (480 sequences x 24 rows x 12 heads, mask, dropout, row
+The same kernels, compiled twice (product / head-major panels: only the address arithmetic differs; random operands, so the
+numbers are the same work either way), on the bench batch's launch (480 sequences x 24 rows x 12 heads, mask, dropout, row
 statistics), HOT (one buffer set, resident in the 256 MB Infinity Cache) and COLD (a ring of 8 buffer sets = 1.1 GB walked by
 one hipGraph: every launch finds its operands in HBM, as inside the training step).
-Run once per build:  python tools/lab/attn_layout_ab.py ; HERO_HIP_LIB=tools/lab/libhero_headmajor.so python tools/lab/attn_layout_ab.py"""
+Run once per build:  python tools/lab/attn_layout_ab.py ; HERO_HIP_LIB=tools/lab/libhero_headmajor.so python tools/lab/attn_layout_ab.py
+The head-major variant was measured (profiles/r06_attn_layout_ab.txt) and its switch left the kernels: it builds from commit
+b82a06e or earlier.  The product layout's HOT / COLD lines and the `ppw` sweep run on any build."""
 import os, sys, time
 sys.path.insert(0, os.getcwd())
 import torch

@@ -3,6 +3,8 @@
 build (HERO_HIP_LIB), alternating the builds between processes:
   short    the bench batch's launch: 480 sequences x 24 rows + 32 x 15 rows as one packed launch, 12 heads, mask, dropout 0.1,
            row statistics (attn_mfma_fwd_kernel / attn_mfma_bwd_kernel)
+  ragged   480 sequences of 8..48 rows (drawn once, fixed seed) as one packed launch: both length classes at once, the one-wave
+           kernels on the sequences of <= 32 rows (CLS = 1) and the two-wave kernels on the longer ones (CLS = 2)
   64-row   the Temporal Transformer's: 32 x 60 rows (attn_mfma_fwd2_kernel / attn_mfma_bwd2_kernel)
   long     32 x 100 and 32 x 256 rows, saved probabilities (attn_long_*)"""
 import os, sys, time
@@ -57,6 +59,7 @@ def one(name, lens, Lmax, packed):
 
 tag = os.environ.get("HERO_HIP_LIB", "product").split("/")[-1]
 one("short 480x24+32x15", [24] * 480 + [15] * 32, 24, True)
+one("ragged 480x(8..48)", torch.randint(8, 49, (480,), generator=torch.Generator().manual_seed(5)).tolist(), 48, True)
 one("64-row 32x60", [60] * 32, 60, False)
 one("long 32x100", [100] * 32, 100, False)
 one("long 32x256", [256] * 32, 256, False)
