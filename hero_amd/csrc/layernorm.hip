@@ -5,30 +5,54 @@
 //           front (SubEmbeddings / ImageEmbeddings / FrameEmbeddings sums) and dropout behind.
 // backward: dx with the same row-in-registers scheme; dgamma/dbeta and plain bias gradients by a
 //           two-stage deterministic column reduction (partials in a caller workspace, no atomics).
+//
+// Every row body is written once and compiled in two forms (template parameter FULL):
+//   general       any cols % 4 == 0: a chunk past the row end reads a clamped address and counts as 0 (forward) or is skipped
+//                 (backward); ln_fwd_kernel, ln_bwd_dx_kernel, ln_bwd_fused_kernel
+//   straight-line cols == VPL * 256, known at compile time: no per-chunk branches, so all loads of a row are in flight
+//                 together; ln_fwd_full_kernel, ln_bwd_fused_full_kernel
+// ln_fwd_row / ln_bwd_row are the rows, ln_bwd_fused the grid-stride walk with its column partials, colsum_chunk / colsum_fold
+// the two stages of every column sum (colred_*: LayerNorm's dgamma / dbeta and hero_colsum; colsum_multi_*: many sums at once).
 #include "common.h"
 
 namespace hero {
 
-// General forward (any cols % 4 == 0, optional x, up to three gathered table rows).  Written in PHASES so that the
-// loads of a phase are in flight together: per-chunk branches (`if (c < cols)`, `if (x)`, `if (t[k])`) make every
-// chunk a basic block and the compiler waits vmcnt(0) right after each load (68 serial round trips for a 4352-wide
-// row).  A chunk past the row reads a clamped address and is multiplied by 0.
-template <typename TX, typename TY, int VPL>
-__global__ __launch_bounds__(256) void ln_fwd_kernel(HeroLnFwd a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int row = blockIdx.x * 4 + wave;
-  if (row >= a.rows) return;
-  const int cols = a.cols;
+__device__ __forceinline__ void add4(float4& s, const float4& v) { s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+// v *= the dropout mask of the 4-element group at (row, c) of a [rows, cols] tensor
+__device__ __forceinline__ void ln_mask4(float4& v, const DropCtx& drop, int row, int cols, int c) {
+  const float4 m = drop.mask4(((uint64_t)row * (uint64_t)cols + (uint64_t)c) >> 2);
+  v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
+}
+
+// gamma / beta of chunks i0 .. i0 + GRP - 1
+template <int VPL, int GRP>
+__device__ __forceinline__ void ln_fwd_gamma_beta(const HeroLnFwd& a, const int (&cc)[VPL], int i0, float4 (&g)[GRP], float4 (&b)[GRP]) {
+#pragma unroll
+  for (int u = 0; u < GRP; ++u)
+    if (i0 + u < VPL) {
+      g[u] = *reinterpret_cast<const float4*>(a.gamma + cc[i0 + u]);
+      b[u] = *reinterpret_cast<const float4*>(a.beta + cc[i0 + u]);
+    }
+}
+
+// One forward row.  Written in PHASES so that the loads of a phase are in flight together: per-chunk branches
+// (`if (c < cols)`, `if (x)`, `if (t[k])`) make every chunk a basic block and the compiler waits vmcnt(0) right after each load
+// (68 serial round trips for a 4352-wide row).  General form: optional x, up to three gathered table rows, a chunk past the
+// row reads a clamped address and is multiplied by 0; gamma / beta are fetched GRP chunks at a time behind the statistics.
+// Straight-line form (x given, no tables): gamma / beta are in flight together with the row.
+template <typename TX, typename TY, int VPL, bool FULL>
+__device__ __forceinline__ void ln_fwd_row(const HeroLnFwd& a, int row, int lane) {
+  const int cols = FULL ? VPL * 256 : a.cols;
   int cc[VPL];
   float okf[VPL];
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int c = (lane + 64 * i) * 4;
-    cc[i] = min(c, cols - 4);
-    okf[i] = c < cols ? 1.f : 0.f;
+    cc[i] = FULL ? c : min(c, cols - 4);
+    okf[i] = (FULL || c < cols) ? 1.f : 0.f;
   }
   float4 v[VPL];
-  if (a.x) {                                          // uniform
+  if (FULL || a.x) {                                  // uniform
     const TX* x = static_cast<const TX*>(a.x) + (size_t)row * cols;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) v[i] = V4<TX>::ld(x + cc[i]);
@@ -36,20 +60,27 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(HeroLnFwd a) {
 #pragma unroll
     for (int i = 0; i < VPL; ++i) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
+  constexpr int GRP = FULL ? VPL : 4;                 // gamma / beta of GRP chunks are fetched together, then GRP stores
+  float4 g[GRP], b[GRP];
+  if constexpr (FULL) {
+    ln_fwd_gamma_beta(a, cc, 0, g, b);
+  } else {
 #pragma unroll
-  for (int k = 0; k < 3; ++k)
-    if (a.tab[k]) {                                   // uniform
-      const float* t = a.tab[k] + (size_t)(a.idx[k] ? a.idx[k][row] : 0) * cols;
-      float4 w[VPL];
+    for (int k = 0; k < 3; ++k)
+      if (a.tab[k]) {                                 // uniform
+        const float* t = a.tab[k] + (size_t)(a.idx[k] ? a.idx[k][row] : 0) * cols;
+        float4 w[VPL];
 #pragma unroll
-      for (int i = 0; i < VPL; ++i) w[i] = *reinterpret_cast<const float4*>(t + cc[i]);
+        for (int i = 0; i < VPL; ++i) w[i] = *reinterpret_cast<const float4*>(t + cc[i]);
 #pragma unroll
-      for (int i = 0; i < VPL; ++i) { v[i].x += w[i].x; v[i].y += w[i].y; v[i].z += w[i].z; v[i].w += w[i].w; }
-    }
+        for (int i = 0; i < VPL; ++i) add4(v[i], w[i]);
+      }
+  }
+  // ---- statistics: sum -> mean -> centred squares -> rstd
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
-    v[i].x *= okf[i]; v[i].y *= okf[i]; v[i].z *= okf[i]; v[i].w *= okf[i];
+    if constexpr (!FULL) { v[i].x *= okf[i]; v[i].y *= okf[i]; v[i].z *= okf[i]; v[i].w *= okf[i]; }
     s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
   }
   const float mean = wave_sum(s) / (float)cols;
@@ -57,117 +88,86 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(HeroLnFwd a) {
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
-    q += ((dx * dx + dy * dy) + (dz * dz + dw * dw)) * okf[i];
+    const float sq = (dx * dx + dy * dy) + (dz * dz + dw * dw);
+    if constexpr (FULL) q += sq; else q += sq * okf[i];
   }
   const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)cols + a.eps);
   if (lane == 0) {
     if (a.mean) a.mean[row] = mean;
     if (a.rstd) a.rstd[row] = rstd;
   }
+  // ---- normalise, dropout, store
   DropCtx drop(a.dropout);
   TY* y = static_cast<TY*>(a.y) + (size_t)row * cols;
   TY* pre = a.pre ? static_cast<TY*>(a.pre) + (size_t)row * cols : nullptr;
-  constexpr int GRP = 4;                              // gamma / beta of GRP chunks are fetched together, then GRP stores
 #pragma unroll
   for (int i0 = 0; i0 < VPL; i0 += GRP) {
-    float4 g[GRP], b[GRP];
-#pragma unroll
-    for (int u = 0; u < GRP; ++u)
-      if (i0 + u < VPL) {
-        g[u] = *reinterpret_cast<const float4*>(a.gamma + cc[i0 + u]);
-        b[u] = *reinterpret_cast<const float4*>(a.beta + cc[i0 + u]);
-      }
+    if constexpr (!FULL) ln_fwd_gamma_beta(a, cc, i0, g, b);
+    float4 o[GRP];
 #pragma unroll
     for (int u = 0; u < GRP; ++u)
       if (i0 + u < VPL) {
         const int i = i0 + u;
-        float4 o;
-        o.x = (v[i].x - mean) * rstd * g[u].x + b[u].x;
-        o.y = (v[i].y - mean) * rstd * g[u].y + b[u].y;
-        o.z = (v[i].z - mean) * rstd * g[u].z + b[u].z;
-        o.w = (v[i].w - mean) * rstd * g[u].w + b[u].w;
-        if (drop.on()) {
-          const float4 m = drop.mask4(((uint64_t)row * (uint64_t)cols + (uint64_t)cc[i]) >> 2);
-          o.x *= m.x; o.y *= m.y; o.z *= m.z; o.w *= m.w;
-        }
-        if (okf[i] != 0.f) {
-          if (pre) V4<TY>::st(pre + cc[i], v[i]);
-          V4<TY>::st(y + cc[i], o);
-        }
+        o[u].x = (v[i].x - mean) * rstd * g[u].x + b[u].x;
+        o[u].y = (v[i].y - mean) * rstd * g[u].y + b[u].y;
+        o[u].z = (v[i].z - mean) * rstd * g[u].z + b[u].z;
+        o[u].w = (v[i].w - mean) * rstd * g[u].w + b[u].w;
       }
+    if (drop.on()) {
+#pragma unroll
+      for (int u = 0; u < GRP; ++u)
+        if (i0 + u < VPL) ln_mask4(o[u], drop, row, cols, cc[i0 + u]);
+    }
+    if (pre) {
+#pragma unroll
+      for (int u = 0; u < GRP; ++u)
+        if (i0 + u < VPL && (FULL || okf[i0 + u] != 0.f)) V4<TY>::st(pre + cc[i0 + u], v[i0 + u]);
+    }
+#pragma unroll
+    for (int u = 0; u < GRP; ++u)
+      if (i0 + u < VPL && (FULL || okf[i0 + u] != 0.f)) V4<TY>::st(y + cc[i0 + u], o[u]);
   }
 }
 
-// Straight-line form for the common case (x given, no embedding tables, cols == VPL * 256): no per-chunk branches, so all
-// loads of a row - and gamma / beta - are in flight together.  In the general kernel above every chunk sits in its
-// own basic block (`if (c < cols)`, `if (x)`, `if (t[k])`) and the compiler waits vmcnt(0) right after each load:
-// three serial round trips per 768-wide row.
+template <typename TX, typename TY, int VPL>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(HeroLnFwd a) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row < a.rows) ln_fwd_row<TX, TY, VPL, false>(a, row, lane);
+}
 template <typename TX, typename TY, int VPL>
 __global__ __launch_bounds__(256) void ln_fwd_full_kernel(HeroLnFwd a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int row = blockIdx.x * 4 + wave;
-  if (row >= a.rows) return;
-  constexpr int cols = VPL * 256;
-  const TX* x = static_cast<const TX*>(a.x) + (size_t)row * cols;
-  float4 v[VPL], g[VPL], b[VPL];
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) v[i] = V4<TX>::ld(x + (lane + 64 * i) * 4);
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    g[i] = *reinterpret_cast<const float4*>(a.gamma + (lane + 64 * i) * 4);
-    b[i] = *reinterpret_cast<const float4*>(a.beta + (lane + 64 * i) * 4);
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-  const float mean = wave_sum(s) / (float)cols;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
-    q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)cols + a.eps);
-  if (lane == 0) {
-    if (a.mean) a.mean[row] = mean;
-    if (a.rstd) a.rstd[row] = rstd;
-  }
-  DropCtx drop(a.dropout);
-  TY* y = static_cast<TY*>(a.y) + (size_t)row * cols;
-  TY* pre = a.pre ? static_cast<TY*>(a.pre) + (size_t)row * cols : nullptr;
-  float4 o[VPL];
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    o[i].x = (v[i].x - mean) * rstd * g[i].x + b[i].x;
-    o[i].y = (v[i].y - mean) * rstd * g[i].y + b[i].y;
-    o[i].z = (v[i].z - mean) * rstd * g[i].z + b[i].z;
-    o[i].w = (v[i].w - mean) * rstd * g[i].w + b[i].w;
-  }
-  if (drop.on()) {
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const float4 m = drop.mask4(((uint64_t)row * (uint64_t)cols + (uint64_t)((lane + 64 * i) * 4)) >> 2);
-      o[i].x *= m.x; o[i].y *= m.y; o[i].z *= m.z; o[i].w *= m.w;
-    }
-  }
-  if (pre) {
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) V4<TY>::st(pre + (lane + 64 * i) * 4, v[i]);
-  }
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) V4<TY>::st(y + (lane + 64 * i) * 4, o[i]);
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row < a.rows) ln_fwd_row<TX, TY, VPL, true>(a, row, lane);
 }
 
-template <typename TX, typename T, int VPL>
-__global__ __launch_bounds__(256) void ln_bwd_dx_kernel(HeroLnBwd a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int row = blockIdx.x * 4 + wave;
-  if (row >= a.rows) return;
-  const int cols = a.cols;
+// One backward row: dx (and dx * mask_in); with ACC also this wave's column partials ag += dy*xhat (dgamma), ab += dy (dbeta),
+// ai += dx*mask_in (dbias_in: the bias gradient of the linear layer that feeds this LayerNorm), dy being dy * mask_out.
+// General form: a chunk past the row end is skipped, which makes every chunk a basic block of its own (the compiler waits
+// vmcnt(0) after each chunk's loads).  Straight-line form: gamma comes in registers (gm, loaded once per kernel) and all loads
+// of the row are issued before anything is used.  (The two DropCtx come by value: by reference the general fused kernels
+// took 2 - 4 more VGPRs, one of them an occupancy step.)
+template <typename TX, typename T, int VPL, bool FULL, bool ACC>
+__device__ __forceinline__ void ln_bwd_row(const HeroLnBwd& a, int row, int lane, const DropCtx dout, const DropCtx din,
+                                           const float4* gm, float4* ag, float4* ab, float4* ai) {
+  const int cols = FULL ? VPL * 256 : a.cols;
+  const float inv = 1.f / (float)cols;
   const TX* x = static_cast<const TX*>(a.x) + (size_t)row * cols;
   const T* dy = static_cast<const T*>(a.dy) + (size_t)row * cols;
+  float4 xv[VPL], d[VPL];
+  if constexpr (FULL) {
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      xv[i] = V4<TX>::ld(x + (lane + 64 * i) * 4);
+      d[i] = V4<T>::ld(dy + (lane + 64 * i) * 4);
+    }
+  }
   const float mean = a.mean[row], rstd = a.rstd[row];
-  DropCtx dout(a.dropout_out);
+  if constexpr (FULL) {
+    if (dout.on()) {
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) ln_mask4(d[i], dout, row, cols, (lane + 64 * i) * 4);
+    }
+  }
   float4 xh[VPL], g[VPL];
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -175,117 +175,89 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_kernel(HeroLnBwd a) {
     const int c = (lane + 64 * i) * 4;
     xh[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     g[i] = xh[i];
-    if (c < cols) {
-      const float4 xv = V4<TX>::ld(x + c);
-      float4 d = V4<T>::ld(dy + c);
-      if (dout.on()) {
-        const float4 m = dout.mask4(((uint64_t)row * (uint64_t)cols + (uint64_t)c) >> 2);
-        d.x *= m.x; d.y *= m.y; d.z *= m.z; d.w *= m.w;
+    if (FULL || c < cols) {
+      if constexpr (!FULL) {
+        xv[i] = V4<TX>::ld(x + c);
+        d[i] = V4<T>::ld(dy + c);
+        if (dout.on()) ln_mask4(d[i], dout, row, cols, c);
       }
-      const float4 gm = *reinterpret_cast<const float4*>(a.gamma + c);
-      xh[i] = make_float4((xv.x - mean) * rstd, (xv.y - mean) * rstd, (xv.z - mean) * rstd, (xv.w - mean) * rstd);
-      g[i] = make_float4(d.x * gm.x, d.y * gm.y, d.z * gm.z, d.w * gm.w);
+      const float4 gv = FULL ? gm[i] : *reinterpret_cast<const float4*>(a.gamma + c);
+      xh[i] = make_float4((xv[i].x - mean) * rstd, (xv[i].y - mean) * rstd, (xv[i].z - mean) * rstd, (xv[i].w - mean) * rstd);
+      g[i] = make_float4(d[i].x * gv.x, d[i].y * gv.y, d[i].z * gv.z, d[i].w * gv.w);
+      if constexpr (ACC) {
+        ag[i].x += d[i].x * xh[i].x; ag[i].y += d[i].y * xh[i].y; ag[i].z += d[i].z * xh[i].z; ag[i].w += d[i].w * xh[i].w;
+        add4(ab[i], d[i]);
+      }
       s1 += (g[i].x + g[i].y) + (g[i].z + g[i].w);
       s2 += (g[i].x * xh[i].x + g[i].y * xh[i].y) + (g[i].z * xh[i].z + g[i].w * xh[i].w);
     }
   }
-  const float inv = 1.f / (float)cols;
   s1 = wave_sum(s1) * inv;
   s2 = wave_sum(s2) * inv;
-  DropCtx din(a.dropout_in);
   T* dx = a.dx ? static_cast<T*>(a.dx) + (size_t)row * cols : nullptr;
   T* dxd = a.dx_dropped ? static_cast<T*>(a.dx_dropped) + (size_t)row * cols : nullptr;
+  constexpr int GRP = FULL ? VPL : 1;                 // straight-line: the whole row goes through each step together
 #pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int c = (lane + 64 * i) * 4;
-    if (c < cols) {
-      float4 o;
-      o.x = rstd * (g[i].x - s1 - xh[i].x * s2);
-      o.y = rstd * (g[i].y - s1 - xh[i].y * s2);
-      o.z = rstd * (g[i].z - s1 - xh[i].z * s2);
-      o.w = rstd * (g[i].w - s1 - xh[i].w * s2);
-      if (dx) V4<T>::st(dx + c, o);
-      if (dxd) {
-        if (din.on()) {
-          const float4 m = din.mask4(((uint64_t)row * (uint64_t)cols + (uint64_t)c) >> 2);
-          o.x *= m.x; o.y *= m.y; o.z *= m.z; o.w *= m.w;
-        }
-        V4<T>::st(dxd + c, o);
-      }
+  for (int i0 = 0; i0 < VPL; i0 += GRP) {
+    if (!FULL && (lane + 64 * i0) * 4 >= cols) continue;
+    float4 o[GRP];
+#pragma unroll
+    for (int u = 0; u < GRP; ++u) {
+      const int i = i0 + u;
+      o[u].x = rstd * (g[i].x - s1 - xh[i].x * s2);
+      o[u].y = rstd * (g[i].y - s1 - xh[i].y * s2);
+      o[u].z = rstd * (g[i].z - s1 - xh[i].z * s2);
+      o[u].w = rstd * (g[i].w - s1 - xh[i].w * s2);
+    }
+    if (dx) {
+#pragma unroll
+      for (int u = 0; u < GRP; ++u) V4<T>::st(dx + (lane + 64 * (i0 + u)) * 4, o[u]);
+    }
+    if (din.on()) {
+#pragma unroll
+      for (int u = 0; u < GRP; ++u) ln_mask4(o[u], din, row, cols, (lane + 64 * (i0 + u)) * 4);
+    }
+    if (dxd) {
+#pragma unroll
+      for (int u = 0; u < GRP; ++u) V4<T>::st(dxd + (lane + 64 * (i0 + u)) * 4, o[u]);
+    }
+    if constexpr (ACC) {
+#pragma unroll
+      for (int u = 0; u < GRP; ++u) add4(ai[i0 + u], o[u]);
     }
   }
 }
 
-// Fused backward for rows <= 1024 wide: dx (and dx * mask_in) as above, PLUS per-workgroup partial
-// sums of dgamma = sum dy*xhat, dbeta = sum dy and dbias_in = sum dx*mask_in (the bias gradient of
-// the linear layer that feeds this LayerNorm) in the same pass over x and dy.  Each wave walks rows
-// grid-stride and keeps the column partials in registers; one LDS reduction per workgroup writes
-// partial[block][3][cols]; colred_final3_kernel folds the partials (deterministic, no atomics).
 template <typename TX, typename T, int VPL>
-__global__ __launch_bounds__(256) void ln_bwd_fused_kernel(HeroLnBwd a, float* partial) {
+__global__ __launch_bounds__(256) void ln_bwd_dx_kernel(HeroLnBwd a) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= a.rows) return;
+  DropCtx dout(a.dropout_out), din(a.dropout_in);
+  ln_bwd_row<TX, T, VPL, false, false>(a, row, lane, dout, din, nullptr, nullptr, nullptr, nullptr);
+}
+
+// Fused backward for rows <= 1024 wide: dx (and dx * mask_in) PLUS per-workgroup partial sums of dgamma, dbeta and dbias_in
+// in the same pass over x and dy.  Each wave walks rows grid-stride and keeps the column partials in registers; one LDS
+// reduction per workgroup writes partial[block][3][cols]; colred_final3_kernel folds the partials (deterministic, no atomics).
+template <typename TX, typename T, int VPL, bool FULL>
+__device__ __forceinline__ void ln_bwd_fused(const HeroLnBwd& a, float* partial) {
   extern __shared__ __attribute__((aligned(16))) float red[];       // [4 waves][3][cols]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int cols = a.cols;
+  const int cols = FULL ? VPL * 256 : a.cols;
   DropCtx dout(a.dropout_out), din(a.dropout_in);
-  float4 ag[VPL], ab[VPL], ai[VPL];
+  float4 ag[VPL], ab[VPL], ai[VPL], gm[VPL];
 #pragma unroll
-  for (int i = 0; i < VPL; ++i) ag[i] = ab[i] = ai[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  const float inv = 1.f / (float)cols;
-  for (int row = blockIdx.x * 4 + wave; row < a.rows; row += gridDim.x * 4) {
-    const TX* x = static_cast<const TX*>(a.x) + (size_t)row * cols;
-    const T* dy = static_cast<const T*>(a.dy) + (size_t)row * cols;
-    const float mean = a.mean[row], rstd = a.rstd[row];
-    float4 xh[VPL], g[VPL];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const int c = (lane + 64 * i) * 4;
-      xh[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      g[i] = xh[i];
-      if (c < cols) {
-        const float4 xv = V4<TX>::ld(x + c);
-        float4 d = V4<T>::ld(dy + c);
-        if (dout.on()) {
-          const float4 m = dout.mask4(((uint64_t)row * (uint64_t)cols + (uint64_t)c) >> 2);
-          d.x *= m.x; d.y *= m.y; d.z *= m.z; d.w *= m.w;
-        }
-        const float4 gm = *reinterpret_cast<const float4*>(a.gamma + c);
-        xh[i] = make_float4((xv.x - mean) * rstd, (xv.y - mean) * rstd, (xv.z - mean) * rstd, (xv.w - mean) * rstd);
-        g[i] = make_float4(d.x * gm.x, d.y * gm.y, d.z * gm.z, d.w * gm.w);
-        ag[i].x += d.x * xh[i].x; ag[i].y += d.y * xh[i].y; ag[i].z += d.z * xh[i].z; ag[i].w += d.w * xh[i].w;
-        ab[i].x += d.x; ab[i].y += d.y; ab[i].z += d.z; ab[i].w += d.w;
-        s1 += (g[i].x + g[i].y) + (g[i].z + g[i].w);
-        s2 += (g[i].x * xh[i].x + g[i].y * xh[i].y) + (g[i].z * xh[i].z + g[i].w * xh[i].w);
-      }
-    }
-    s1 = wave_sum(s1) * inv;
-    s2 = wave_sum(s2) * inv;
-    T* dx = a.dx ? static_cast<T*>(a.dx) + (size_t)row * cols : nullptr;
-    T* dxd = a.dx_dropped ? static_cast<T*>(a.dx_dropped) + (size_t)row * cols : nullptr;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const int c = (lane + 64 * i) * 4;
-      if (c < cols) {
-        float4 o;
-        o.x = rstd * (g[i].x - s1 - xh[i].x * s2);
-        o.y = rstd * (g[i].y - s1 - xh[i].y * s2);
-        o.z = rstd * (g[i].z - s1 - xh[i].z * s2);
-        o.w = rstd * (g[i].w - s1 - xh[i].w * s2);
-        if (dx) V4<T>::st(dx + c, o);
-        if (din.on()) {
-          const float4 m = din.mask4(((uint64_t)row * (uint64_t)cols + (uint64_t)c) >> 2);
-          o.x *= m.x; o.y *= m.y; o.z *= m.z; o.w *= m.w;
-        }
-        if (dxd) V4<T>::st(dxd + c, o);
-        ai[i].x += o.x; ai[i].y += o.y; ai[i].z += o.z; ai[i].w += o.w;
-      }
-    }
+  for (int i = 0; i < VPL; ++i) {
+    ag[i] = ab[i] = ai[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (FULL) gm[i] = *reinterpret_cast<const float4*>(a.gamma + (lane + 64 * i) * 4);
   }
+  for (int row = blockIdx.x * 4 + wave; row < a.rows; row += gridDim.x * 4)
+    ln_bwd_row<TX, T, VPL, FULL, true>(a, row, lane, dout, din, gm, ag, ab, ai);
   // ---- workgroup reduction of the three column partials
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int c = (lane + 64 * i) * 4;
-    if (c < cols) {
+    if (FULL || c < cols) {
       *reinterpret_cast<float4*>(red + ((size_t)(wave * 3 + 0)) * cols + c) = ag[i];
       *reinterpret_cast<float4*>(red + ((size_t)(wave * 3 + 1)) * cols + c) = ab[i];
       *reinterpret_cast<float4*>(red + ((size_t)(wave * 3 + 2)) * cols + c) = ai[i];
@@ -297,114 +269,23 @@ __global__ __launch_bounds__(256) void ln_bwd_fused_kernel(HeroLnBwd a, float* p
     const int k = q / (cols >> 2), c = (q - k * (cols >> 2)) * 4;
     float4 v = *reinterpret_cast<const float4*>(red + (size_t)k * cols + c);
 #pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const float4 u = *reinterpret_cast<const float4*>(red + ((size_t)(w * 3 + k)) * cols + c);
-      v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-    }
+    for (int w = 1; w < 4; ++w) add4(v, *reinterpret_cast<const float4*>(red + ((size_t)(w * 3 + k)) * cols + c));
     *reinterpret_cast<float4*>(partial + ((size_t)blockIdx.x * 3 + k) * cols + c) = v;
   }
 }
 
-// Straight-line form of the fused backward (cols == VPL * 256): gamma lives in registers for the whole kernel and
-// all loads of a row are issued before anything is used (the general kernel waits vmcnt(0) after each chunk's load
-// because every chunk is a basic block of its own).
+template <typename TX, typename T, int VPL>
+__global__ __launch_bounds__(256) void ln_bwd_fused_kernel(HeroLnBwd a, float* partial) {
+  ln_bwd_fused<TX, T, VPL, false>(a, partial);
+}
 template <typename TX, typename T, int VPL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void ln_bwd_fused_full_kernel(HeroLnBwd a, float* partial) {
-  extern __shared__ __attribute__((aligned(16))) float red[];       // [4 waves][3][cols]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr int cols = VPL * 256;
-  DropCtx dout(a.dropout_out), din(a.dropout_in);
-  float4 ag[VPL], ab[VPL], ai[VPL], gm[VPL];
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    ag[i] = ab[i] = ai[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    gm[i] = *reinterpret_cast<const float4*>(a.gamma + (lane + 64 * i) * 4);
-  }
-  const float inv = 1.f / (float)cols;
-  for (int row = blockIdx.x * 4 + wave; row < a.rows; row += gridDim.x * 4) {
-    const TX* x = static_cast<const TX*>(a.x) + (size_t)row * cols;
-    const T* dy = static_cast<const T*>(a.dy) + (size_t)row * cols;
-    float4 xv[VPL], d[VPL];
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      xv[i] = V4<TX>::ld(x + (lane + 64 * i) * 4);
-      d[i] = V4<T>::ld(dy + (lane + 64 * i) * 4);
-    }
-    const float mean = a.mean[row], rstd = a.rstd[row];
-    if (dout.on()) {
-#pragma unroll
-      for (int i = 0; i < VPL; ++i) {
-        const float4 m = dout.mask4(((uint64_t)row * (uint64_t)cols + (uint64_t)((lane + 64 * i) * 4)) >> 2);
-        d[i].x *= m.x; d[i].y *= m.y; d[i].z *= m.z; d[i].w *= m.w;
-      }
-    }
-    float4 xh[VPL], g[VPL];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      xh[i] = make_float4((xv[i].x - mean) * rstd, (xv[i].y - mean) * rstd, (xv[i].z - mean) * rstd, (xv[i].w - mean) * rstd);
-      g[i] = make_float4(d[i].x * gm[i].x, d[i].y * gm[i].y, d[i].z * gm[i].z, d[i].w * gm[i].w);
-      ag[i].x += d[i].x * xh[i].x; ag[i].y += d[i].y * xh[i].y; ag[i].z += d[i].z * xh[i].z; ag[i].w += d[i].w * xh[i].w;
-      ab[i].x += d[i].x; ab[i].y += d[i].y; ab[i].z += d[i].z; ab[i].w += d[i].w;
-      s1 += (g[i].x + g[i].y) + (g[i].z + g[i].w);
-      s2 += (g[i].x * xh[i].x + g[i].y * xh[i].y) + (g[i].z * xh[i].z + g[i].w * xh[i].w);
-    }
-    s1 = wave_sum(s1) * inv;
-    s2 = wave_sum(s2) * inv;
-    T* dx = a.dx ? static_cast<T*>(a.dx) + (size_t)row * cols : nullptr;
-    T* dxd = a.dx_dropped ? static_cast<T*>(a.dx_dropped) + (size_t)row * cols : nullptr;
-    float4 o[VPL];
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      o[i].x = rstd * (g[i].x - s1 - xh[i].x * s2);
-      o[i].y = rstd * (g[i].y - s1 - xh[i].y * s2);
-      o[i].z = rstd * (g[i].z - s1 - xh[i].z * s2);
-      o[i].w = rstd * (g[i].w - s1 - xh[i].w * s2);
-    }
-    if (dx) {
-#pragma unroll
-      for (int i = 0; i < VPL; ++i) V4<T>::st(dx + (lane + 64 * i) * 4, o[i]);
-    }
-    if (din.on()) {
-#pragma unroll
-      for (int i = 0; i < VPL; ++i) {
-        const float4 m = din.mask4(((uint64_t)row * (uint64_t)cols + (uint64_t)((lane + 64 * i) * 4)) >> 2);
-        o[i].x *= m.x; o[i].y *= m.y; o[i].z *= m.z; o[i].w *= m.w;
-      }
-    }
-    if (dxd) {
-#pragma unroll
-      for (int i = 0; i < VPL; ++i) V4<T>::st(dxd + (lane + 64 * i) * 4, o[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) { ai[i].x += o[i].x; ai[i].y += o[i].y; ai[i].z += o[i].z; ai[i].w += o[i].w; }
-  }
-  // ---- workgroup reduction of the three column partials (as in ln_bwd_fused_kernel)
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int c = (lane + 64 * i) * 4;
-    *reinterpret_cast<float4*>(red + ((size_t)(wave * 3 + 0)) * cols + c) = ag[i];
-    *reinterpret_cast<float4*>(red + ((size_t)(wave * 3 + 1)) * cols + c) = ab[i];
-    *reinterpret_cast<float4*>(red + ((size_t)(wave * 3 + 2)) * cols + c) = ai[i];
-  }
-  __syncthreads();
-  constexpr int n4 = 3 * (cols >> 2);
-  for (int q = threadIdx.x; q < n4; q += 256) {
-    const int k = q / (cols >> 2), c = (q - k * (cols >> 2)) * 4;
-    float4 v = *reinterpret_cast<const float4*>(red + (size_t)k * cols + c);
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const float4 u = *reinterpret_cast<const float4*>(red + ((size_t)(w * 3 + k)) * cols + c);
-      v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-    }
-    *reinterpret_cast<float4*>(partial + ((size_t)blockIdx.x * 3 + k) * cols + c) = v;
-  }
+  ln_bwd_fused<TX, T, VPL, true>(a, partial);
 }
 
 // out_k[c] = beta*out_k[c] + sum_b partial[b][k][c] for k = blockIdx.y (outputs may be NULL).
-// 16 float4 column groups x 16 partial-lanes per workgroup; fixed summation order.
-// gridDim.z > 1 (only with beta == 1): each z-slice folds its share of the partials and adds it with
-// fp32 atomics (8-way contention) - 8x the parallelism of the single-slice, deterministic form.
+// 16 float4 column groups x 16 partial-lanes per workgroup; fixed summation order (the partials of a lane one after the other,
+// not pairwise as in colsum_fold: the two loops are not one).
 __global__ __launch_bounds__(256) void colred_final3_kernel(const float* partial, float* o0, float* o1, float* o2, int cols,
                                                             int nblocks, float beta) {
   const int k = blockIdx.y;
@@ -413,52 +294,109 @@ __global__ __launch_bounds__(256) void colred_final3_kernel(const float* partial
   __shared__ float4 red[16][16];
   const int cg = threadIdx.x & 15, kl = threadIdx.x >> 4;
   const int c = (blockIdx.x * 16 + cg) * 4;
-  const int per = (nblocks + gridDim.z - 1) / gridDim.z;
-  const int b0 = blockIdx.z * per, b1 = min(nblocks, b0 + per);
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   if (c < cols) {
-    int b = b0 + kl;
+    int b = kl;
     // four partials per trip, loads issued together (one per trip = one 16-byte request in flight per thread: the
     // 8 trips of the 1024-block fold were 8 serial round trips, most of the kernel's 5 us)
-    for (; b + 48 < b1; b += 64) {
+    for (; b + 48 < nblocks; b += 64) {
       float4 v[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(partial + ((size_t)(b + 16 * u) * 3 + k) * cols + c);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
+      for (int u = 0; u < 4; ++u) add4(s, v[u]);
     }
-    for (; b < b1; b += 16) {
-      const float4 v = *reinterpret_cast<const float4*>(partial + ((size_t)b * 3 + k) * cols + c);
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
+    for (; b < nblocks; b += 16) add4(s, *reinterpret_cast<const float4*>(partial + ((size_t)b * 3 + k) * cols + c));
   }
   red[kl][cg] = s;
   __syncthreads();
   if (kl == 0 && c < cols) {
-#pragma unroll
-    for (int j = 1; j < 16; ++j) {
-      const float4 v = red[j][cg];
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    if (gridDim.z > 1) {
-      atomicAdd(out + c, s.x); atomicAdd(out + c + 1, s.y); atomicAdd(out + c + 2, s.z); atomicAdd(out + c + 3, s.w);
-      return;
-    }
-    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);     // the destination is fetched while the LDS sum runs
     if (beta != 0.f) {
       o = *reinterpret_cast<const float4*>(out + c);
       o.x *= beta; o.y *= beta; o.z *= beta; o.w *= beta;
     }
-    o.x += s.x; o.y += s.y; o.z += s.z; o.w += s.w;
+#pragma unroll
+    for (int j = 1; j < 16; ++j) add4(s, red[j][cg]);
+    add4(o, s);
     *reinterpret_cast<float4*>(out + c) = o;
   }
 }
 
+// ---- column sums, stage 1: what one workgroup row-lane (ty of 4) adds up over the rows r0 + ty, r0 + ty + 4, ... < r1 of a
+// chunk, 4 columns from c.  sb += d, and with x given sg += d * xhat, d being the dy row times its dropout mask (drop may be
+// null).  Four rows per trip, their loads issued together (one load per trip left a single 8-byte request in flight per wave:
+// 12 serial round trips per chunk).
+template <typename TX, typename T>
+__device__ __forceinline__ void colsum_chunk(const T* dy, int ld, int c, int r0, int r1, int ty, float4& sb, const TX* x,
+                                             const float* mean, const float* rstd, int cols, const DropCtx* drop, float4& sg) {
+  const bool masked = drop && drop->on();
+  int r = r0 + ty;
+  for (; r + 12 < r1; r += 16) {
+    float4 d[4], xv[4];
+    float mu[4], rs[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) d[u] = V4<T>::ld(dy + (size_t)(r + 4 * u) * ld + c);
+    if (x) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        xv[u] = V4<TX>::ld(x + (size_t)(r + 4 * u) * cols + c);
+        mu[u] = mean[r + 4 * u];
+        rs[u] = rstd[r + 4 * u];
+      }
+    }
+    if (masked) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) ln_mask4(d[u], *drop, r + 4 * u, cols, c);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) add4(sb, d[u]);
+    if (x) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        sg.x += d[u].x * (xv[u].x - mu[u]) * rs[u]; sg.y += d[u].y * (xv[u].y - mu[u]) * rs[u];
+        sg.z += d[u].z * (xv[u].z - mu[u]) * rs[u]; sg.w += d[u].w * (xv[u].w - mu[u]) * rs[u];
+      }
+    }
+  }
+  for (; r < r1; r += 4) {
+    float4 d = V4<T>::ld(dy + (size_t)r * ld + c);
+    if (masked) ln_mask4(d, *drop, r, cols, c);
+    add4(sb, d);
+    if (x) {
+      const float4 xv = V4<TX>::ld(x + (size_t)r * cols + c);
+      const float mu = mean[r], rs = rstd[r];
+      sg.x += d.x * (xv.x - mu) * rs; sg.y += d.y * (xv.y - mu) * rs;
+      sg.z += d.z * (xv.z - mu) * rs; sg.w += d.w * (xv.w - mu) * rs;
+    }
+  }
+}
+
+// ---- column sums, stage 2: the sum over part[nchunks][cols] of column c, fixed order: 16 columns x 16 chunk-lanes per
+// workgroup, four chunks per trip (loads issued together), the lanes of a column combined with shuffles, the four waves
+// through red.  part may be null (sum 0).  Every thread of the workgroup calls it; threads 0 .. 15 get the result.
+__device__ __forceinline__ float colsum_fold(const float* part, int cols, int c, int nchunks, float (&red)[4][16]) {
+  const int cl = threadIdx.x & 15;
+  float s = 0.f;
+  if (part && c < cols) {
+    int k = threadIdx.x >> 4;
+    for (; k + 48 < nchunks; k += 64) {
+      float v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = part[(size_t)(k + 16 * u) * cols + c];
+      s += (v[0] + v[1]) + (v[2] + v[3]);
+    }
+    for (; k < nchunks; k += 16) s += part[(size_t)k * cols + c];
+  }
+#pragma unroll
+  for (int o = 16; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) < 16) red[threadIdx.x >> 6][cl] = s;
+  __syncthreads();
+  return (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
+}
+
 // partial column sums over a chunk of rows.  pb[chunk][c] = sum dy_eff ; pg[chunk][c] = sum dy_eff*xhat
 struct ColRed {
-  float* og;          // atomic mode: accumulate straight into the outputs (beta == 1), no second pass
-  float* ob;
-  int atomic;
   const void* x;      // [rows, cols] TX or null
   const void* dy;     // [rows, ld]  T
   const float* mean;
@@ -480,124 +418,27 @@ __global__ __launch_bounds__(256) void colred_kernel(ColRed a) {
   float4 sg = make_float4(0.f, 0.f, 0.f, 0.f), sb = sg;
   if (c < a.cols) {
     DropCtx drop(a.dropout);
-    const TX* x = static_cast<const TX*>(a.x);
-    const T* dy = static_cast<const T*>(a.dy);
-    int r = r0 + ty;
-    // four rows per trip, their loads issued together (one load per trip left a single 8-byte request in flight per
-    // wave: 12 serial round trips per chunk)
-    for (; r + 12 < r1; r += 16) {
-      float4 d[4], xv[4];
-      float mu[4], rs[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) d[u] = V4<T>::ld(dy + (size_t)(r + 4 * u) * a.ld + c);
-      if (x) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          xv[u] = V4<TX>::ld(x + (size_t)(r + 4 * u) * a.cols + c);
-          mu[u] = a.mean[r + 4 * u];
-          rs[u] = a.rstd[r + 4 * u];
-        }
-      }
-      if (drop.on()) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float4 m = drop.mask4(((uint64_t)(r + 4 * u) * (uint64_t)a.cols + (uint64_t)c) >> 2);
-          d[u].x *= m.x; d[u].y *= m.y; d[u].z *= m.z; d[u].w *= m.w;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { sb.x += d[u].x; sb.y += d[u].y; sb.z += d[u].z; sb.w += d[u].w; }
-      if (x) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          sg.x += d[u].x * (xv[u].x - mu[u]) * rs[u]; sg.y += d[u].y * (xv[u].y - mu[u]) * rs[u];
-          sg.z += d[u].z * (xv[u].z - mu[u]) * rs[u]; sg.w += d[u].w * (xv[u].w - mu[u]) * rs[u];
-        }
-      }
-    }
-    for (; r < r1; r += 4) {
-      float4 d = V4<T>::ld(dy + (size_t)r * a.ld + c);
-      if (drop.on()) {
-        const float4 m = drop.mask4(((uint64_t)r * (uint64_t)a.cols + (uint64_t)c) >> 2);
-        d.x *= m.x; d.y *= m.y; d.z *= m.z; d.w *= m.w;
-      }
-      sb.x += d.x; sb.y += d.y; sb.z += d.z; sb.w += d.w;
-      if (x) {
-        const float4 xv = V4<TX>::ld(x + (size_t)r * a.cols + c);
-        const float mu = a.mean[r], rs = a.rstd[r];
-        sg.x += d.x * (xv.x - mu) * rs; sg.y += d.y * (xv.y - mu) * rs;
-        sg.z += d.z * (xv.z - mu) * rs; sg.w += d.w * (xv.w - mu) * rs;
-      }
-    }
+    colsum_chunk(static_cast<const T*>(a.dy), a.ld, c, r0, r1, ty, sb, static_cast<const TX*>(a.x), a.mean, a.rstd, a.cols, &drop, sg);
   }
   red[0][ty][tx] = sg;
   red[1][ty][tx] = sb;
   __syncthreads();
   if (ty == 0 && c < a.cols) {
 #pragma unroll
-    for (int k = 1; k < 4; ++k) {
-      const float4 g2 = red[0][k][tx], b2 = red[1][k][tx];
-      sg.x += g2.x; sg.y += g2.y; sg.z += g2.z; sg.w += g2.w;
-      sb.x += b2.x; sb.y += b2.y; sb.z += b2.z; sb.w += b2.w;
-    }
-    if (a.atomic) {
-      if (a.og) { atomicAdd(a.og + c, sg.x); atomicAdd(a.og + c + 1, sg.y); atomicAdd(a.og + c + 2, sg.z); atomicAdd(a.og + c + 3, sg.w); }
-      if (a.ob) { atomicAdd(a.ob + c, sb.x); atomicAdd(a.ob + c + 1, sb.y); atomicAdd(a.ob + c + 2, sb.z); atomicAdd(a.ob + c + 3, sb.w); }
-    } else {
-      if (a.pg) *reinterpret_cast<float4*>(a.pg + (size_t)chunk * a.cols + c) = sg;
-      *reinterpret_cast<float4*>(a.pb + (size_t)chunk * a.cols + c) = sb;
-    }
+    for (int k = 1; k < 4; ++k) { add4(sg, red[0][k][tx]); add4(sb, red[1][k][tx]); }
+    if (a.pg) *reinterpret_cast<float4*>(a.pg + (size_t)chunk * a.cols + c) = sg;
+    *reinterpret_cast<float4*>(a.pb + (size_t)chunk * a.cols + c) = sb;
   }
 }
 
-// out[c] = beta*out[c] + sum_k partial[k][c]: 16 columns x 16 chunk-lanes per block, lanes of one
-// column combine with shuffles (fixed order -> deterministic).
+// out[c] = beta*out[c] + sum_k partial[k][c] (outputs may be NULL)
 __global__ __launch_bounds__(256) void colred_final_kernel(const float* pg, const float* pb, float* og, float* ob, int cols,
                                                            int nchunks, float beta) {
-  const int cl = threadIdx.x & 15, kl = threadIdx.x >> 4;
-  const int c = blockIdx.x * 16 + cl;
-  // gridDim.z > 1 (only with beta == 1): each z-slice folds its share of the chunks and adds it with
-  // fp32 atomics (8-way contention), as in colred_final3_kernel
-  const int per = (nchunks + gridDim.z - 1) / gridDim.z;
-  const int k0 = blockIdx.z * per, k1 = min(nchunks, k0 + per);
-  float sg = 0.f, sb = 0.f;
-  if (c < cols) {
-    int k = k0 + kl;
-    for (; k + 48 < k1; k += 64) {                     // four chunks per trip, loads issued together
-      float g4[4] = {0.f, 0.f, 0.f, 0.f}, b4[4] = {0.f, 0.f, 0.f, 0.f};
-      if (og) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) g4[u] = pg[(size_t)(k + 16 * u) * cols + c];
-      }
-      if (ob) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) b4[u] = pb[(size_t)(k + 16 * u) * cols + c];
-      }
-      sg += (g4[0] + g4[1]) + (g4[2] + g4[3]);
-      sb += (b4[0] + b4[1]) + (b4[2] + b4[3]);
-    }
-    for (; k < k1; k += 16) {
-      if (og) sg += pg[(size_t)k * cols + c];
-      if (ob) sb += pb[(size_t)k * cols + c];
-    }
-  }
-#pragma unroll
-  for (int o = 16; o < 64; o <<= 1) {
-    sg += __shfl_xor(sg, o, 64);
-    sb += __shfl_xor(sb, o, 64);
-  }
   __shared__ float red[2][4][16];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) < 16) { red[0][wave][cl] = sg; red[1][wave][cl] = sb; }
-  __syncthreads();
+  const int c = blockIdx.x * 16 + (threadIdx.x & 15);
+  const float sg = colsum_fold(og ? pg : nullptr, cols, c, nchunks, red[0]);
+  const float sb = colsum_fold(ob ? pb : nullptr, cols, c, nchunks, red[1]);
   if (threadIdx.x < 16 && c < cols) {
-    sg = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
-    sb = (red[1][0][cl] + red[1][1][cl]) + (red[1][2][cl] + red[1][3][cl]);
-    if (gridDim.z > 1) {
-      if (og) atomicAdd(og + c, sg);
-      if (ob) atomicAdd(ob + c, sb);
-      return;
-    }
     if (og) og[c] = (beta != 0.f ? beta * og[c] : 0.f) + sg;
     if (ob) ob[c] = (beta != 0.f ? beta * ob[c] : 0.f) + sb;
   }
@@ -610,37 +451,50 @@ static inline int chunking(int rows, int* rpc) {
   return (rows + r - 1) / r;
 }
 
+// Two launches, fixed order.  (fp32 atomics straight into the outputs instead of the fold were measured SLOWER, at 256-way and
+// at 64-way contention; a fold cut into 8 z-slices that add their shares with atomics gives order-dependent sums, and one
+// slice folds 256 partial rows in a few microseconds.)
 template <typename TX, typename T>
 static int run_colred(const void* x, const void* dy, const float* mean, const float* rstd, float* og, float* ob, int rows,
                       int cols, int ld, float beta, const HeroDropout& dr, void* ws, hipStream_t s) {
   ColRed a;
   a.x = x; a.dy = dy; a.mean = mean; a.rstd = rstd;
   a.rows = rows; a.cols = cols; a.ld = ld; a.dropout = dr;
-  a.og = x ? og : nullptr;
-  a.ob = ob;
   const int nchunks = chunking(rows, &a.rows_per_chunk);
   a.pb = static_cast<float*>(ws);
   a.pg = x ? a.pb + (size_t)nchunks * cols : nullptr;
-  a.atomic = 0;   // (fp32 atomics straight into the outputs were measured SLOWER, at 256-way and at 64-way contention)
   hipLaunchKernelGGL((colred_kernel<TX, T>), dim3((cols + 255) / 256, nchunks), dim3(256), 0, s, a);
   int rc = check_launch("colred");
-  if (rc || a.atomic) return rc;
-  // (round 3 cut long folds into 8 z-slices that added their shares with fp32 atomics: order-dependent sums; one slice
-  // folds 256 partial rows in a few microseconds, and the result is the same every run)
-  const int zs = 1;
-  (void)beta;
-  hipLaunchKernelGGL(colred_final_kernel, dim3((cols + 15) / 16, 1, zs), dim3(256), 0, s, a.pg, a.pb, x ? og : nullptr, ob, cols,
+  if (rc) return rc;
+  hipLaunchKernelGGL(colred_final_kernel, dim3((cols + 15) / 16), dim3(256), 0, s, a.pg, a.pb, x ? og : nullptr, ob, cols,
                      nchunks, beta);
   return check_launch("colred_final");
 }
 
+// (x dtype, dy / y dtype) -> f(TX(), T()) for the three pairs the kernels are built for; `second` names the other tensor
+template <typename F>
+static int ln_dtypes(const char* who, const char* second, int xd, int d, F f) {
+  if (xd == HERO_F32 && d == HERO_F32) return f(float(), float());
+  if (xd == HERO_F32 && d == HERO_BF16) return f(float(), bf16_t());
+  if (xd == HERO_BF16 && d == HERO_BF16) return f(bf16_t(), bf16_t());
+  set_error("%s: unsupported dtypes x=%d %s=%d", who, xd, second, d);
+  return HERO_ERR_UNSUPPORTED;
+}
+
+// CALL(VPL) with the float4 chunks per lane that a row of `cols` needs; rows up to 1024 wide (all that the fused backward and
+// the straight-line kernels are built for) take HERO_VPL_SWITCH4
+#define HERO_VPL_SWITCH4(cols, CALL)                                       \
+  do {                                                                     \
+    const int need4 = ((cols) + 255) / 256;                                \
+    if (need4 <= 1) { CALL(1); }                                           \
+    else if (need4 <= 2) { CALL(2); }                                      \
+    else if (need4 <= 3) { CALL(3); }                                      \
+    else { CALL(4); }                                                      \
+  } while (0)
 #define HERO_VPL_SWITCH(cols, CALL)                                        \
   do {                                                                     \
     const int need = ((cols) + 255) / 256;                                 \
-    if (need <= 1) { CALL(1); }                                            \
-    else if (need <= 2) { CALL(2); }                                       \
-    else if (need <= 3) { CALL(3); }                                       \
-    else if (need <= 4) { CALL(4); }                                       \
+    if (need <= 4) HERO_VPL_SWITCH4(cols, CALL);                           \
     else if (need <= 6) { CALL(6); }                                       \
     else if (need <= 8) { CALL(8); }                                       \
     else if (need <= 12) { CALL(12); }                                     \
@@ -662,25 +516,23 @@ extern "C" int hero_layernorm_fwd(const HeroLnFwd* a, hero_stream_t stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid((a->rows + 3) / 4), block(256);
   const int xd = a->x ? a->x_dtype : a->y_dtype, yd = a->y_dtype;
+  int rc = HERO_OK;
+#define LAUNCH(KERNEL, V)                                                                         \
+  rc = ln_dtypes("hero_layernorm_fwd", "y", xd, yd, [&](auto tx, auto ty) {                       \
+    hipLaunchKernelGGL((KERNEL<decltype(tx), decltype(ty), V>), grid, block, 0, s, *a);           \
+    return HERO_OK;                                                                               \
+  })
   if (a->x && !a->tab[0] && !a->tab[1] && !a->tab[2] && a->cols % 256 == 0 && a->cols <= 1024) {   // straight-line kernel
-#define CALLF(V)                                                                                                           \
-  if (xd == HERO_F32 && yd == HERO_F32) hipLaunchKernelGGL((ln_fwd_full_kernel<float, float, V>), grid, block, 0, s, *a);        \
-  else if (xd == HERO_F32 && yd == HERO_BF16) hipLaunchKernelGGL((ln_fwd_full_kernel<float, bf16_t, V>), grid, block, 0, s, *a); \
-  else if (xd == HERO_BF16 && yd == HERO_BF16) hipLaunchKernelGGL((ln_fwd_full_kernel<bf16_t, bf16_t, V>), grid, block, 0, s, *a); \
-  else { set_error("hero_layernorm_fwd: unsupported dtypes x=%d y=%d", xd, yd); return HERO_ERR_UNSUPPORTED; }
-    const int v = a->cols / 256;
-    if (v == 1) { CALLF(1); } else if (v == 2) { CALLF(2); } else if (v == 3) { CALLF(3); } else { CALLF(4); }
-#undef CALLF
-    return check_launch("hero_layernorm_fwd(full)");
+#define CALL(V) LAUNCH(ln_fwd_full_kernel, V)
+    HERO_VPL_SWITCH4(a->cols, CALL);
+#undef CALL
+    return rc ? rc : check_launch("hero_layernorm_fwd(full)");
   }
-#define CALL(V)                                                                                                   \
-  if (xd == HERO_F32 && yd == HERO_F32) hipLaunchKernelGGL((ln_fwd_kernel<float, float, V>), grid, block, 0, s, *a);        \
-  else if (xd == HERO_F32 && yd == HERO_BF16) hipLaunchKernelGGL((ln_fwd_kernel<float, bf16_t, V>), grid, block, 0, s, *a); \
-  else if (xd == HERO_BF16 && yd == HERO_BF16) hipLaunchKernelGGL((ln_fwd_kernel<bf16_t, bf16_t, V>), grid, block, 0, s, *a); \
-  else { set_error("hero_layernorm_fwd: unsupported dtypes x=%d y=%d", xd, yd); return HERO_ERR_UNSUPPORTED; }
+#define CALL(V) LAUNCH(ln_fwd_kernel, V)
   HERO_VPL_SWITCH(a->cols, CALL);
 #undef CALL
-  return check_launch("hero_layernorm_fwd");
+#undef LAUNCH
+  return rc ? rc : check_launch("hero_layernorm_fwd");
 }
 
 extern "C" size_t hero_layernorm_bwd_workspace_bytes(int rows, int cols) {
@@ -700,6 +552,12 @@ extern "C" int hero_layernorm_bwd(const HeroLnBwd* a, hero_stream_t stream) {
   const int xd = a->x_dtype, d = a->dtype;
   const bool want_params = a->dgamma || a->dbeta || a->dbias_in;
   if (want_params) HERO_REQUIRE(a->workspace, "hero_layernorm_bwd: workspace required for parameter gradients");
+  int rc = HERO_OK;
+#define LAUNCH(KERNEL, V, LDS, ...)                                                                         \
+  rc = ln_dtypes("hero_layernorm_bwd", "dy", xd, d, [&](auto tx, auto t) {                                  \
+    hipLaunchKernelGGL((KERNEL<decltype(tx), decltype(t), V>), grid, block, LDS, s, __VA_ARGS__);          \
+    return HERO_OK;                                                                                         \
+  })
   // ---- fused single pass (rows up to 1024 wide)
   if (want_params && (a->dx || a->dx_dropped || a->dbias_in) && a->cols <= 1024) {
     int nblk = (a->rows + 3) / 4;
@@ -707,26 +565,20 @@ extern "C" int hero_layernorm_bwd(const HeroLnBwd* a, hero_stream_t stream) {
     float* partial = static_cast<float*>(a->workspace);
     const size_t lds = (size_t)4 * 3 * a->cols * sizeof(float);
     const dim3 grid(nblk), block(256);
-#define CALLF(V)                                                                                                              \
-  if (xd == HERO_F32 && d == HERO_F32) hipLaunchKernelGGL((ln_bwd_fused_kernel<float, float, V>), grid, block, lds, s, *a, partial);          \
-  else if (xd == HERO_F32 && d == HERO_BF16) hipLaunchKernelGGL((ln_bwd_fused_kernel<float, bf16_t, V>), grid, block, lds, s, *a, partial);   \
-  else if (xd == HERO_BF16 && d == HERO_BF16) hipLaunchKernelGGL((ln_bwd_fused_kernel<bf16_t, bf16_t, V>), grid, block, lds, s, *a, partial); \
-  else { set_error("hero_layernorm_bwd: unsupported dtypes x=%d dy=%d", xd, d); return HERO_ERR_UNSUPPORTED; }
-    const int need = (a->cols + 255) / 256;
     if (a->cols % 256 == 0) {                          // straight-line kernel
-#define CALLS(V)                                                                                                                   \
-  if (xd == HERO_F32 && d == HERO_F32) hipLaunchKernelGGL((ln_bwd_fused_full_kernel<float, float, V>), grid, block, lds, s, *a, partial);          \
-  else if (xd == HERO_F32 && d == HERO_BF16) hipLaunchKernelGGL((ln_bwd_fused_full_kernel<float, bf16_t, V>), grid, block, lds, s, *a, partial);   \
-  else if (xd == HERO_BF16 && d == HERO_BF16) hipLaunchKernelGGL((ln_bwd_fused_full_kernel<bf16_t, bf16_t, V>), grid, block, lds, s, *a, partial); \
-  else { set_error("hero_layernorm_bwd: unsupported dtypes x=%d dy=%d", xd, d); return HERO_ERR_UNSUPPORTED; }
-      if (need <= 1) { CALLS(1); } else if (need <= 2) { CALLS(2); } else if (need <= 3) { CALLS(3); } else { CALLS(4); }
-#undef CALLS
-    } else if (need <= 1) { CALLF(1); } else if (need <= 2) { CALLF(2); } else if (need <= 3) { CALLF(3); } else { CALLF(4); }
-#undef CALLF
-    int rc = check_launch("hero_layernorm_bwd(fused)");
+#define CALL(V) LAUNCH(ln_bwd_fused_full_kernel, V, lds, *a, partial)
+      HERO_VPL_SWITCH4(a->cols, CALL);
+#undef CALL
+    } else {
+#define CALL(V) LAUNCH(ln_bwd_fused_kernel, V, lds, *a, partial)
+      HERO_VPL_SWITCH4(a->cols, CALL);
+#undef CALL
+    }
+    if (rc) return rc;
+    rc = check_launch("hero_layernorm_bwd(fused)");
     if (rc || a->defer_fold) return rc;
-    const int zs = 1;               // fixed-order fold (see run_colred)
-    hipLaunchKernelGGL(colred_final3_kernel, dim3((a->cols + 63) / 64, 3, zs), dim3(256), 0, s, partial, a->dgamma, a->dbeta,
+    // one fixed-order fold (see run_colred)
+    hipLaunchKernelGGL(colred_final3_kernel, dim3((a->cols + 63) / 64, 3), dim3(256), 0, s, partial, a->dgamma, a->dbeta,
                        a->dbias_in, a->cols, nblk, a->grad_beta);
     return check_launch("hero_layernorm_bwd(final3)");
   }
@@ -734,26 +586,19 @@ extern "C" int hero_layernorm_bwd(const HeroLnBwd* a, hero_stream_t stream) {
   HERO_REQUIRE(!a->defer_fold, "hero_layernorm_bwd: defer_fold needs the fused path (cols <= 1024, dx or dbias_in wanted)");
   if (a->dx || a->dx_dropped) {
     const dim3 grid((a->rows + 3) / 4), block(256);
-#define CALL(V)                                                                                                      \
-  if (xd == HERO_F32 && d == HERO_F32) hipLaunchKernelGGL((ln_bwd_dx_kernel<float, float, V>), grid, block, 0, s, *a);          \
-  else if (xd == HERO_F32 && d == HERO_BF16) hipLaunchKernelGGL((ln_bwd_dx_kernel<float, bf16_t, V>), grid, block, 0, s, *a);   \
-  else if (xd == HERO_BF16 && d == HERO_BF16) hipLaunchKernelGGL((ln_bwd_dx_kernel<bf16_t, bf16_t, V>), grid, block, 0, s, *a); \
-  else { set_error("hero_layernorm_bwd: unsupported dtypes x=%d dy=%d", xd, d); return HERO_ERR_UNSUPPORTED; }
+#define CALL(V) LAUNCH(ln_bwd_dx_kernel, V, 0, *a)
     HERO_VPL_SWITCH(a->cols, CALL);
 #undef CALL
-    int rc = check_launch("hero_layernorm_bwd(dx)");
+    if (rc) return rc;
+    rc = check_launch("hero_layernorm_bwd(dx)");
     if (rc) return rc;
   }
-  if (a->dgamma || a->dbeta) {
-    if (xd == HERO_F32 && d == HERO_F32)
-      return run_colred<float, float>(a->x, a->dy, a->mean, a->rstd, a->dgamma, a->dbeta, a->rows, a->cols, a->cols, a->grad_beta, a->dropout_out, a->workspace, s);
-    if (xd == HERO_F32 && d == HERO_BF16)
-      return run_colred<float, bf16_t>(a->x, a->dy, a->mean, a->rstd, a->dgamma, a->dbeta, a->rows, a->cols, a->cols, a->grad_beta, a->dropout_out, a->workspace, s);
-    if (xd == HERO_BF16 && d == HERO_BF16)
-      return run_colred<bf16_t, bf16_t>(a->x, a->dy, a->mean, a->rstd, a->dgamma, a->dbeta, a->rows, a->cols, a->cols, a->grad_beta, a->dropout_out, a->workspace, s);
-    set_error("hero_layernorm_bwd: unsupported dtypes x=%d dy=%d", xd, d);
-    return HERO_ERR_UNSUPPORTED;
-  }
+#undef LAUNCH
+  if (a->dgamma || a->dbeta)
+    return ln_dtypes("hero_layernorm_bwd", "dy", xd, d, [&](auto tx, auto t) {
+      return run_colred<decltype(tx), decltype(t)>(a->x, a->dy, a->mean, a->rstd, a->dgamma, a->dbeta, a->rows, a->cols, a->cols,
+                                                   a->grad_beta, a->dropout_out, a->workspace, s);
+    });
   return HERO_OK;
 }
 
@@ -781,24 +626,6 @@ __device__ __forceinline__ int colsum_find(const ColsumMulti& a, int b) {
   return lo;
 }
 
-template <typename T>
-__device__ __forceinline__ float4 colsum_chunk(const T* src, int ld, int c, int r0, int r1, int ty) {
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  int r = r0 + ty;
-  for (; r + 12 < r1; r += 16) {           // four rows per trip, their loads issued together
-    float4 d[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) d[u] = V4<T>::ld(src + (size_t)(r + 4 * u) * ld + c);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { s.x += d[u].x; s.y += d[u].y; s.z += d[u].z; s.w += d[u].w; }
-  }
-  for (; r < r1; r += 4) {
-    const float4 d = V4<T>::ld(src + (size_t)r * ld + c);
-    s.x += d.x; s.y += d.y; s.z += d.z; s.w += d.w;
-  }
-  return s;
-}
-
 __global__ __launch_bounds__(256) void colsum_multi_part_kernel(ColsumMulti a, float* ws) {
   __shared__ float4 red[4][64];
   const int pi = colsum_find(a, blockIdx.x);
@@ -808,46 +635,30 @@ __global__ __launch_bounds__(256) void colsum_multi_part_kernel(ColsumMulti a, f
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = (cb * 64 + tx) * 4;
   const int r0 = chunk * a.rpc[pi], r1 = min(P.rows, r0 + a.rpc[pi]);
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f), unused = s;
+  const float* const none = nullptr;                  // plain sums: no x, no dropout
   if (c < P.cols) {
-    if (P.dtype == HERO_BF16) s = colsum_chunk(static_cast<const bf16_t*>(P.src), P.ld, c, r0, r1, ty);
-    else s = colsum_chunk(static_cast<const float*>(P.src), P.ld, c, r0, r1, ty);
+    if (P.dtype == HERO_BF16) colsum_chunk(static_cast<const bf16_t*>(P.src), P.ld, c, r0, r1, ty, s, none, none, none, 0, nullptr, unused);
+    else colsum_chunk(static_cast<const float*>(P.src), P.ld, c, r0, r1, ty, s, none, none, none, 0, nullptr, unused);
   }
   red[ty][tx] = s;
   __syncthreads();
   if (ty == 0 && c < P.cols) {
 #pragma unroll
-    for (int k = 1; k < 4; ++k) { const float4 v = red[k][tx]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+    for (int k = 1; k < 4; ++k) add4(s, red[k][tx]);
     *reinterpret_cast<float4*>(ws + a.woff[pi] + (size_t)chunk * P.cols + c) = s;
   }
 }
 
-// dst[c] = beta*dst[c] + sum over the chunks, fixed order: 16 columns x 16 chunk-lanes per workgroup
+// dst[c] = beta*dst[c] + sum over the chunks
 __global__ __launch_bounds__(256) void colsum_multi_fold_kernel(ColsumMulti a, const float* ws) {
+  __shared__ float red[4][16];
   const int pi = colsum_find(a, blockIdx.x);
   const HeroColsum P = a.p[pi];
   const int nchunks = (P.rows + a.rpc[pi] - 1) / a.rpc[pi];
-  const int cl = threadIdx.x & 15, kl = threadIdx.x >> 4;
-  const int c = (blockIdx.x - a.blk0[pi]) * 16 + cl;
-  const float* part = ws + a.woff[pi];
-  float s = 0.f;
-  if (c < P.cols) {
-    int k = kl;
-    for (; k + 48 < nchunks; k += 64) {
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = part[(size_t)(k + 16 * u) * P.cols + c];
-      s += (v[0] + v[1]) + (v[2] + v[3]);
-    }
-    for (; k < nchunks; k += 16) s += part[(size_t)k * P.cols + c];
-  }
-#pragma unroll
-  for (int o = 16; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
-  __shared__ float red[4][16];
-  if ((threadIdx.x & 63) < 16) red[threadIdx.x >> 6][cl] = s;
-  __syncthreads();
+  const int c = (blockIdx.x - a.blk0[pi]) * 16 + (threadIdx.x & 15);
+  const float s = colsum_fold(ws + a.woff[pi], P.cols, c, nchunks, red);
   if (threadIdx.x < 16 && c < P.cols) {
-    s = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
     if (P.dst_rows) {
       // indexed destination rows (periodic position ids): distinct rows receive exactly one value per launch, so the
       // atomic is order-free; only a clamped id that repeats inside one period (positions beyond 511) shares a row

@@ -664,6 +664,96 @@ def test_layernorm_fp32_in_bf16_out_and_tables(HF):
         close(y, torch.nn.functional.layer_norm(s, (cols,), g, b, 1e-5), od, scale=3)
 
 
+def _ln_case(HF, rows, cols, dtype, p_out=0.0, eps=1e-12):
+    """Inputs, the library's forward, and torch autograd through layer_norm(x) [* mask / keep] on fp32 copies.  The output
+    mask is read off the library's own forward: the positions where the dropped output is 0 and the undropped one is not."""
+    x = rnd(rows, cols, dtype=dtype, seed=1) * 2 + 0.5
+    g, b = rnd(cols, seed=2) * 0.1 + 1, rnd(cols, seed=3) * 0.1
+    dy = rnd(rows, cols, dtype=dtype, seed=4)
+    drop = HF.RNG.make(p_out, True, x.device)
+    y, mean, rstd, _ = HF.k_ln_fwd(x, g, b, eps, dtype, rows, cols, drop=drop)
+    xf = x.float().clone().requires_grad_(True)
+    gf, bf = g.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    ref = torch.nn.functional.layer_norm(xf, (cols,), gf, bf, eps)
+    if drop is not None:
+        y0, _, _, _ = HF.k_ln_fwd(x, g, b, eps, dtype, rows, cols)
+        dropped = (y == 0) & (y0 != 0)
+        assert 0.5 * p_out < dropped.float().mean().item() < 1.5 * p_out
+        ref = ref * (~dropped).float() / (1.0 - p_out)
+    close(y, ref, dtype, scale=3)
+    ref.backward(dy.float())
+    return x, g, b, dy, mean, rstd, drop, xf.grad, gf.grad, bf.grad
+
+
+def _ln_param_close(dg, db, ref_g, ref_b, dtype):
+    torch.testing.assert_close(dg, ref_g, rtol=2e-2 if dtype == torch.bfloat16 else 1e-4, atol=0.3 if dtype == torch.bfloat16 else 1e-3)
+    torch.testing.assert_close(db, ref_b, rtol=1e-4, atol=1e-3)
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("cols", [256, 132])
+def test_layernorm_bwd_fused_grid_stride(HF, dtype, cols):
+    """More than 4096 rows: workgroups 0 and 1 of the fused backward take a second grid-stride trip, the last one with
+    one live wave.  256 columns: straight-line kernel; 132: general kernel, VPL 1, the last chunk partly past the row."""
+    rows = 4 * 1024 + 5
+    x, g, _, dy, mean, rstd, _, ref_dx, ref_g, ref_b = _ln_case(HF, rows, cols, dtype)
+    dx, _, dg, db = HF.k_ln_bwd(x, dy, g, mean, rstd)
+    close(dx, ref_dx, dtype, scale=3)
+    _ln_param_close(dg, db, ref_g, ref_b, dtype)
+
+
+def test_layernorm_bwd_fused_general_dropouts(HF):
+    """General fused kernel (516 columns: VPL 3, only lane 0 of the third chunk is live) with the output dropout, then with
+    the input dropout and the feeding linear's bias gradient as well, everything accumulated (beta = 1)."""
+    rows, cols, dtype, p = 9, 516, torch.float32, 0.3
+    x, g, b, dy, mean, rstd, drop, ref_dx, ref_g, ref_b = _ln_case(HF, rows, cols, dtype, p_out=p)
+    dx, _, dg, db = HF.k_ln_bwd(x, dy, g, mean, rstd, drop_out=drop)
+    close(dx, ref_dx, dtype, scale=3)
+    _ln_param_close(dg, db, ref_g, ref_b, dtype)
+    # the input mask, read off a forward with that dropout as the output mask was
+    drop_in = HF.RNG.make(p, True, x.device)
+    y1, _, _, _ = HF.k_ln_fwd(x, g, b, 1e-12, dtype, rows, cols, drop=drop_in)
+    y0, _, _, _ = HF.k_ln_fwd(x, g, b, 1e-12, dtype, rows, cols)
+    mask_in = (~((y1 == 0) & (y0 != 0))).float()
+    assert 0.5 < mask_in.mean().item() < 0.9
+    dg = torch.ones(cols, device="cuda"); db = torch.full((cols,), 2.0, device="cuda"); dbias = torch.full((cols,), 3.0, device="cuda")
+    dx2, dxd, _, _ = HF.k_ln_bwd(x, dy, g, mean, rstd, drop_out=drop, drop_in=drop_in, dgamma=dg, dbeta=db, grad_beta=1.0,
+                                 want_params=False, dbias_in=dbias)
+    close(dx2, ref_dx, dtype, scale=3)
+    torch.testing.assert_close(dxd, dx2 * mask_in / (1 - p), rtol=1e-5, atol=1e-6)
+    close(dxd, ref_dx * mask_in / (1 - p), dtype, scale=3)
+    _ln_param_close(dg, db, 1 + ref_g, 2 + ref_b, dtype)
+    torch.testing.assert_close(dbias, 3 + dxd.sum(0), rtol=1e-4, atol=1e-3)
+    torch.testing.assert_close(dbias, 3 + (ref_dx * mask_in / (1 - p)).sum(0), rtol=1e-4, atol=1e-3)
+
+
+@pytest.mark.parametrize("dtype,rows", [(torch.float32, 21), (torch.bfloat16, 21), (torch.float32, 70)])
+def test_layernorm_bwd_wide_dropout(HF, dtype, rows):
+    """1028 columns, the first width past the fused limit: dx kernel (VPL 6, a partial chunk) + two-stage column reduction,
+    with the output dropout, accumulating.  21 rows: the reduction's tail loop alone; 70: a four-row trip and the tail."""
+    cols = 1028
+    x, g, _, dy, mean, rstd, drop, ref_dx, ref_g, ref_b = _ln_case(HF, rows, cols, dtype, p_out=0.3)
+    dg, db = torch.ones(cols, device="cuda"), torch.full((cols,), 2.0, device="cuda")
+    dx, _, _, _ = HF.k_ln_bwd(x, dy, g, mean, rstd, drop_out=drop, dgamma=dg, dbeta=db, grad_beta=1.0)
+    close(dx, ref_dx, dtype, scale=3)
+    _ln_param_close(dg, db, 1 + ref_g, 2 + ref_b, dtype)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_colsum_no_rows_and_few_rows(HF, Lb, dtype):
+    """hero_colsum without rows: beta = 0 writes zeros, beta = 1 leaves the destination alone; and with fewer rows (3) than
+    the four row-lanes of a workgroup, from a wider source (8 of 16 columns)."""
+    src = rnd(3, 16, dtype=dtype, seed=1)
+    ws = torch.empty(Lb.lib().hero_colsum_workspace_bytes(3, 8) // 4, device="cuda")
+    for beta in (0.0, 1.0):
+        out = torch.full((8,), 0.5, device="cuda")
+        Lb.check(Lb.lib().hero_colsum(src.data_ptr(), out.data_ptr(), 0, 8, 16, Lb.dt(src), beta, ws.data_ptr(), Lb.stream()))
+        assert torch.equal(out, torch.full((8,), 0.5 * beta, device="cuda"))
+        out = torch.full((8,), 0.5, device="cuda")
+        HF.k_colsum(src, out=out, beta=beta, ncols=8)
+        torch.testing.assert_close(out, 0.5 * beta + src.float()[:, :8].sum(0), rtol=1e-4, atol=1e-3)
+
+
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("S,L,H", [(3, 9, 2), (5, 24, 12), (2, 60, 12), (2, 100, 3), (1, 130, 2), (4, 15, 12),
                                    (3, 32, 4), (2, 33, 2), (2, 64, 3), (41, 24, 12), (1, 1, 1), (2, 65, 2),
