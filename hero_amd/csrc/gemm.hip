@@ -428,12 +428,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16_t (&acc)
 struct TileCoord { int m0, n0, kbeg, kend; };
 template <typename CF>
 __device__ __forceinline__ TileCoord tile_coord(const GemmArgs& g) {
-  const int nwg = gridDim.x;
-  int wg;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  const int wg = xcd_order(blockIdx.x, gridDim.x);
   const int ntile = g.tiles_m * g.tiles_n;
   const int split = wg / ntile;
   const int tile = wg - split * ntile;
@@ -793,6 +788,11 @@ __global__ void scale_f32_kernel(float* c, int M, int N, int ldc, float beta) {
   }
 }
 
+int gemm_scale_f32(float* C, int M, int N, int ldc, float beta, hipStream_t s) {
+  hipLaunchKernelGGL(scale_f32_kernel, dim3(1024), dim3(256), 0, s, C, M, N, ldc, beta);
+  return check_launch("hero_gemm(scale)");
+}
+
 // ---- optional per-launch timing with HIP events (bench.py roofline leg) ----------------------------
 struct ProfSlot {
   std::vector<hipEvent_t> ev;  // start/stop pairs
@@ -832,31 +832,23 @@ typedef Cfg<2, 4, 4, 2> Cfg256;
 typedef Cfg<2, 2, 3, 2> Cfg192;    // 192x128: 20 % more FLOP per staged byte, 2 x 80 KB = the whole LDS of a CU
 typedef Cfg<2, 2, 1, 1> Cfg64;     // 64x64 tiles for problems that leave most CUs idle at 128x128
 
-template <typename T, int AL, int BL, typename CF>
-static int launch(GemmArgs g, hipStream_t s) {
-  HERO_ENSURE_LDS((&gemm_kernel<T, AL, BL, CF>), CF::LDS, "gemm_kernel");
+// the launch of a 4-wave kernel: one workgroup of NT threads per (tile of CF, reduction split); slot: see g_prof
+template <typename CF>
+static int launch_tiles(void (*kernel)(GemmArgs), GemmArgs g, int nt, int lds, int slot, const char* what, hipStream_t s) {
   g.tiles_m = (g.M + CF::BM - 1) / CF::BM;
   g.tiles_n = (g.N + CF::BN - 1) / CF::BN;
   const int split = g.epi.split_k > 1 ? g.epi.split_k : 1;
   const int grid = g.tiles_m * g.tiles_n * split;
-  ProfSlot* ps = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (g_prof_on) {
-    ps = &g_prof[(sizeof(T) == 2 ? 4 : 0) + AL * 2 + BL];
-    if (ps->flops.size() < 16384 && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-      (void)hipEventRecord(e0, s);
-    } else {
-      ps = nullptr;
-    }
-  }
-  hipLaunchKernelGGL((gemm_kernel<T, AL, BL, CF>), dim3(grid), dim3(CF::NT), CF::LDS, s, g);
-  if (ps) {
-    (void)hipEventRecord(e1, s);
-    ps->ev.push_back(e0);
-    ps->ev.push_back(e1);
-    ps->flops.push_back(2.0 * (double)g.M * (double)g.N * (double)g.K);
-  }
-  return check_launch("hero_gemm");
+  void* tok = gemm_prof_begin(slot, s);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(nt), lds, s, g);
+  gemm_prof_end(tok, 2.0 * (double)g.M * (double)g.N * (double)g.K, s);
+  return check_launch(what);
+}
+
+template <typename T, int AL, int BL, typename CF>
+static int launch(const GemmArgs& g, hipStream_t s) {
+  HERO_ENSURE_LDS((&gemm_kernel<T, AL, BL, CF>), CF::LDS, "gemm_kernel");
+  return launch_tiles<CF>(gemm_kernel<T, AL, BL, CF>, g, CF::NT, CF::LDS, (sizeof(T) == 2 ? 4 : 0) + AL * 2 + BL, "hero_gemm", s);
 }
 
 // Geometry choice (measured on MI355X, tools/gemm_bench.py): the 128x128 tile with two resident
@@ -898,30 +890,9 @@ template __global__ void gemm_glds_kernel<float, Cfg128, EK_GENERIC>(GemmArgs);
 template __global__ void gemm_glds_kernel<float, Cfg256, EK_GENERIC>(GemmArgs);
 
 template <typename T, typename CF, int EK>
-static int launch_glds_ek(GemmArgs g, hipStream_t s) {
+static int launch_glds_ek(const GemmArgs& g, hipStream_t s) {
   HERO_ENSURE_LDS((&gemm_glds_kernel<T, CF, EK>), GldsRing<CF>::LDS, "gemm_glds_kernel");
-  g.tiles_m = (g.M + CF::BM - 1) / CF::BM;
-  g.tiles_n = (g.N + CF::BN - 1) / CF::BN;
-  const int split = g.epi.split_k > 1 ? g.epi.split_k : 1;
-  const int grid = g.tiles_m * g.tiles_n * split;
-  ProfSlot* ps = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (g_prof_on) {
-    ps = &g_prof[(sizeof(T) == 2 ? 4 : 0)];
-    if (ps->flops.size() < 16384 && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-      (void)hipEventRecord(e0, s);
-    } else {
-      ps = nullptr;
-    }
-  }
-  hipLaunchKernelGGL((gemm_glds_kernel<T, CF, EK>), dim3(grid), dim3(CF::NT), GldsRing<CF>::LDS, s, g);
-  if (ps) {
-    (void)hipEventRecord(e1, s);
-    ps->ev.push_back(e0);
-    ps->ev.push_back(e1);
-    ps->flops.push_back(2.0 * (double)g.M * (double)g.N * (double)g.K);
-  }
-  return check_launch("hero_gemm(glds)");
+  return launch_tiles<CF>(gemm_glds_kernel<T, CF, EK>, g, CF::NT, GldsRing<CF>::LDS, sizeof(T) == 2 ? 4 : 0, "hero_gemm(glds)", s);
 }
 
 // epilogue specialisation: the hot-path combinations of the bf16 training step get their own
@@ -941,31 +912,9 @@ static int launch_glds(const GemmArgs& g, hipStream_t s) {
   return launch_glds_ek<T, CF, EK_GENERIC>(g, s);
 }
 
-static int launch_glds_tr(GemmArgs g, hipStream_t s) {
-  typedef Cfg<2, 2, 2, 2> CF;
-  g.tiles_m = (g.M + CF::BM - 1) / CF::BM;
-  g.tiles_n = (g.N + CF::BN - 1) / CF::BN;
-  const int split = g.epi.split_k > 1 ? g.epi.split_k : 1;
-  const int grid = g.tiles_m * g.tiles_n * split;
-  ProfSlot* ps = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (g_prof_on) {
-    ps = &g_prof[7];
-    if (ps->flops.size() < 16384 && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-      (void)hipEventRecord(e0, s);
-    } else {
-      ps = nullptr;
-    }
-  }
+static int launch_glds_tr(const GemmArgs& g, hipStream_t s) {
   HERO_ENSURE_LDS(&gemm_glds_tr_kernel, 65536, "gemm_glds_tr_kernel");
-  hipLaunchKernelGGL(gemm_glds_tr_kernel, dim3(grid), dim3(256), 65536, s, g);
-  if (ps) {
-    (void)hipEventRecord(e1, s);
-    ps->ev.push_back(e0);
-    ps->ev.push_back(e1);
-    ps->flops.push_back(2.0 * (double)g.M * (double)g.N * (double)g.K);
-  }
-  return check_launch("hero_gemm(glds_tr)");
+  return launch_tiles<Cfg128>(gemm_glds_tr_kernel, g, 256, 65536, 7, "hero_gemm(glds_tr)", s);
 }
 
 template <typename T, int AL, int BL>
@@ -1110,6 +1059,15 @@ __global__ __launch_bounds__(256) void gemm_skinny_f32_kernel(const float* __res
   }
 }
 
+// Reduction splits a request for split_k gets: at most one per k-tile, rounded so that no split is empty (*per: k-tiles each).
+static int split_count(int K, int split_k, int bk, int* per) {
+  const int ktiles = (K + bk - 1) / bk;
+  int split = split_k < ktiles ? split_k : ktiles;
+  if (split <= 1) return 1;
+  *per = (ktiles + split - 1) / split;
+  return (ktiles + *per - 1) / *per;
+}
+
 extern "C" int hero_gemm(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
                          int a_layout, int b_layout, int dtype, const HeroGemmEpilogue* epi, hero_stream_t stream) {
   HERO_REQUIRE(A && B && C && epi, "hero_gemm: null pointer");
@@ -1159,22 +1117,17 @@ extern "C" int hero_gemm(const void* A, const void* B, void* C, int M, int N, in
   if (epi->split_k > 1) {
     HERO_REQUIRE(epi->out_f32 && epi->act == HERO_ACT_NONE && !epi->bias && !epi->residual && epi->dropout.threshold16 == 0,
                  "hero_gemm: split_k supports only a plain fp32 accumulate epilogue");
-    const int ktiles = (K + bk - 1) / bk;
-    int split = epi->split_k < ktiles ? epi->split_k : ktiles;
+    int per = 0;
+    const int split = split_count(K, epi->split_k, bk, &per);
     if (split > 1) {
-      const int per = (ktiles + split - 1) / split;
-      split = (ktiles + per - 1) / per;
-      if (split > 1) {
-        if (epi->split_stride == 0 && epi->beta != 1.f) {  // atomics accumulate into beta * C (slabs are overwritten)
-          hipLaunchKernelGGL(scale_f32_kernel, dim3(1024), dim3(256), 0, s, static_cast<float*>(C), M, N, ldc, epi->beta);
-          const int rc = check_launch("hero_gemm(scale)");
-          if (rc) return rc;
-        }
-        g.k_per_split = per * bk;
-        g.epi.split_k = split;
-        const int cfg = pick_cfg(M, N, split, k_contig);
-        return dtype == HERO_BF16 ? dispatch<bf16_t>(g, a_layout, b_layout, cfg, s) : dispatch<float>(g, a_layout, b_layout, cfg, s);
+      if (epi->split_stride == 0 && epi->beta != 1.f) {  // atomics accumulate into beta * C (slabs are overwritten)
+        const int rc = gemm_scale_f32(static_cast<float*>(C), M, N, ldc, epi->beta, s);
+        if (rc) return rc;
       }
+      g.k_per_split = per * bk;
+      g.epi.split_k = split;
+      const int cfg = pick_cfg(M, N, split, k_contig);
+      return dtype == HERO_BF16 ? dispatch<bf16_t>(g, a_layout, b_layout, cfg, s) : dispatch<float>(g, a_layout, b_layout, cfg, s);
     }
   }
   g.k_per_split = K > 0 ? ((K + bk - 1) / bk) * bk : bk;
@@ -1184,12 +1137,8 @@ extern "C" int hero_gemm(const void* A, const void* B, void* C, int M, int N, in
 }
 
 extern "C" int hero_gemm_splits(int K, int split_k, int dtype) {
-  const int bk = dtype == HERO_BF16 ? 64 : 32;
-  const int ktiles = (K + bk - 1) / bk;
-  int split = split_k < ktiles ? split_k : ktiles;
-  if (split <= 1) return 1;
-  const int per = (ktiles + split - 1) / split;
-  return (ktiles + per - 1) / per;
+  int per = 0;
+  return split_count(K, split_k, dtype == HERO_BF16 ? 64 : 32, &per);
 }
 
 // Tuning hook: force a tile geometry (0: 128x128, 1: 192x128, 2: 256x256, 3: 64x64 [1 and 3: direct-to-LDS path only], -1: heuristic).

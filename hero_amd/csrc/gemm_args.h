@@ -12,6 +12,18 @@ enum { EK_GENERIC = 0x100, EK_BIAS = 1, EK_GELU = 2, EK_RES = 4, EK_DROP = 8, EK
 void* gemm_prof_begin(int slot, hipStream_t s);
 void gemm_prof_end(void* token, double flops, hipStream_t s);
 
+// C <- beta * C over an [M, N] fp32 matrix (pre-pass of the fp32-atomic accumulate paths; gemm.hip)
+int gemm_scale_f32(float* C, int M, int N, int ldc, float beta, hipStream_t s);
+
+int num_cus();                // compute units of the current device (gemm_ws.hip)
+
+// Logical workgroup index of block `bid` of an nwg-block grid.  The hardware deals consecutive block ids round-robin to the
+// 8 XCDs; in the logical order every XCD owns one contiguous chunk, so neighbouring tiles share their panels in its L2.
+__device__ __forceinline__ int xcd_order(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+}
+
 int gemm_forced_config();     // hero_gemm_force_config state (gemm.hip): -1 heuristic, 8 = 4-wave kernels only, 9 = wave-specialised always
 
 // gemm_ws.hip.  Returns -1 when the problem is outside this kernel family (caller falls through to the

@@ -59,17 +59,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwg = gridDim.x;
-  int wg;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  const int wg = xcd_order(blockIdx.x, nwg);
 
   if (wave >= 4) {
     // ------------------------------------------------------------------ loader waves
     // The ring holds NSG stages: NSG - 1 are issued ahead, the wave then always waits until all but the NSG - 2 youngest
     // have landed (VMEM operations of a wave complete in order), i.e. until the stage the compute waves read next is in.
-    Loader<G, TR> ld(g, smem, wg, nwg, wave - 4, lane);
+    Loader<G, TR, ItemSource<G>> ld(ItemSource<G>{g, wg, nwg}, smem, wave - 4, lane);
     constexpr int AHEAD = (G::NSG - 2) * G::PW;
     bool more = ld.issue();
 #pragma unroll
@@ -97,129 +93,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
   // -------------------------------------------------------------------- compute waves
   const int wm = wave >> 1, wn = wave & 1;
-  const int arow0 = wm * TM * 32, brow0 = wn * TN * 32;
-  unsigned ao[TM], bo[TN];                                            // per-lane LDS offsets inside a stage (slice 0)
-  if (!TR) {
-    const int r = lane & 31, kg = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) { const int ra = arow0 + i * 32 + r; ao[i] = ra * 128 + ((kg ^ swz_k(ra)) << 4); }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) { const int rb = brow0 + j * 32 + r; bo[j] = G::A_BYTES + rb * 128 + ((kg ^ swz_k(rb)) << 4); }
-  } else {
-    const int p = lane & 15, gq = (lane >> 4) & 1, kg = lane >> 5;
-    const int krow = kg * 8 + (p >> 2);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int col = arow0 + i * 32 + gq * 16 + 4 * (p & 3);
-      ao[i] = krow * (G::BM * 2) + ((((col >> 3) ^ swz_o<G::BM * 2>(krow)) << 4) | ((col & 7) * 2));
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int col = brow0 + j * 32 + gq * 16 + 4 * (p & 3);
-      bo[j] = G::A_BYTES + krow * (G::BN * 2) + ((((col >> 3) ^ swz_o<G::BN * 2>(krow)) << 4) | ((col & 7) * 2));
-    }
-  }
-  bf16x8_t a0[TM], b0[TN], a1[TM], b1[TN];
-  // Read order a[0], b[0..], a[1..]: the MFMAs of the NEXT slice run (i outer, j inner), the reads are spread over the
-  // MFMAs of the current slice in this order, so every fragment is requested >= 7 MFMAs (224 cycles) before its first
-  // use (a[0..], b[0..] order: 5 MFMAs for b[0] - less than the LDS latency beside the DMA writes).
-  auto ldf = [&](bf16x8_t (&a)[TM], bf16x8_t (&b)[TN], const char* st, int ks) {
-    typedef __attribute__((address_space(3))) bf16x4_t* lp_t;
-    auto ra = [&](int i) {
-      if (!TR) {
-        a[i] = *reinterpret_cast<const bf16x8_t*>(st + (ao[i] ^ (ks << 5)));
-      } else {
-        const char* q = st + ao[i] + ks * 16 * (G::BM * 2);
-        const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q));
-        const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q + 4 * (G::BM * 2)));
-        a[i] = bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-    };
-    auto rb = [&](int j) {
-      if (!TR) {
-        b[j] = *reinterpret_cast<const bf16x8_t*>(st + (bo[j] ^ (ks << 5)));
-      } else {
-        const char* q = st + bo[j] + ks * 16 * (G::BN * 2);
-        const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q));
-        const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q + 4 * (G::BN * 2)));
-        b[j] = bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-    };
-    if (!TR) {                                      // K,K: the MFMA is (b[j], a[i]) but the loop order is the same
-      ra(0);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) rb(j);
-#pragma unroll
-      for (int i = 1; i < TM; ++i) ra(i);
-    } else {
-      ra(0);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) rb(j);
-#pragma unroll
-      for (int i = 1; i < TM; ++i) ra(i);
-    }
-  };
-  f32x16_t acc[TM][TN];
-  auto mma = [&](const bf16x8_t (&a)[TM], const bf16x8_t (&b)[TN]) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if (!TR) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j], a[i], acc[i][j], 0, 0, 0);   // D^T: lane <-> output row
-        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-      }
-  };
-
+  MainLoop<G, TR, !TR> ml(smem, wm, wn, lane);        // K,K: swapped operands (epilogue_rows), O,O: unswapped (atomic_tile)
   __builtin_amdgcn_s_setprio(2);
   __builtin_amdgcn_s_barrier();                                       // B(-1)
-  unsigned curo = 0;
-  if (wg < g.nwork) ldf(a0, b0, smem, 0);
+  if (wg < g.nwork) ml.read_first();
   int item_no = 0;
   for (int cit = wg; cit < g.nwork; cit += nwg, ++item_no) {
     const Item ic = item_coord<G>(g, cit);
     WS_T(item_no, 0, wave, lane);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    ml.template zero<false>();
     const bool more_items = cit + nwg < g.nwork;
-    unsigned last = curo;
-    for (int t = 0; t < ic.nk; ++t) {
-      const char* cur = smem + curo;
-      last = curo;
-      curo += G::STAGE;
-      if (curo == G::NSG * G::STAGE) curo = 0;
-      const char* nxt = smem + curo;
-      // one scheduling region per 16-k slice: the fragment reads of the NEXT slice are spread between the MFMAs of the
-      // current one (round 3; as a block in front of them they cost MFMA-idle issue time, see gemm_wsb_kernel)
-      constexpr int NRD = TR ? 2 * (TM + TN) : TM + TN;
-      ldf(a1, b1, cur, 1);
-      mma(a0, b0);
-      WS_INTERLEAVE(TM * TN, NRD);
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a0, b0, cur, 2);
-      mma(a1, b1);
-      WS_INTERLEAVE(TM * TN, NRD);
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a1, b1, cur, 3);
-      mma(a0, b0);
-      WS_INTERLEAVE(TM * TN, NRD);
-      __builtin_amdgcn_sched_barrier(0);
-      wait_lds();
-      __builtin_amdgcn_s_barrier();                                   // B(u): done reading `cur`, stage u+1 landed
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a0, b0, nxt, 0);            // unconditional: behind an item's last step it reads the next item's landed first
-      mma(a1, b1);                    // stage (K,K: read again after the epilogue) or stale LDS, never used
-      WS_INTERLEAVE(TM * TN, NRD);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    ml.template run<false>(ic.nk);
     if constexpr (!TR) {
       __builtin_amdgcn_s_setprio(0);
       WS_T(item_no, 1, wave, lane);
 #ifndef HERO_WS_NOEPI
-      epilogue_rows<G, EK, true>(g, ic, smem, last, acc, wave, lane, item_no);
+      epilogue_rows<G, EK, true>(g, ic, smem, ml.last, ml.acc, wave, lane, item_no);
 #else
       {                                     // every accumulator element stays live (or the compiler deletes MFMAs); never true
         float sum = 0.f;
@@ -228,26 +117,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) sum += acc[i][j][e];
+            for (int e = 0; e < 16; ++e) sum += ml.acc[i][j][e];
         if (sum == 1.2345e-30f) static_cast<bf16_t*>(g.C)[lane] = (bf16_t)1;
       }
 #endif
       __builtin_amdgcn_s_setprio(2);
-      if (more_items) ldf(a0, b0, smem + curo, 0);
+      if (more_items) ml.read_first();
     } else {
-      // fp32 atomics from the accumulator layout: 32 consecutive columns per half-wave, two rows per instruction
-      float* C = static_cast<float*>(g.C);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int gn = ic.n0 + brow0 + j * 32 + (lane & 31);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int gm = ic.m0 + arow0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (gm < g.M && gn < g.N) atomicAdd(C + (size_t)gm * g.ldc + gn, acc[i][j][r]);
-          }
-        }
+      atomic_tile<TM, TN>(static_cast<float*>(g.C), g.ldc, g.M, g.N, ic.m0 + wm * TM * 32, ic.n0 + wn * TN * 32, ml.acc, lane);
     }
   }
 }
@@ -291,6 +168,21 @@ __device__ __forceinline__ Seg seg_at(const WsgArgs& g, int pos, int end) {
   return s;
 }
 
+// panel source: the segments of the range [pos, end) of the group's (tile, k-step) space
+struct SegSource {
+  static constexpr bool DMA = true;
+  const WsgArgs& g;
+  int pos, end, nk;
+  __device__ __forceinline__ bool done() const { return pos >= end; }
+  __device__ __forceinline__ Panel panel() {
+    const Seg sg = seg_at<Geo<3, 3>>(g, pos, end);
+    const WsgProb& P = g.p[sg.prob];
+    nk = sg.nk;
+    return Panel{P.A, P.B, P.lda, P.ldb, P.M, P.N, g.K, sg.m0, sg.n0, sg.k0 * 64, sg.nk};
+  }
+  __device__ __forceinline__ void advance() { pos += nk; }
+};
+
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_wsg_kernel(WsgArgs g) {
   typedef Geo<3, 3> G;
   constexpr int TM = 3, TN = 3;
@@ -298,77 +190,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwg = gridDim.x;
-  int wg;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  const int wg = xcd_order(blockIdx.x, nwg);
   const long long total = (long long)g.total_tiles * g.ksteps;
   const int start = (int)(total * wg / nwg), end = (int)(total * (wg + 1) / nwg);
   if (start >= end) return;                                          // uniform for the workgroup
 
   if (wave >= 4) {
     // ------------------------------------------------------------------ loader waves
-    const int w = wave - 4;
-    constexpr int CA = G::BM / 8, CB = G::BN / 8;
-    int pos = start;                 // next stage to issue belongs to the segment that contains `pos`
-    Seg sg = seg_at<G>(g, pos, end);
-    int ik = 0;
-    unsigned goa[G::PA], gob[G::PB];
-    const char* pa = nullptr;
-    const char* pb = nullptr;
-    unsigned ra_left = 0, rb_left = 0, sa = 0, sb = 0, fill = 0;
-    auto setup = [&]() {
-      const WsgProb& P = g.p[sg.prob];
-#pragma unroll
-      for (int i = 0; i < G::PA; ++i) {
-        const int id = (w * G::PA + i) * 64 + lane, row = id / CA, c = (id % CA) ^ swz_o<G::BM * 2>(row);
-        goa[i] = (unsigned)row * (unsigned)P.lda * 2u + (c << 4);
-      }
-#pragma unroll
-      for (int i = 0; i < G::PB; ++i) {
-        const int id = (w * G::PB + i) * 64 + lane, row = id / CB, c = (id % CB) ^ swz_o<G::BN * 2>(row);
-        gob[i] = (unsigned)row * (unsigned)P.ldb * 2u + (c << 4);
-      }
-      const int kb = sg.k0 * 64;
-      pa = reinterpret_cast<const char*>(P.A + (size_t)kb * P.lda + sg.m0);
-      pb = reinterpret_cast<const char*>(P.B + (size_t)kb * P.ldb + sg.n0);
-      ra_left = (unsigned)(((size_t)(g.K - kb) * P.lda - sg.m0) * 2);
-      rb_left = (unsigned)(((size_t)(g.K - kb) * P.ldb - sg.n0) * 2);
-      sa = 64u * (unsigned)P.lda * 2u;
-      sb = 64u * (unsigned)P.ldb * 2u;
-    };
-    setup();
-    auto issue = [&]() -> bool {
-      if (pos >= end) return false;
-      char* buf = smem + fill;
-      const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pa), 0, ra_left, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pb), 0, rb_left, 0x00020000);
-#pragma unroll
-      for (int i = 0; i < G::PA; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, HERO_LDS_PTR(buf + (w * G::PA + i) * 1024), 16, goa[i], 0, 0, HERO_WS_LOAD_AUX_A);
-#pragma unroll
-      for (int i = 0; i < G::PB; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, HERO_LDS_PTR(buf + G::A_BYTES + (w * G::PB + i) * 1024), 16, gob[i], 0, 0, HERO_WS_LOAD_AUX_B);
-      fill += G::STAGE;
-      if (fill == NS * G::STAGE) fill = 0;
-      ++pos;
-      if (++ik == sg.nk) {
-        ik = 0;
-        if (pos < end) { sg = seg_at<G>(g, pos, end); setup(); }
-      } else {
-        pa += sa; pb += sb;
-        ra_left = ra_left > sa ? ra_left - sa : 0u;
-        rb_left = rb_left > sb ? rb_left - sb : 0u;
-      }
-      return true;
-    };
-    issue();
-    const bool second = issue();
+    Loader<G, true, SegSource> ld(SegSource{g, start, end, 0}, smem, wave - 4, lane);
+    ld.issue();
+    const bool second = ld.issue();
     if (second) wait_vm<G::PW>(); else wait_vm<0>();
     __builtin_amdgcn_s_barrier();                                     // B(-1)
     for (int u = start; u < end; ++u) {
-      if (issue()) wait_vm<G::PW>(); else wait_vm<0>();
+      if (ld.issue()) wait_vm<G::PW>(); else wait_vm<0>();
       __builtin_amdgcn_s_barrier();                                   // B(u)
     }
     return;
@@ -376,105 +211,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
   // -------------------------------------------------------------------- compute waves
   const int wm = wave >> 1, wn = wave & 1;
-  const int arow0 = wm * TM * 32, brow0 = wn * TN * 32;
-  unsigned ao[TM], bo[TN];
-  {
-    const int p = lane & 15, gq = (lane >> 4) & 1, kg = lane >> 5;
-    const int krow = kg * 8 + (p >> 2);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int col = arow0 + i * 32 + gq * 16 + 4 * (p & 3);
-      ao[i] = krow * (G::BM * 2) + ((((col >> 3) ^ swz_o<G::BM * 2>(krow)) << 4) | ((col & 7) * 2));
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int col = brow0 + j * 32 + gq * 16 + 4 * (p & 3);
-      bo[j] = G::A_BYTES + krow * (G::BN * 2) + ((((col >> 3) ^ swz_o<G::BN * 2>(krow)) << 4) | ((col & 7) * 2));
-    }
-  }
-  typedef __attribute__((address_space(3))) bf16x4_t* lp_t;
-  bf16x8_t a0[TM], b0[TN], a1[TM], b1[TN];
-  auto ldf = [&](bf16x8_t (&a)[TM], bf16x8_t (&b)[TN], const char* st, int ks) {       // order a[0], b[..], a[1..]: see gemm_ws_kernel
-    auto ra = [&](int i) {
-      const char* q = st + ao[i] + ks * 16 * (G::BM * 2);
-      const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q));
-      const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q + 4 * (G::BM * 2)));
-      a[i] = bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    };
-    ra(0);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const char* q = st + bo[j] + ks * 16 * (G::BN * 2);
-      const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q));
-      const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q + 4 * (G::BN * 2)));
-      b[j] = bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    }
-#pragma unroll
-    for (int i = 1; i < TM; ++i) ra(i);
-  };
-  f32x16_t acc[TM][TN];
-  auto mma = [&](const bf16x8_t (&a)[TM], const bf16x8_t (&b)[TN]) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-  };
+  MainLoop<G, true, false> ml(smem, wm, wn, lane);
   __builtin_amdgcn_s_setprio(2);
   __builtin_amdgcn_s_barrier();                                       // B(-1)
-  unsigned curo = 0;
-  ldf(a0, b0, smem, 0);
+  ml.read_first();
   [[maybe_unused]] int seg_no = 0;
   for (int pos = start; pos < end; ++seg_no) {
     const Seg sg = seg_at<G>(g, pos, end);
     WS_T(seg_no, 0, wave, lane);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    for (int t = 0; t < sg.nk; ++t) {
-      const char* cur = smem + curo;
-      curo += G::STAGE;
-      if (curo == NS * G::STAGE) curo = 0;
-      const char* nxt = smem + curo;
-      ldf(a1, b1, cur, 1);
-      mma(a0, b0);
-      WS_INTERLEAVE(TM * TN, 2 * (TM + TN));
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a0, b0, cur, 2);
-      mma(a1, b1);
-      WS_INTERLEAVE(TM * TN, 2 * (TM + TN));
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a1, b1, cur, 3);
-      mma(a0, b0);
-      WS_INTERLEAVE(TM * TN, 2 * (TM + TN));
-      __builtin_amdgcn_sched_barrier(0);
-      wait_lds();
-      __builtin_amdgcn_s_barrier();                                   // B(u)
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a0, b0, nxt, 0);            // unconditional (stale LDS behind the range's last step, never used)
-      mma(a1, b1);
-      WS_INTERLEAVE(TM * TN, 2 * (TM + TN));
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    ml.zero<false>();
+    ml.run<false>(sg.nk);
     pos += sg.nk;
     WS_T(seg_no, 1, wave, lane);
 #ifdef HERO_WS_TRACE
     if (blockIdx.x == 0 && lane == 0 && seg_no < 4) g_ws_trace[(seg_no * 16 + 3) * 8 + wave] = (unsigned long long)sg.nk;
 #endif
     const WsgProb& P = g.p[sg.prob];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int gn = sg.n0 + brow0 + j * 32 + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int gm = sg.m0 + arow0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          if (gm < P.M && gn < P.N) atomicAdd(P.C + (size_t)gm * P.ldc + gn, acc[i][j][r]);
-        }
-      }
+    atomic_tile<TM, TN>(P.C, P.ldc, P.M, P.N, sg.m0 + wm * TM * 32, sg.n0 + wn * TN * 32, ml.acc, lane);
     WS_T(seg_no, 14, wave, lane);
   }
 }
@@ -516,19 +269,16 @@ struct WsbArgs {
 template <typename G, bool COMPUTE>
 __device__ __forceinline__ void epilogue_acc(const WsbProb& P, const WsbItem& it, int* flags, char* smem, unsigned slot,
                                              f32x16_t (*acc)[G::TN], int wave, int lane, bool want_cs = false) {
-  constexpr int TM = G::TM, TN = G::TN, BN = G::BN, RPP = G::RPP, C8 = G::C8, RPI = G::RPI, ITERS = G::ITERS;
+  constexpr int BN = G::BN, RPP = G::RPP, RPI = G::RPI, ITERS = G::ITERS;
   char* st = smem + slot;
-  int tid = threadIdx.x;                             // opaque copy: see epilogue_rows
-  asm volatile("" : "+v"(tid));
-  lane = tid & 63;
-  wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c8 = tid % C8, r0 = tid / C8;
+  const PassLane<G> pl;                               // opaque copy of the thread index: see PassLane
+  const int tid = pl.tid, c8 = pl.c8, r0 = pl.r0;
+  lane = pl.lane;
+  wave = pl.wave;
   const int gn = it.n0 + c8 * 8;
   const bool col_ok = r0 < RPI && gn < P.N;
-  const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
   const bool plain = it.nslices == 1;                                 // uniform
-  constexpr bool SPLIT = (RPP == 64 && G::PASSES == TM);
-  auto tile_row = [](int p, int row) { return SPLIT ? (row >> 5) * (TM * 32) + p * 32 + (row & 31) : p * RPP + row; };
+  auto tile_row = [](int p, int row) { return PassLane<G>::tile_row(p, row); };
   // dW through a buffer descriptor: masked-off lanes get an out-of-range offset (loads return 0, stores are dropped),
   // so every access of a pass is issued back to back in straight-line code (a branch per store makes hipcc wait for
   // the previous store's round trip in every iteration: 58 us instead of 7 per tile)
@@ -559,23 +309,7 @@ __device__ __forceinline__ void epilogue_acc(const WsbProb& P, const WsbItem& it
 #endif
       }
     }
-    if constexpr (COMPUTE) {
-#pragma unroll
-      for (int b = 0; b < RPP / 32; ++b) {
-        const int blk = SPLIT ? b * TM + p : p * (RPP / 32) + b;
-        if (wm == blk / TM) {
-          const int i = blk % TM;
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int chunk = (wn * TN * 32 + j * 32 + 8 * q + 4 * half) >> 2;
-              const f32x4_t v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-              *reinterpret_cast<f32x4_t*>(st + (32 * b + l31) * G::ROWB + ((chunk ^ (l31 & 7)) << 4)) = v;
-            }
-        }
-      }
-    }
+    if constexpr (COMPUTE) pl.stage_pass(st, p, acc);
     wait_lds();
     __builtin_amdgcn_s_barrier();                    // E1: the pass is staged
     if constexpr (!COMPUTE) {
@@ -640,100 +374,68 @@ __device__ __forceinline__ void epilogue_acc(const WsbProb& P, const WsbItem& it
     __hip_atomic_store(flags + it.flag, it.order + 1 < it.nslices ? it.order + 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// the next busy round of workgroup wg at or after r (rounds with an idle slot are skipped by all eight waves alike)
+__device__ __forceinline__ int wsb_next_round(const WsbArgs& g, int r, int nwg, int wg) {
+  while (r < g.rounds && g.items[(size_t)r * nwg + wg].nk == 0) ++r;
+  return r;
+}
+
+// panel source: the plan rounds of workgroup wg, idle slots skipped
+struct PlanSource {
+#ifdef HERO_WSB_NOLOADS         // lab ablations (tools/lab/build_variants.sh): results are garbage, timing only
+  static constexpr bool DMA = false;
+#else
+  static constexpr bool DMA = true;
+#endif
+  const WsbArgs& g;
+  int nwg, wg, lr;
+  __device__ __forceinline__ bool done() const { return lr >= g.rounds; }
+  __device__ __forceinline__ Panel panel() const {
+    const WsbItem it = g.items[(size_t)lr * nwg + wg];
+    const WsbProb& P = g.p[it.prob];
+    return Panel{P.A, P.B, P.lda, P.ldb, P.M, P.N, g.K, it.m0, it.n0, it.k0 * 64, it.nk};
+  }
+  __device__ __forceinline__ void advance() { lr = wsb_next_round(g, lr + 1, nwg, wg); }
+};
+
+constexpr int WSB_LAB = 0
+#ifdef HERO_WSB_NOLDF
+                        | LAB_NOLDF
+#endif
+#ifdef HERO_WSB_NOMFMA
+                        | LAB_NOMFMA
+#endif
+#ifdef HERO_WSB_NOBAR
+                        | LAB_NOBAR
+#endif
+    ;
+
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_wsb_kernel(WsbArgs g) {
   typedef Geo<3, 3> G;
-  constexpr int TM = 3, TN = 3;
+  constexpr int TM = 3;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwg = gridDim.x;
-  int wg;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
-  // the next busy round of this workgroup at or after r (rounds with an idle slot are skipped by all eight waves alike)
-  auto next_round = [&](int r) {
-    while (r < g.rounds && g.items[(size_t)r * nwg + wg].nk == 0) ++r;
-    return r;
-  };
+  const int wg = xcd_order(blockIdx.x, nwg);
 
   if (wave >= 4) {
     // ------------------------------------------------------------------ loader waves
-    const int w = wave - 4;
-    constexpr int CA = G::BM / 8, CB = G::BN / 8;
-    int lr = next_round(0), ik = 0, lnk = 0;       // round / stage being issued next
-    unsigned goa[G::PA], gob[G::PB];
-    const char* pa = nullptr;
-    const char* pb = nullptr;
-    unsigned long long ra_left = 0, rb_left = 0;   // bytes to the end of the operand (64-bit: 1.4 M rows x 3072 columns at config 5)
-    unsigned sa = 0, sb = 0, fill = 0;
-    auto setup = [&]() {
-      const WsbItem it = g.items[(size_t)lr * nwg + wg];
-      const WsbProb& P = g.p[it.prob];
-      lnk = it.nk;
-#pragma unroll
-      for (int i = 0; i < G::PA; ++i) {
-        const int id = (w * G::PA + i) * 64 + lane, row = id / CA, c = (id % CA) ^ swz_o<G::BM * 2>(row);
-        goa[i] = (unsigned)row * (unsigned)P.lda * 2u + (c << 4);
-      }
-#pragma unroll
-      for (int i = 0; i < G::PB; ++i) {
-        const int id = (w * G::PB + i) * 64 + lane, row = id / CB, c = (id % CB) ^ swz_o<G::BN * 2>(row);
-        gob[i] = (unsigned)row * (unsigned)P.ldb * 2u + (c << 4);
-      }
-      const int kb = it.k0 * 64;
-      pa = reinterpret_cast<const char*>(P.A + (size_t)kb * P.lda + it.m0);
-      pb = reinterpret_cast<const char*>(P.B + (size_t)kb * P.ldb + it.n0);
-      ra_left = ((unsigned long long)(g.K - kb) * P.lda - it.m0) * 2;
-      rb_left = ((unsigned long long)(g.K - kb) * P.ldb - it.n0) * 2;
-      sa = 64u * (unsigned)P.lda * 2u;
-      sb = 64u * (unsigned)P.ldb * 2u;
-    };
-    if (lr < g.rounds) setup();
-    auto issue = [&]() -> bool {
-      if (lr >= g.rounds) return false;
-      char* buf = smem + fill;
-      // the descriptor base moves with the k-step, so offsets stay small; only the range is clamped to 32 bits
-      const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pa), 0, (unsigned)(ra_left < 0xfffffff0ull ? ra_left : 0xfffffff0ull), 0x00020000);
-      const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pb), 0, (unsigned)(rb_left < 0xfffffff0ull ? rb_left : 0xfffffff0ull), 0x00020000);
-#ifndef HERO_WSB_NOLOADS        // lab ablations (tools/lab/build_variants.sh): results are garbage, timing only
-#pragma unroll
-      for (int i = 0; i < G::PA; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, HERO_LDS_PTR(buf + (w * G::PA + i) * 1024), 16, goa[i], 0, 0, HERO_WS_LOAD_AUX_A);
-#pragma unroll
-      for (int i = 0; i < G::PB; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, HERO_LDS_PTR(buf + G::A_BYTES + (w * G::PB + i) * 1024), 16, gob[i], 0, 0, HERO_WS_LOAD_AUX_B);
-#else
-      (void)ra; (void)rb; (void)buf;
-#endif
-      fill += G::STAGE;
-      if (fill == NS * G::STAGE) fill = 0;
-      if (++ik == lnk) {
-        ik = 0;
-        lr = next_round(lr + 1);
-        if (lr < g.rounds) setup();
-      } else {
-        pa += sa; pb += sb;
-        ra_left = ra_left > sa ? ra_left - sa : 0ull;
-        rb_left = rb_left > sb ? rb_left - sb : 0ull;
-      }
-      return true;
-    };
-    issue();
-    const bool second = issue();
+    Loader<G, true, PlanSource> ld(PlanSource{g, nwg, wg, wsb_next_round(g, 0, nwg, wg)}, smem, wave - 4, lane);
+    ld.issue();
+    const bool second = ld.issue();
     if (second) wait_vm<G::PW>(); else wait_vm<0>();
     __builtin_amdgcn_s_barrier();                                     // B(-1): stage 0 landed
     unsigned slot = 0;
     // Bias gradients (WsbProb.colsum): the column sums of the dY panel come from the COMPUTE waves (one extra MFMA per row
-    // block against a constant selector, see below); the loader waves only apply them in the epilogue.  Rounds 4-5 had
+    // block against a constant selector, see MainLoop); the loader waves only apply them in the epilogue.  Rounds 4-5 had
     // these waves add the landed stages up between their DMA issues - 24 KB more LDS reads per k-step on a loop that is
     // bound by the LDS: the tiles that did it ran ~20 % slower and gated their round (profiles/r06_d4_ride_ab.txt).
-    for (int r = next_round(0); r < g.rounds; r = next_round(r + 1)) {
+    for (int r = wsb_next_round(g, 0, nwg, wg); r < g.rounds; r = wsb_next_round(g, r + 1, nwg, wg)) {
       const WsbItem it = g.items[(size_t)r * nwg + wg];
       const bool want_cs = it.n0 == 0 && g.p[it.prob].colsum != nullptr;         // uniform
       for (int t = 0; t < it.nk; ++t) {
-        const bool more = issue();
+        const bool more = ld.issue();
         if (more) wait_vm<G::PW>(); else wait_vm<0>();
 #ifndef HERO_WSB_NOBAR
         __builtin_amdgcn_s_barrier();                                 // B(u)
@@ -749,147 +451,42 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 
   // -------------------------------------------------------------------- compute waves
+  // swapped operands (acc = dW^T fragments) for epilogue_acc; the bias-gradient ride only on the waves with wn == 0 of the
+  // tiles with n0 == 0 - the loop is instantiated with and without it
   const int wm = wave >> 1, wn = wave & 1;
-  const int arow0 = wm * TM * 32, brow0 = wn * TN * 32;
-  unsigned ao[TM], bo[TN];
-  {
-    const int p = lane & 15, gq = (lane >> 4) & 1, kg = lane >> 5;
-    const int krow = kg * 8 + (p >> 2);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int col = arow0 + i * 32 + gq * 16 + 4 * (p & 3);
-      ao[i] = krow * (G::BM * 2) + ((((col >> 3) ^ swz_o<G::BM * 2>(krow)) << 4) | ((col & 7) * 2));
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int col = brow0 + j * 32 + gq * 16 + 4 * (p & 3);
-      bo[j] = G::A_BYTES + krow * (G::BN * 2) + ((((col >> 3) ^ swz_o<G::BN * 2>(krow)) << 4) | ((col & 7) * 2));
-    }
-  }
-  typedef __attribute__((address_space(3))) bf16x4_t* lp_t;
-  bf16x8_t a0[TM], b0[TN], a1[TM], b1[TN];
-  auto ldf = [&](bf16x8_t (&a)[TM], bf16x8_t (&b)[TN], const char* st, int ks) {       // order a[0], b[..], a[1..]: see gemm_ws_kernel
-#ifdef HERO_WSB_NOLDF
-    return;
-#endif
-    auto ra = [&](int i) {
-      const char* q = st + ao[i] + ks * 16 * (G::BM * 2);
-      const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q));
-      const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q + 4 * (G::BM * 2)));
-      a[i] = bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    };
-    ra(0);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const char* q = st + bo[j] + ks * 16 * (G::BN * 2);
-      const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q));
-      const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q + 4 * (G::BN * 2)));
-      b[j] = bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    }
-#pragma unroll
-    for (int i = 1; i < TM; ++i) ra(i);
-  };
-  f32x16_t acc[TM][TN];
-  // Bias gradient = column sums of the dY panel (the B operand a[i]: lane <-> dW row): one more MFMA per row block against
-  // a constant SELECTOR as the A operand - sel_i[mm][k] = 1 for the eight output rows mm = 8 i .. 8 i + 7, else 0 - so that
-  // rows 8 i .. 8 i + 7 of ONE extra accumulator collect block i's sums: accumulator register 4 i of lane l < 32 = the sum
-  // of column arow0 + 32 i + l of the tile.  Only the waves with wn == 0 of the tiles with n0 == 0: 3 MFMAs on top of 9 per
-  // 16-k slice on a loop whose matrix pipe is about half idle, no LDS traffic, 16 more registers.
-  f32x16_t accb;
-  unsigned selw[TM];
-#pragma unroll
-  for (int i = 0; i < TM; ++i) selw[i] = ((lane & 31) >> 3) == i ? 0x3f803f80u : 0u;       // two bf16 ones
-  auto mma = [&](const bf16x8_t (&a)[TM], const bf16x8_t (&b)[TN], auto cs) {
-#ifdef HERO_WSB_NOMFMA
-    asm volatile("" ::"v"(a[0]), "v"(b[0]), "v"(a[TM - 1]), "v"(b[TN - 1]));
-    return;
-#endif
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j], a[i], acc[i][j], 0, 0, 0);   // dW^T: lane <-> output row
-      if constexpr (decltype(cs)::value) {
-        const u32x4_t w4 = {selw[i], selw[i], selw[i], selw[i]};
-        accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, w4), a[i], accb, 0, 0, 0);
-      }
-    }
-  };
-  // the k-loop of one item (two instantiations: a branch inside the loop would split its scheduling regions)
-  unsigned curo = 0, last = 0;
-  auto k_loop = [&](int nk, auto cs) {
-    constexpr int NM = TM * TN + (decltype(cs)::value ? TM : 0);
-    for (int t = 0; t < nk; ++t) {
-      const char* cur = smem + curo;
-      last = curo;
-      curo += G::STAGE;
-      if (curo == NS * G::STAGE) curo = 0;
-      const char* nxt = smem + curo;
-      // One scheduling region per 16-k slice: the 12 transposing fragment reads of the NEXT slice are spread between
-      // the 9 MFMAs of the current one (MFMA, 2 reads, MFMA, 2 reads, ...).  Issued as a block in front of the MFMAs
-      // (round 2) the reads cost ~140 cycles of MFMA-idle issue time per slice: 0.89 us per 64-k step with the DMA
-      // switched off against 0.58 us of MFMA issue (tools/lab/wsb_sweep.py, noloads).
-      ldf(a1, b1, cur, 1);
-      mma(a0, b0, cs);
-      WS_INTERLEAVE(NM, 2 * (TM + TN));
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a0, b0, cur, 2);
-      mma(a1, b1, cs);
-      WS_INTERLEAVE(NM, 2 * (TM + TN));
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a1, b1, cur, 3);
-      mma(a0, b0, cs);
-      WS_INTERLEAVE(NM, 2 * (TM + TN));
-      __builtin_amdgcn_sched_barrier(0);
-      wait_lds();
-#ifndef HERO_WSB_NOBAR
-      __builtin_amdgcn_s_barrier();                                   // B(u)
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a0, b0, nxt, 0);            // unconditional (a branch around it doubles the MFMA code and spills): after the
-      mma(a1, b1, cs);                // item's last step this reads the landed first stage of the next item and is
-      WS_INTERLEAVE(NM, 2 * (TM + TN));        // simply read again behind the epilogue
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
+  MainLoop<G, true, true, WSB_LAB> ml(smem, wm, wn, lane);
   __builtin_amdgcn_s_setprio(2);
   __builtin_amdgcn_s_barrier();                                       // B(-1)
-  int r = next_round(0);
-  if (r < g.rounds) ldf(a0, b0, smem, 0);
+  int r = wsb_next_round(g, 0, nwg, wg);
+  if (r < g.rounds) ml.read_first();
   while (r < g.rounds) {
     const WsbItem it = g.items[(size_t)r * nwg + wg];
-    const int rn = next_round(r + 1);
+    const int rn = wsb_next_round(g, r + 1, nwg, wg);
     const bool cs_on = wn == 0 && it.n0 == 0 && g.p[it.prob].colsum != nullptr;        // uniform
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    last = curo;
     if (cs_on) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) accb[e] = 0.f;
-      k_loop(it.nk, std::true_type{});
+      ml.zero<true>();
+      ml.run<true>(it.nk);
       // park the sums for the epilogue (loader waves 0-2 apply them behind the first pass barrier)
       float* sp = reinterpret_cast<float*>(smem + SPARE_OFF);
       if (lane < 32) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) sp[arow0 + 32 * i + lane] = accb[4 * i];
+        for (int i = 0; i < TM; ++i) sp[wm * TM * 32 + 32 * i + lane] = ml.accb[4 * i];
       }
     } else {
-      k_loop(it.nk, std::false_type{});
+      ml.zero<false>();
+      ml.run<false>(it.nk);
     }
     __builtin_amdgcn_s_setprio(0);
 #ifndef HERO_WSB_NOEPI
-    epilogue_acc<G, true>(g.p[it.prob], it, g.flags, smem, last, acc, wave, lane);
+    epilogue_acc<G, true>(g.p[it.prob], it, g.flags, smem, ml.last, ml.acc, wave, lane);
 #else
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(acc[i][j]));
+      for (int j = 0; j < G::TN; ++j) asm volatile("" ::"v"(ml.acc[i][j]));
 #endif
     __builtin_amdgcn_s_setprio(2);
-    if (rn < g.rounds) ldf(a0, b0, smem + curo, 0);
+    if (rn < g.rounds) ml.read_first();
     r = rn;
   }
 }
@@ -910,30 +507,6 @@ HERO_WS_INST(2, 3)
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-__global__ void ws_scale_f32_kernel(float* c, int M, int N, int ldc, float beta) {
-  const size_t n4 = (size_t)N >> 2;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)M * n4; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t r = i / n4, c4 = (i - r * n4) * 4;
-    float4* p = reinterpret_cast<float4*>(c + r * ldc + c4);
-    if (beta == 0.f) {
-      *p = make_float4(0.f, 0.f, 0.f, 0.f);
-    } else {
-      float4 v = *p;
-      v.x *= beta; v.y *= beta; v.z *= beta; v.w *= beta;
-      *p = v;
-    }
-  }
-}
-
-static int num_cus() {
-  static int n = [] {
-    int dev = 0, v = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    return v > 0 ? v : 256;
-  }();
-  return n;
-}
-
 template <int TM, int TN, bool TR, int EK>
 static int launch(WsArgs g, int slot, hipStream_t s) {
   typedef Geo<TM, TN> G;
@@ -964,6 +537,15 @@ static int launch_kk(const WsArgs& g, hipStream_t s) {
 }
 
 }  // namespace ws
+
+int num_cus() {
+  static int n = [] {
+    int dev = 0, v = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
+    return v > 0 ? v : 256;
+  }();
+  return n;
+}
 
 // Problems this family takes: bf16, K,K operands with one of the six hot-path epilogues, or the O,O
 // wgrad accumulate; large enough to fill the chip with 192 x 192 (or, under one round, 128 x 192) tiles.
@@ -1020,7 +602,6 @@ int gemm_ws_run(const void* A, const void* B, void* C, int M, int N, int K, int 
     // profiles/r04_vs_library.txt); 18.2 us with this geometry, 6.7 vs 8.0 at K = 768 (tools/lab/smallm_ws.py).
     if (force_cfg == 13 || force_cfg == 14 || (force_cfg == -1 && ntile * 2 < cus && K >= 512)) {
       typedef Geo<1, 2> G12;
-      typedef Geo<1, 3> G13;
       const int rows64 = (M + 63) / 64;
       const int t12 = rows64 * ((N + G12::BN - 1) / G12::BN), t13 = rows64 * g.tiles_n;
       // 64 x 192 (four stages) where 64 x 128 tiles would spill into a second round: the ragged batch's ~3100 padded frame rows
@@ -1061,8 +642,7 @@ int gemm_ws_run(const void* A, const void* B, void* C, int M, int N, int K, int 
   g.nwork = ntile * split;
   g.group = 8;
   if (epi.beta != 1.f) {
-    hipLaunchKernelGGL(ws_scale_f32_kernel, dim3(1024), dim3(256), 0, s, static_cast<float*>(C), M, N, ldc, epi.beta);
-    const int rc = check_launch("hero_gemm(ws scale)");
+    const int rc = gemm_scale_f32(static_cast<float*>(C), M, N, ldc, epi.beta, s);
     if (rc) return rc;
   }
   return launch<3, 3, true, 0>(g, 9, s);

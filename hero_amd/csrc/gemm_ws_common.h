@@ -1,6 +1,8 @@
-// Shared pieces of the wave-specialised persistent GEMM family (gemm_ws.hip: in-line epilogue, wgrad flavours;
-// gemm_wsd.hip: the K,K kernel whose epilogue is drained by the loader waves during the next tile's main loop).
-// Geometry, work-item order, LDS images and the loader-wave DMA stream are described at the top of gemm_ws.hip.
+// Shared pieces of the wave-specialised persistent GEMM family (gemm_ws.hip): geometry and work-item order, the loader
+// waves' DMA stream, the compute waves' fragment reader and main loop, the staging of an epilogue pass and the K,K
+// epilogue.  The kernels of gemm_ws.hip differ in where the stream goes next (a panel source) and in what happens to a
+// finished tile.  Roles, ring and LDS images are described at the top of gemm_ws.hip.
+// (tools/lab/gemm_wsd.hip, a lab kernel outside the library, is built on this header too.)
 #pragma once
 #include <vector>
 
@@ -124,97 +126,356 @@ template <int RB> __device__ __forceinline__ int swz_o(int k) { return RB % 256 
 // ------------------------------------------------------------------------------------------------
 // loader waves
 // ------------------------------------------------------------------------------------------------
-template <typename G, bool TR>
-struct Loader {
+// One stretch of the DMA stream: nk 64-k stages of the panels A (BM rows / columns at m0) and B (BN at n0) from
+// reduction index k0 on.  K,K operands are [M, lda] / [N, ldb] (rows past M / N are clamped to the last one), O,O operands
+// [K, lda] / [K, ldb] (stages past K are out of range for the descriptor and deliver zeros).
+struct Panel {
+  const bf16_t* A;
+  const bf16_t* B;
+  int lda, ldb, M, N, K;
+  int m0, n0, k0, nk;
+};
+
+// A panel source tells the loader where the stream goes next: done() - the stream has ended; panel() - the stretch that
+// starts now; advance() - that stretch has been issued; DMA - false drops the loads (lab ablation, timing only).
+// This one walks the work items of a WsArgs launch (item_coord order), every nwg-th from `item` on.
+template <typename G>
+struct ItemSource {
+  static constexpr bool DMA = true;
   const WsArgs& g;
+  int item, nwg;
+  __device__ __forceinline__ bool done() const { return item >= g.nwork; }
+  __device__ __forceinline__ Panel panel() const {
+    const Item ic = item_coord<G>(g, item);
+    return Panel{static_cast<const bf16_t*>(g.A), static_cast<const bf16_t*>(g.B), g.lda, g.ldb, g.M, g.N, g.K, ic.m0, ic.n0, ic.kbeg, ic.nk};
+  }
+  __device__ __forceinline__ void advance() { item += nwg; }
+};
+
+template <typename G, bool TR, typename Src>
+struct Loader {
+  Src src;
   char* smem;
-  int w, lane, nwg;
-  int item, ik;           // item / stage being issued next
-  Item ic;
-  unsigned fill;
+  int w, lane;
+  int ik, nk;             // stage being issued next / stages of the current stretch
+  unsigned fill;          // ring cursor
   unsigned goa[G::PA], gob[G::PB];
   const char* pa;         // stage base of the A / B panels (uniform)
   const char* pb;
-  unsigned ra_left, rb_left;   // bytes from the stage base to the end of the operand (O,O bounds)
+  // O,O bounds: bytes from the stage base to the end of the operand (64-bit: 1.4 M rows x 3072 columns at config 5; the
+  // descriptor base moves with the k-step, so offsets stay small and only the range is clamped to 32 bits)
+  unsigned long long ra_left, rb_left;
+  unsigned sa, sb;        // bytes the bases move per stage
 
-  __device__ __forceinline__ Loader(const WsArgs& g_, char* smem_, int wg, int nwg_, int w_, int lane_)
-      : g(g_), smem(smem_), w(w_), lane(lane_), nwg(nwg_), item(wg), ik(0), fill(0) {
-    if (item < g.nwork) setup();
+  __device__ __forceinline__ Loader(const Src& src_, char* smem_, int w_, int lane_)
+      : src(src_), smem(smem_), w(w_), lane(lane_), ik(0), nk(0), fill(0), pa(nullptr), pb(nullptr), ra_left(0), rb_left(0), sa(0), sb(0) {
+    if (!src.done()) setup();
   }
   __device__ __forceinline__ void setup() {
-    ic = item_coord<G>(g, item);
-    const bf16_t* A = static_cast<const bf16_t*>(g.A);
-    const bf16_t* B = static_cast<const bf16_t*>(g.B);
+    const Panel p = src.panel();
+    nk = p.nk;
     if (!TR) {
 #pragma unroll
       for (int i = 0; i < G::PA; ++i) {
         const int r = (w * G::PA + i) * 8 + (lane >> 3);
-        goa[i] = (unsigned)(min(ic.m0 + r, g.M - 1) - ic.m0) * (unsigned)g.lda * 2u + (((lane & 7) ^ swz_k(r)) << 4);
+        goa[i] = (unsigned)(min(p.m0 + r, p.M - 1) - p.m0) * (unsigned)p.lda * 2u + (((lane & 7) ^ swz_k(r)) << 4);
       }
 #pragma unroll
       for (int i = 0; i < G::PB; ++i) {
         const int r = (w * G::PB + i) * 8 + (lane >> 3);
-        gob[i] = (unsigned)(min(ic.n0 + r, g.N - 1) - ic.n0) * (unsigned)g.ldb * 2u + (((lane & 7) ^ swz_k(r)) << 4);
+        gob[i] = (unsigned)(min(p.n0 + r, p.N - 1) - p.n0) * (unsigned)p.ldb * 2u + (((lane & 7) ^ swz_k(r)) << 4);
       }
-      pa = reinterpret_cast<const char*>(A + (size_t)ic.m0 * g.lda + ic.kbeg);
-      pb = reinterpret_cast<const char*>(B + (size_t)ic.n0 * g.ldb + ic.kbeg);
-      ra_left = rb_left = 0x7fffffffu;
+      pa = reinterpret_cast<const char*>(p.A + (size_t)p.m0 * p.lda + p.k0);
+      pb = reinterpret_cast<const char*>(p.B + (size_t)p.n0 * p.ldb + p.k0);
+      ra_left = rb_left = 0ull;                          // unused
+      sa = sb = 128u;
     } else {
       constexpr int CA = G::BM / 8, CB = G::BN / 8;      // 16-B chunks per tile row
 #pragma unroll
       for (int i = 0; i < G::PA; ++i) {
         const int id = (w * G::PA + i) * 64 + lane, row = id / CA, c = (id % CA) ^ swz_o<G::BM * 2>(row);
-        goa[i] = (unsigned)row * (unsigned)g.lda * 2u + (c << 4);
+        goa[i] = (unsigned)row * (unsigned)p.lda * 2u + (c << 4);
       }
 #pragma unroll
       for (int i = 0; i < G::PB; ++i) {
         const int id = (w * G::PB + i) * 64 + lane, row = id / CB, c = (id % CB) ^ swz_o<G::BN * 2>(row);
-        gob[i] = (unsigned)row * (unsigned)g.ldb * 2u + (c << 4);
+        gob[i] = (unsigned)row * (unsigned)p.ldb * 2u + (c << 4);
       }
       // A is [K, lda] with the tile's M columns at m0; B is [K, ldb] with the N columns at n0
-      pa = reinterpret_cast<const char*>(A + (size_t)ic.kbeg * g.lda + ic.m0);
-      pb = reinterpret_cast<const char*>(B + (size_t)ic.kbeg * g.ldb + ic.n0);
-      ra_left = (unsigned)(((size_t)(g.K - ic.kbeg) * g.lda - ic.m0) * 2);
-      rb_left = (unsigned)(((size_t)(g.K - ic.kbeg) * g.ldb - ic.n0) * 2);
+      pa = reinterpret_cast<const char*>(p.A + (size_t)p.k0 * p.lda + p.m0);
+      pb = reinterpret_cast<const char*>(p.B + (size_t)p.k0 * p.ldb + p.n0);
+      ra_left = ((unsigned long long)(p.K - p.k0) * p.lda - p.m0) * 2;
+      rb_left = ((unsigned long long)(p.K - p.k0) * p.ldb - p.n0) * 2;
+      sa = 64u * (unsigned)p.lda * 2u;
+      sb = 64u * (unsigned)p.ldb * 2u;
     }
   }
-  // gemm_wsd_kernel: issue PW pieces in EVERY step, so that the wave's vmcnt arithmetic is the same on every path.  Behind
-  // the end of the item stream the descriptors have a zero range: the loads fetch nothing, write zeros into a ring slot
-  // nobody reads again, and count like the real ones.
-  __device__ __forceinline__ void issue_always() {
-    if (item >= g.nwork) { ra_left = rb_left = 0u; ic.nk = 0x7fffffff; }
-    issue_body();
+  // Descriptor range of a stage: K,K rows are clamped by setup(), nothing to bound.  O,O: clamped at 0xffffffff, so that every
+  // count below 4 GB - all that gemm_ws_kernel / gemm_wsg_kernel are launched with - is the range itself, as with the 32-bit
+  // counters these kernels had; above it (batched kernel, config 5; it used to clamp at 0xfffffff0) any value past the
+  // < 2^31 bytes a stage touches does.
+  __device__ __forceinline__ static unsigned range(unsigned long long left) {
+    return !TR ? 0x7fffffffu : (unsigned)(left < 0xffffffffull ? left : 0xffffffffull);
   }
-  // issue the next stage of the item stream (false: the stream has ended)
+  // issue the next stage of the stream (false: the stream has ended)
   __device__ __forceinline__ bool issue() {
-    if (item >= g.nwork) return false;
-    issue_body();
+    if (src.done()) return false;
+    stage();
     return true;
   }
-  __device__ __forceinline__ void issue_body() {
+  __device__ __forceinline__ void stage() {
     char* buf = smem + fill;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pa), 0, ra_left, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pb), 0, rb_left, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pa), 0, range(ra_left), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pb), 0, range(rb_left), 0x00020000);
+    if constexpr (Src::DMA) {
 #pragma unroll
-    for (int i = 0; i < G::PA; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, HERO_LDS_PTR(buf + (w * G::PA + i) * 1024), 16, goa[i], 0, 0, HERO_WS_LOAD_AUX_A);
+      for (int i = 0; i < G::PA; ++i)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, HERO_LDS_PTR(buf + (w * G::PA + i) * 1024), 16, goa[i], 0, 0, HERO_WS_LOAD_AUX_A);
 #pragma unroll
-    for (int i = 0; i < G::PB; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, HERO_LDS_PTR(buf + G::A_BYTES + (w * G::PB + i) * 1024), 16, gob[i], 0, 0, HERO_WS_LOAD_AUX_B);
+      for (int i = 0; i < G::PB; ++i)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, HERO_LDS_PTR(buf + G::A_BYTES + (w * G::PB + i) * 1024), 16, gob[i], 0, 0, HERO_WS_LOAD_AUX_B);
+    }
     fill += G::STAGE;
     if (fill == G::NSG * G::STAGE) fill = 0;
-    if (++ik == ic.nk) {
-      item += nwg;
+    if (++ik == nk) {
       ik = 0;
-      if (item < g.nwork) setup();
-    } else if (!TR) {
-      pa += 128;
-      pb += 128;
+      src.advance();
+      if (!src.done()) setup();
     } else {
-      const unsigned sa = 64u * (unsigned)g.lda * 2u, sb = 64u * (unsigned)g.ldb * 2u;
       pa += sa; pb += sb;
-      ra_left = ra_left > sa ? ra_left - sa : 0u;
-      rb_left = rb_left > sb ? rb_left - sb : 0u;
+      if (TR) {
+        ra_left = ra_left > sa ? ra_left - sa : 0ull;
+        rb_left = rb_left > sb ? rb_left - sb : 0ull;
+      }
+    }
+  }
+};
+
+// ------------------------------------------------------------------------------------------------
+// compute waves
+// ------------------------------------------------------------------------------------------------
+// Fragment reader of compute wave (wm, wn): per-lane LDS offsets inside a stage (slice 0) and the reads of one 16-k slice.
+// TR = false: K,K image, one ds_read_b128 per fragment; TR = true: O,O image, two transposing 64-bit reads.
+// Read order a[0], b[0..], a[1..]: the MFMAs of the NEXT slice run (i outer, j inner), the reads are spread over the
+// MFMAs of the current slice in this order, so every fragment is requested >= 7 MFMAs (224 cycles) before its first
+// use (a[0..], b[0..] order: 5 MFMAs for b[0] - less than the LDS latency beside the DMA writes).
+template <typename G, bool TR>
+struct Frags {
+  static constexpr int TM = G::TM, TN = G::TN;
+  static constexpr int NRD = TR ? 2 * (TM + TN) : TM + TN;            // LDS reads per slice
+  unsigned ao[TM], bo[TN];
+  __device__ __forceinline__ Frags(int wm, int wn, int lane) {
+    const int arow0 = wm * TM * 32, brow0 = wn * TN * 32;
+    if (!TR) {
+      const int r = lane & 31, kg = lane >> 5;
+#pragma unroll
+      for (int i = 0; i < TM; ++i) { const int ra = arow0 + i * 32 + r; ao[i] = ra * 128 + ((kg ^ swz_k(ra)) << 4); }
+#pragma unroll
+      for (int j = 0; j < TN; ++j) { const int rb = brow0 + j * 32 + r; bo[j] = G::A_BYTES + rb * 128 + ((kg ^ swz_k(rb)) << 4); }
+    } else {
+      const int p = lane & 15, gq = (lane >> 4) & 1, kg = lane >> 5;
+      const int krow = kg * 8 + (p >> 2);
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int col = arow0 + i * 32 + gq * 16 + 4 * (p & 3);
+        ao[i] = krow * (G::BM * 2) + ((((col >> 3) ^ swz_o<G::BM * 2>(krow)) << 4) | ((col & 7) * 2));
+      }
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const int col = brow0 + j * 32 + gq * 16 + 4 * (p & 3);
+        bo[j] = G::A_BYTES + krow * (G::BN * 2) + ((((col >> 3) ^ swz_o<G::BN * 2>(krow)) << 4) | ((col & 7) * 2));
+      }
+    }
+  }
+  template <int RB>                                                   // RB: bytes of a reduction row of the O,O image
+  __device__ __forceinline__ static bf16x8_t read(const char* st, unsigned off, int ks) {
+    if (!TR) {
+      return *reinterpret_cast<const bf16x8_t*>(st + (off ^ (ks << 5)));
+    } else {
+      typedef __attribute__((address_space(3))) bf16x4_t* lp_t;
+      const char* q = st + off + ks * 16 * RB;
+      const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q));
+      const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(q + 4 * RB));
+      return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    }
+  }
+  __device__ __forceinline__ void load(bf16x8_t (&a)[TM], bf16x8_t (&b)[TN], const char* st, int ks) const {
+    a[0] = read<G::BM * 2>(st, ao[0], ks);
+#pragma unroll
+    for (int j = 0; j < TN; ++j) b[j] = read<G::BN * 2>(st, bo[j], ks);
+#pragma unroll
+    for (int i = 1; i < TM; ++i) a[i] = read<G::BM * 2>(st, ao[i], ks);
+  }
+};
+
+// lab ablations of the main loop (timing only, results are garbage): no fragment reads / no MFMAs / no step barrier
+enum { LAB_NOLDF = 1, LAB_NOMFMA = 2, LAB_NOBAR = 4 };
+
+// Main loop of a compute wave: two fragment register sets, the accumulators and the ring cursor.
+// SWAP: the MFMA operands are swapped (D^T = B A^T: lane <-> output row, a lane holds 4 consecutive columns of a row), which
+// is what stage_pass wants; unswapped, a half-wave holds 32 consecutive columns (atomic_tile).
+template <typename G, bool TR, bool SWAP, int LAB = 0>
+struct MainLoop {
+  static constexpr int TM = G::TM, TN = G::TN;
+  Frags<G, TR> fr;
+  const char* smem;
+  bf16x8_t a0[TM], b0[TN], a1[TM], b1[TN];
+  f32x16_t acc[TM][TN];
+  // The ride (batched wgrad, bias gradient = column sums of the dY panel, the operand a[i]: lane <-> dW row): one more MFMA
+  // per row block against a constant SELECTOR - sel_i[mm][k] = 1 for the eight output rows mm = 8 i .. 8 i + 7, else 0 - so
+  // that rows 8 i .. 8 i + 7 of ONE extra accumulator collect block i's sums: accumulator register 4 i of lane l < 32 = the
+  // sum of column arow0 + 32 i + l of the tile.  3 MFMAs on top of 9 per 16-k slice on a loop whose matrix pipe is about half
+  // idle, no LDS traffic, 16 more registers.
+  f32x16_t accb;
+  unsigned selw[TM];
+  unsigned curo, last;      // ring cursor: the stage read next / the stage read last (the epilogue's staging slot)
+
+  __device__ __forceinline__ MainLoop(const char* smem_, int wm, int wn, int lane) : fr(wm, wn, lane), smem(smem_), curo(0), last(0) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i) selw[i] = ((lane & 31) >> 3) == i ? 0x3f803f80u : 0u;       // two bf16 ones
+  }
+  __device__ __forceinline__ void ldf(bf16x8_t (&a)[TM], bf16x8_t (&b)[TN], const char* st, int ks) {
+    if constexpr (!(LAB & LAB_NOLDF)) fr.load(a, b, st, ks);
+  }
+  // Slice 0 of the stage at the cursor (start of the stream, and again behind an epilogue that used the ring).  The empty asm
+  // pins the reads to the call site: without it the compiler merges the two sites of a kernel into the top of the item loop,
+  // behind the item's coordinate arithmetic, and their latency is no longer covered by it (64 x 128 tiles, two items per
+  // workgroup: +1 - 2 %).
+  __device__ __forceinline__ void read_first() {
+    ldf(a0, b0, smem + curo, 0);
+    asm volatile("");
+  }
+  template <bool RIDE>
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    if constexpr (RIDE) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) accb[e] = 0.f;
+    }
+    last = curo;
+  }
+  template <bool RIDE>
+  __device__ __forceinline__ void mma(const bf16x8_t (&a)[TM], const bf16x8_t (&b)[TN]) {
+    if constexpr (LAB & LAB_NOMFMA) {
+      asm volatile("" ::"v"(a[0]), "v"(b[0]), "v"(a[TM - 1]), "v"(b[TN - 1]));
+    } else {
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          if (SWAP) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
+          else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+        if constexpr (RIDE) {
+          const u32x4_t w4 = {selw[i], selw[i], selw[i], selw[i]};
+          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, w4), a[i], accb, 0, 0, 0);
+        }
+      }
+    }
+  }
+  // nk 64-k steps.  One scheduling region per 16-k slice: the fragment reads of the NEXT slice are spread between the MFMAs
+  // of the current one (MFMA, 1-2 reads, MFMA, ...).  Issued as a block in front of the MFMAs (round 2) the reads cost ~140
+  // cycles of MFMA-idle issue time per slice: 0.89 us per 64-k step with the DMA switched off against 0.58 us of MFMA issue
+  // (tools/lab/wsb_sweep.py, noloads).  RIDE is a template argument: a branch inside the loop would split its regions.
+  template <bool RIDE>
+  __device__ __forceinline__ void run(int nk) {
+    constexpr int NM = TM * TN + (RIDE ? TM : 0), NRD = Frags<G, TR>::NRD;
+    for (int t = 0; t < nk; ++t) {
+      const char* cur = smem + curo;
+      last = curo;
+      curo += G::STAGE;
+      if (curo == G::NSG * G::STAGE) curo = 0;
+      const char* nxt = smem + curo;
+      ldf(a1, b1, cur, 1);
+      mma<RIDE>(a0, b0);
+      WS_INTERLEAVE(NM, NRD);
+      __builtin_amdgcn_sched_barrier(0);
+      ldf(a0, b0, cur, 2);
+      mma<RIDE>(a1, b1);
+      WS_INTERLEAVE(NM, NRD);
+      __builtin_amdgcn_sched_barrier(0);
+      ldf(a1, b1, cur, 3);
+      mma<RIDE>(a0, b0);
+      WS_INTERLEAVE(NM, NRD);
+      __builtin_amdgcn_sched_barrier(0);
+      wait_lds();
+      if constexpr (!(LAB & LAB_NOBAR)) __builtin_amdgcn_s_barrier();   // B(u): done reading `cur`, stage u+1 landed
+      __builtin_amdgcn_sched_barrier(0);
+      // unconditional (a branch around it doubles the MFMA code and spills): behind the last step of a stretch this reads the
+      // landed first stage of the next one - read again behind an epilogue that used the ring - or stale LDS, never used
+      ldf(a0, b0, nxt, 0);
+      mma<RIDE>(a1, b1);
+      WS_INTERLEAVE(NM, NRD);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+};
+
+// fp32 atomics straight from the UNSWAPPED accumulator layout of a wave whose fragments start at (m0, n0): 32 consecutive
+// columns per half-wave, two rows per instruction
+template <int TM, int TN>
+__device__ __forceinline__ void atomic_tile(float* C, int ldc, int M, int N, int m0, int n0, const f32x16_t (*acc)[TN], int lane) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int gn = n0 + j * 32 + (lane & 31);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int gm = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (gm < M && gn < N) atomicAdd(C + (size_t)gm * ldc + gn, acc[i][j][r]);
+      }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// epilogues through LDS (swapped accumulators): the thread's place in a pass and the staging of a pass
+// ------------------------------------------------------------------------------------------------
+// A pass stages RPP rows of the tile as fp32 in a ring slot (16-byte chunks XOR-swizzled by row); all 8 waves then work on
+// full rows, thread (r0 + it * RPI, c8) on 8 columns.
+// Everything derived from the thread index is recomputed per tile from an opaque copy: hoisted out of the item loop these
+// values stay live across the main loop, where 144 accumulators + 48 fragment registers leave no room, and get spilled to
+// scratch (a reload = one memory round trip at the start of every epilogue).
+template <typename G>
+struct PassLane {
+  static constexpr int TM = G::TM, TN = G::TN, RPP = G::RPP;
+  // With three passes over a 192-row tile the two 32-row blocks of a pass are taken from the two wave rows (block p of
+  // each), so that all four compute waves stage 12 fragments per pass instead of two waves staging 24 (the staging of a
+  // pass was 2100 cycles of a 5300-cycle pass, tools/lab/trace_ws.py).
+  static constexpr bool SPLIT = (RPP == 64 && G::PASSES == TM);
+  int tid, lane, wave, c8, r0;
+  __device__ __forceinline__ PassLane() {
+    tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    lane = tid & 63;
+    wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    c8 = tid % G::C8;
+    r0 = tid / G::C8;
+  }
+  // row of the tile that row `row` of pass p holds
+  __device__ __forceinline__ static int tile_row(int p, int row) { return SPLIT ? (row >> 5) * (TM * 32) + p * 32 + (row & 31) : p * RPP + row; }
+  // compute waves: this wave's share of pass p, accumulators -> the pass image at st (ds_write_b128)
+  __device__ __forceinline__ void stage_pass(char* st, int p, const f32x16_t (*acc)[TN]) const {
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
+#pragma unroll
+    for (int b = 0; b < RPP / 32; ++b) {
+      const int blk = SPLIT ? b * TM + p : p * (RPP / 32) + b;   // 32-row block of the tile
+      if (wm == blk / TM) {
+        const int i = blk % TM;                     // compile-time after unrolling
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int chunk = (wn * TN * 32 + j * 32 + 8 * q + 4 * half) >> 2;
+            const f32x4_t v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
+            *reinterpret_cast<f32x4_t*>(st + (32 * b + l31) * G::ROWB + ((chunk ^ (l31 & 7)) << 4)) = v;
+          }
+      }
     }
   }
 };
@@ -225,17 +486,13 @@ struct Loader {
 template <typename G, int EK, bool COMPUTE>
 __device__ __forceinline__ void epilogue_rows(const WsArgs& g, const Item& ic, char* smem, unsigned slot, f32x16_t (*acc)[G::TN], int wave,
                                               int lane, int trace_item = -1) {
-  constexpr int TM = G::TM, TN = G::TN, BN = G::BN, RPP = G::RPP, C8 = G::C8, RPI = G::RPI, ITERS = G::ITERS;
+  constexpr int BN = G::BN, RPP = G::RPP, RPI = G::RPI, ITERS = G::ITERS;
   const HeroGemmEpilogue& e = g.epi;
   char* st = smem + slot;
-  // Everything the epilogue derives from the thread index is recomputed per tile from an opaque copy: hoisted out of the
-  // item loop these values stay live across the main loop, where 144 accumulators + 48 fragment registers leave no room,
-  // and get spilled to scratch (a reload = one memory round trip at the start of every epilogue).
-  int tid = threadIdx.x;
-  asm volatile("" : "+v"(tid));
-  lane = tid & 63;
-  wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c8 = tid % C8, r0 = tid / C8;
+  const PassLane<G> pl;                               // opaque copy of the thread index: see PassLane
+  const int tid = pl.tid, c8 = pl.c8, r0 = pl.r0;
+  lane = pl.lane;
+  wave = pl.wave;
   const bool active = r0 < RPI;
   const int gn = ic.n0 + c8 * 8;
   const bool col_ok = active && gn < g.N;
@@ -260,12 +517,7 @@ __device__ __forceinline__ void epilogue_rows(const WsArgs& g, const Item& ic, c
   const bool save_dg = (EK & EK_GELU) && e.act == HERO_ACT_GELU_DG, mul_aux = (EK & EK_GELU_BWD) && e.act == HERO_ACT_MUL_AUX;
   const bool relu = (EK & EK_GELU) && e.act == HERO_ACT_RELU;      // uniform: the activation-with-saved-value instantiations serve ReLU too
   float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
-  // A pass stages 64 rows.  With three passes over a 192-row tile the two 32-row blocks of a pass are taken from the
-  // two wave rows (block p of each), so that all four compute waves stage 12 fragments per pass instead of two waves
-  // staging 24 (the staging of a pass was 2100 cycles of a 5300-cycle pass, tools/lab/trace_ws.py).
-  constexpr bool SPLIT = (RPP == 64 && G::PASSES == TM);
-  auto tile_row = [](int p, int row) { return SPLIT ? (row >> 5) * (TM * 32) + p * 32 + (row & 31) : p * RPP + row; };
+  auto tile_row = [](int p, int row) { return PassLane<G>::tile_row(p, row); };
 
 #pragma unroll
   for (int p = 0; p < G::PASSES; ++p) {
@@ -284,23 +536,7 @@ __device__ __forceinline__ void epilogue_rows(const WsArgs& g, const Item& ic, c
       if (EK & EK_GELU_BWD) pre[it] = *reinterpret_cast<const uint4*>(X + torg + off[it]);
     }
     WS_T(trace_item, 2 + 4 * p, wave, lane);
-    if constexpr (COMPUTE) {
-#pragma unroll
-      for (int b = 0; b < RPP / 32; ++b) {
-        const int blk = SPLIT ? b * TM + p : p * (RPP / 32) + b;   // 32-row block of the tile
-        if (wm == blk / TM) {
-          const int i = blk % TM;                     // compile-time after unrolling
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int chunk = (wn * TN * 32 + j * 32 + 8 * q + 4 * half) >> 2;
-              const f32x4_t v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-              *reinterpret_cast<f32x4_t*>(st + (32 * b + l31) * G::ROWB + ((chunk ^ (l31 & 7)) << 4)) = v;
-            }
-        }
-      }
-    }
+    if constexpr (COMPUTE) pl.stage_pass(st, p, acc);
     wait_lds();
     WS_T(trace_item, 3 + 4 * p, wave, lane);
     __builtin_amdgcn_s_barrier();                    // E1: the pass is staged

@@ -259,10 +259,12 @@ def _ws_against_4wave(HF, Lb, M, N, K, ws_cfg, colsum=True):
 
 
 @pytest.mark.parametrize("rows,n_out,n_in", [(12000, 768, 768), (12040, 3072, 768), (4100, 768, 3072), (520, 200, 136),
-                                             (12000, 2304, 768)])
+                                             (12000, 2304, 768), (520, 3264, 3264)])
 def test_gemm_wave_specialised_wgrad(HF, Lb, rows, n_out, n_in):
     """dW += dY^T X on the wave-specialised O,O kernel: transpose reads, reduction split with fp32
-    atomics, reduction tails (rows % 64 != 0 -> out-of-range rows read as zeros), accumulate into C."""
+    atomics, reduction tails (rows % 64 != 0 -> out-of-range rows read as zeros), accumulate into C.
+    (520, 3264, 3264): 17 x 17 = 289 tiles, split 1, on 256 workgroups - 33 of them take a second item, so the
+    transposed loader hands over from one item to the next (every other shape has tiles x split <= 256)."""
     dtype = torch.bfloat16
     dy, x = rnd(rows, n_out, dtype=dtype, seed=1), rnd(rows, n_in, dtype=dtype, seed=2)
     ref = dy.float().t() @ x.float()

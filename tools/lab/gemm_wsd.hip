@@ -29,6 +29,22 @@
 namespace hero {
 namespace ws {
 
+// Issue PW pieces in EVERY step, so that the wave's vmcnt arithmetic is the same on every path.  Behind the end of the
+// item stream the descriptor has a zero range: the loads fetch nothing, write zeros into a ring slot nobody reads again,
+// and count like the real ones.
+template <typename G, typename L>
+__device__ __forceinline__ void issue_always(L& ld) {
+  if (!ld.src.done()) { ld.stage(); return; }
+  char* buf = ld.smem + ld.fill;
+  const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc(ld.smem, 0, 0, 0x00020000);
+#pragma unroll
+  for (int i = 0; i < G::PA; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(none, HERO_LDS_PTR(buf + (ld.w * G::PA + i) * 1024), 16, 0, 0, 0, 0);
+#pragma unroll
+  for (int i = 0; i < G::PB; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(none, HERO_LDS_PTR(buf + G::A_BYTES + (ld.w * G::PB + i) * 1024), 16, 0, 0, 0, 0);
+  ld.fill += G::STAGE;
+  if (ld.fill == G::NSG * G::STAGE) ld.fill = 0;
+}
+
 template <int TM, int TN, int EK>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_wsd_kernel(WsArgs g) {
   typedef Geo<TM, TN> G;
@@ -42,18 +58,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   constexpr int DSTEPS = NITEM / IPS;           // ring steps a drain takes: the launcher requires K / 64 >= DSTEPS
   constexpr int PW = G::PW;
   static_assert(RPP * C8 % 256 == 0 && NITEM % IPS == 0 && DSTEPS >= 1, "item mapping");
-  constexpr bool SPLIT = (RPP == 64 && PASSES == TM);
-  auto tile_row = [](int p, int row) { return SPLIT ? (row >> 5) * (TM * 32) + p * 32 + (row & 31) : p * RPP + row; };
+  auto tile_row = [](int p, int row) { return PassLane<G>::tile_row(p, row); };
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwg = gridDim.x;
-  int wg;
-  {
-    const int bid = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  const int wg = xcd_order(blockIdx.x, nwg);
 
   if (wave >= 4) {
     // ------------------------------------------------------------------ loader waves: DMA stream + drain
@@ -66,9 +77,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const bf16_t* R = (EK & EK_RES) ? static_cast<const bf16_t*>(e.residual) : nullptr;
     bf16_t* X = static_cast<bf16_t*>(e.aux);
     float* bsp = reinterpret_cast<float*>(smem + SPARE_OFF);          // the parked tile's bias columns
-    Loader<G, false> ld(g, smem, wg, nwg, w, lane);
-    ld.issue_always();
-    ld.issue_always();
+    Loader<G, false, ItemSource<G>> ld(ItemSource<G>{g, wg, nwg}, smem, w, lane);
+    issue_always<G>(ld);
+    issue_always<G>(ld);
     wait_vm<PW>();
     __builtin_amdgcn_s_barrier();                                     // B(-1): stage 0 landed
     unsigned slot = 0;
@@ -173,7 +184,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // issues the same VMEM operations, so the compiler's own waits agree with the explicit ones)
 #pragma unroll
         for (int c = 0; c < NITEM; c += IPS) {
-          ld.issue_always();                                            // stage u+2
+          issue_always<G>(ld);                                            // stage u+2
           if (c == 0) wait_vm<PW>(); else wait_vm<PW + NST>();          // stage u+1 and R(current items) have landed
           __builtin_amdgcn_s_barrier();                                 // B(u)
           if (t + 1 < nk) { slot += G::STAGE; if (slot == NS * G::STAGE) slot = 0; }
@@ -189,7 +200,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         WS_T(item_no, 2, wave, lane);
       }
       for (; t < nk; ++t) {
-        ld.issue_always();
+        issue_always<G>(ld);
         wait_vm<PW>();
         __builtin_amdgcn_s_barrier();                                   // B(u)
         if (t + 1 < nk) { slot += G::STAGE; if (slot == NS * G::STAGE) slot = 0; }
@@ -242,98 +253,26 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 
   // -------------------------------------------------------------------- compute waves
-  const int wm = wave >> 1, wn = wave & 1;
-  const int arow0 = wm * TM * 32, brow0 = wn * TN * 32;
-  unsigned ao[TM], bo[TN];                                            // per-lane LDS offsets inside a stage (slice 0)
-  {
-    const int r = lane & 31, kg = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) { const int ra = arow0 + i * 32 + r; ao[i] = ra * 128 + ((kg ^ swz_k(ra)) << 4); }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) { const int rb = brow0 + j * 32 + r; bo[j] = G::A_BYTES + rb * 128 + ((kg ^ swz_k(rb)) << 4); }
-  }
-  bf16x8_t a0[TM], b0[TN], a1[TM], b1[TN];
-  auto ldf = [&](bf16x8_t (&a)[TM], bf16x8_t (&b)[TN], const char* st, int ks) {       // order a[0], b[..], a[1..]: see gemm_ws_kernel
-    a[0] = *reinterpret_cast<const bf16x8_t*>(st + (ao[0] ^ (ks << 5)));
-#pragma unroll
-    for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const bf16x8_t*>(st + (bo[j] ^ (ks << 5)));
-#pragma unroll
-    for (int i = 1; i < TM; ++i) a[i] = *reinterpret_cast<const bf16x8_t*>(st + (ao[i] ^ (ks << 5)));
-  };
-  f32x16_t acc[TM][TN];
-  auto mma = [&](const bf16x8_t (&a)[TM], const bf16x8_t (&b)[TN]) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j], a[i], acc[i][j], 0, 0, 0);   // D^T: lane <-> output row
-  };
-
+  MainLoop<G, false, true> ml(smem, wave >> 1, wave & 1, lane);      // swapped operands: see gemm_ws_kernel
   __builtin_amdgcn_s_setprio(2);
   __builtin_amdgcn_s_barrier();                                       // B(-1)
-  unsigned curo = 0;
-  if (wg < g.nwork) ldf(a0, b0, smem, 0);
+  if (wg < g.nwork) ml.read_first();
   int item_no = 0;
   for (int cit = wg; cit < g.nwork; cit += nwg, ++item_no) {
     const Item ic = item_coord<G>(g, cit);
     WS_T(item_no, 0, wave, lane);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    ml.template zero<false>();
     const bool more_items = cit + nwg < g.nwork;
-    unsigned last = curo;
-    for (int t = 0; t < ic.nk; ++t) {
-      const char* cur = smem + curo;
-      last = curo;
-      curo += G::STAGE;
-      if (curo == NS * G::STAGE) curo = 0;
-      const char* nxt = smem + curo;
-      constexpr int NRD = TM + TN;
-      ldf(a1, b1, cur, 1);
-      mma(a0, b0);
-      WS_INTERLEAVE(TM * TN, NRD);
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a0, b0, cur, 2);
-      mma(a1, b1);
-      WS_INTERLEAVE(TM * TN, NRD);
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a1, b1, cur, 3);
-      mma(a0, b0);
-      WS_INTERLEAVE(TM * TN, NRD);
-      __builtin_amdgcn_sched_barrier(0);
-      wait_lds();
-      __builtin_amdgcn_s_barrier();                                   // B(u): done reading `cur`, stage u+1 landed
-      __builtin_amdgcn_sched_barrier(0);
-      ldf(a0, b0, nxt, 0);            // unconditional: behind an item's last step it reads the next item's landed first
-      mma(a1, b1);                    // stage (read again after the hand-off) or stale LDS, never used
-      WS_INTERLEAVE(TM * TN, NRD);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    ml.template run<false>(ic.nk);
     __builtin_amdgcn_s_setprio(0);
     WS_T(item_no, 1, wave, lane);
     // ------------------------------------------------------------------ hand-off: stage the accumulators, pass by pass
     {
-      char* st = smem + last;
-      const int l31 = lane & 31, half = lane >> 5;
+      char* st = smem + ml.last;
+      const PassLane<G> pl;
 #pragma unroll
       for (int p = 0; p < PASSES; ++p) {
-#pragma unroll
-        for (int b = 0; b < RPP / 32; ++b) {
-          const int blk = SPLIT ? b * TM + p : p * (RPP / 32) + b;   // 32-row block of the tile
-          if (wm == blk / TM) {
-            const int i = blk % TM;                     // compile-time after unrolling
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const int chunk = (wn * TN * 32 + j * 32 + 8 * q + 4 * half) >> 2;
-                const f32x4_t v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-                *reinterpret_cast<f32x4_t*>(st + (32 * b + l31) * G::ROWB + ((chunk ^ (l31 & 7)) << 4)) = v;
-              }
-          }
-        }
+        pl.stage_pass(st, p, ml.acc);
         wait_lds();
         __builtin_amdgcn_s_barrier();                    // H1: the pass is staged
         __builtin_amdgcn_s_barrier();                    // H2: the loader waves hold it
@@ -341,7 +280,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     WS_T(item_no, 3, wave, lane);
     __builtin_amdgcn_s_setprio(2);
-    if (more_items) ldf(a0, b0, smem + curo, 0);
+    if (more_items) ml.read_first();
   }
 }
 
@@ -355,15 +294,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 HERO_WSD_INST(3, 3)
 HERO_WSD_INST(2, 3)
 
-static int wsd_num_cus() {
-  static int n = [] {
-    int dev = 0, v = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    return v > 0 ? v : 256;
-  }();
-  return n;
-}
-
 template <int TM, int TN, int EK>
 static int launch_d(const WsArgs& g, int slot, hipStream_t s) {
   typedef Geo<TM, TN> G;
@@ -372,7 +302,7 @@ static int launch_d(const WsArgs& g, int slot, hipStream_t s) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_wsd_kernel<TM, TN, EK>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
     attr_set = true;
   }
-  const int grid = g.nwork < wsd_num_cus() ? g.nwork : wsd_num_cus();
+  const int grid = g.nwork < num_cus() ? g.nwork : num_cus();
   void* tok = gemm_prof_begin(slot, s);
   hipLaunchKernelGGL((gemm_wsd_kernel<TM, TN, EK>), dim3(grid), dim3(512), G::LDS, s, g);
   gemm_prof_end(tok, 2.0 * (double)g.M * (double)g.N * (double)g.K, s);
