@@ -1,15 +1,28 @@
 // Masked multi-head self-attention, head size 64, forward and backward (gfx950): the fp32-VALU
-// kernels.  They serve the f32 parity mode at every length and bf16 for 64 < L <= 256; bf16 with
-// L <= 64 (every sequence of the TVR step) is dispatched to the matrix-core kernels of
-// attention_mfma.hip, which issue ~10x fewer wave instructions per head.
+// kernels and the dispatcher of all attention kernels.  bf16, the training dtype, runs on the
+// matrix cores (attention_mfma.hip: L <= 64; attention_mfma_long.hip: 64 < L <= 256, the backward
+// given the forward output in a.ctx).  This file keeps the f32 parity mode and the bf16 calls
+// those two do not take.  Every kernel it emits, by the calls that launch it (run<T>() below):
+//
+//   dtype  call                      L                          kernel
+//   f32    fwd / bwd, packed or not  1-16 / 17-32 / 33-64       attn_{fwd,bwd}_small_kernel<4 / 2 / 1>
+//   f32    fwd                       65 .. max_len<float>(0)    attn_fwd_kernel<float>
+//   f32    bwd                       65-128                     attn_bwd_kernel<float, 32, staged>
+//   f32    bwd                       129-144                    attn_bwd_kernel<float, 64, staged>
+//   f32    bwd                       145-256                    attn_bwd_kernel<float, 64, QO_GLOBAL>
+//   bf16   bwd without a.ctx         65-128 / 129-256           attn_bwd_kernel<bf16_t, 32 / 64, staged>
+//   bf16   fwd                       257 .. max_len<bf16_t>(0)  attn_fwd_kernel<bf16_t>
+//
+// hero_attention_fwd serves the last row although hero_attention_max_len(bf16, 0) answers 256 (the
+// reach of the matrix-core kernels and of every bf16 backward): a caller that asks first never
+// gets there.  Packed batches (seq_off) exist in the small and the matrix-core kernels only.
 //
 // HERO's sequences are short (a subtitle's frames+tokens: 10-40; a clip's frames: <= 100; the
 // long-video stress case: 256), so attention is < 1 % of the FLOPs of a layer and is bound by
 // launch count and HBM traffic, not by the matrix cores.  One workgroup (4 waves) owns one
 // (sequence, head): K and V of that head are staged once in LDS, every wave then walks query rows:
-//   scores : a key is owned by LPK adjacent lanes (LPK = 1/2/4 chosen from L so short sequences
-//            still fill the wave), each lane dots its 64/LPK slice of q (held in registers)
-//            with the K row in LDS, partial dots are combined with wave shuffles;
+//   scores : a lane owns one key (64 keys per pass) and dots the query row, held in registers,
+//            with its K row in LDS;
 //   softmax: row max / sum with wave shuffles over the per-wave score row in LDS;
 //   P.V    : lane d accumulates output column d over the keys (probability broadcast from LDS,
 //            V row read conflict-free).
@@ -21,6 +34,12 @@
 namespace hero {
 
 constexpr int DH = 64;
+constexpr size_t LDS_BUDGET = 150 * 1024;
+constexpr int SMALL_MAX_L = 64;   // the small kernels: all keys in one pass of a wave
+constexpr int BWD_PASSES = 4;     // score passes of attn_bwd_kernel, 64 keys each: L <= 256
+
+// packed batches (seq_off): bf16 in the matrix-core kernels, f32 in the small kernels
+static int max_packed_len(int dtype) { return dtype == HERO_BF16 ? 256 : SMALL_MAX_L; }
 
 // LDS written by some lanes of a wave and read by other lanes of the SAME wave: the DS pipe is
 // in-order per wave, this only pins the compiler (and its s_waitcnt) at that point.
@@ -45,55 +64,37 @@ __device__ __forceinline__ void stage_head(const T* __restrict__ src, int ld, in
   }
 }
 
-// dot of the register slice qv[0..DPL) with row `row` of an LDS matrix, columns [p*DPL, (p+1)*DPL)
-template <typename T, int DPL> __device__ __forceinline__ float dot_slice(const float (&qv)[DPL], const T* row_ptr);
-template <int DPL> __device__ __forceinline__ float dot_slice_f32(const float (&qv)[DPL], const float* rp) {
+// dot of a 64-wide row held in registers with a row of an LDS matrix
+template <typename T> __device__ __forceinline__ float dot_row(const float (&qv)[DH], const T* rp);
+template <> __device__ __forceinline__ float dot_row<float>(const float (&qv)[DH], const float* rp) {
   float s = 0.f;
 #pragma unroll
-  for (int t = 0; t < DPL; ++t) s = fmaf(qv[t], rp[t], s);
+  for (int t = 0; t < DH; ++t) s = fmaf(qv[t], rp[t], s);
   return s;
 }
-template <int DPL> __device__ __forceinline__ float dot_slice_bf16(const float (&qv)[DPL], const bf16_t* rp) {
+template <> __device__ __forceinline__ float dot_row<bf16_t>(const float (&qv)[DH], const bf16_t* rp) {
   float s = 0.f;
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(rp);  // STRIDE 66 and DPL even keep this 4-byte aligned
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(rp);  // STRIDE 66 keeps this 4-byte aligned
 #pragma unroll
-  for (int t = 0; t < DPL / 2; ++t) {
+  for (int t = 0; t < DH / 2; ++t) {
     const uint32_t u = w[t];
     s = fmaf(qv[2 * t], __uint_as_float(u << 16), s);
     s = fmaf(qv[2 * t + 1], __uint_as_float(u & 0xffff0000u), s);
   }
   return s;
 }
-template <typename T, int DPL> struct Dot;
-template <int DPL> struct Dot<float, DPL> {
-  static __device__ __forceinline__ float run(const float (&qv)[DPL], const float* rp) { return dot_slice_f32<DPL>(qv, rp); }
-};
-template <int DPL> struct Dot<bf16_t, DPL> {
-  static __device__ __forceinline__ float run(const float (&qv)[DPL], const bf16_t* rp) { return dot_slice_bf16<DPL>(qv, rp); }
-};
 
-// load a 64-wide row slice [p*DPL, (p+1)*DPL) from global into registers (same address across the
-// lanes that share p -> broadcast loads)
-template <typename T, int DPL>
-__device__ __forceinline__ void load_row_slice(const T* __restrict__ row, int p, float (&qv)[DPL]) {
+// a 64-wide row into registers (every lane reads the same address -> broadcast)
+template <typename T>
+__device__ __forceinline__ void load_row(const T* row, float (&qv)[DH]) {
 #pragma unroll
-  for (int t = 0; t < DPL; t += 4) {
-    const float4 v = V4<T>::ld(row + p * DPL + t);
-    qv[t] = v.x; qv[t + 1] = v.y; qv[t + 2] = v.z; qv[t + 3] = v.w;
-  }
+  for (int t = 0; t < DH; ++t) qv[t] = ld1<T>(row + t);
 }
 
-// same, from an LDS matrix with row stride 64 (lanes sharing p read the same address -> broadcast)
-template <typename T, int DPL>
-__device__ __forceinline__ void lds_row_slice(const T* row, int p, float (&qv)[DPL]) {
-#pragma unroll
-  for (int t = 0; t < DPL; ++t) qv[t] = ld1<T>(row + p * DPL + t);
-}
-
-template <typename T, int LPK>
+template <typename T>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(HeroAttn a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int DPL = DH / LPK, KPP = 64 / LPK, STR = KvLay<T>::STRIDE;
+  constexpr int STR = KvLay<T>::STRIDE;
   const int L = a.L, H = a.H, D = H * DH;
   const int s = blockIdx.x / H, h = blockIdx.x % H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -110,24 +111,19 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(HeroAttn a) {
 
   const float* mask = a.mask ? a.mask + (size_t)s * L : nullptr;
   DropCtx drop(a.dropout);
-  const int g = lane / LPK, p = lane % LPK;
   T* ctx = static_cast<T*>(a.ctx) + (size_t)s * L * D + h * DH;
   float* probs = a.probs ? a.probs + ((size_t)(s * H + h) * L) * L : nullptr;
 
   for (int i = wave; i < L; i += 4) {
-    float qv[DPL];
-    lds_row_slice<T, DPL>(Qg + (size_t)i * 3 * D, p, qv);
+    float qv[DH];
+    load_row<T>(Qg + (size_t)i * 3 * D, qv);
     // ---- scores
     float mx = -3.0e38f;
-    for (int j0 = 0; j0 < L; j0 += KPP) {
-      const int j = j0 + g;
-      float sc = 0.f;
-      if (j < L) sc = Dot<T, DPL>::run(qv, Ks + j * STR + p * DPL);
-#pragma unroll
-      for (int o = 1; o < LPK; o <<= 1) sc += __shfl_xor(sc, o, 64);
+    for (int j0 = 0; j0 < L; j0 += 64) {
+      const int j = j0 + lane;
       if (j < L) {
-        sc = sc * a.scale + (mask ? mask[j] : 0.f);
-        if (p == 0) Ps[j] = sc;
+        const float sc = dot_row<T>(qv, Ks + j * STR) * a.scale + (mask ? mask[j] : 0.f);
+        Ps[j] = sc;
         mx = fmaxf(mx, sc);
       }
     }
@@ -168,13 +164,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(HeroAttn a) {
 // Backward. LDS: K, V (padded stride), Q, dO (stride 64), and for a chunk of R query rows the
 // matrices dS[R][Lp] (already scaled) and Pd[R][Lp] (dropped probabilities).  dK/dV accumulate in
 // registers across chunks: wave w owns keys w, w+4, ... (KPW of them per wave).
-// QO_GLOBAL (round 3: fp32 up to L = 256, the config-5 length of the parity mode): Q and dO are read from global
+// QO_GLOBAL (f32 beyond 144 rows, up to the 256 of the parity mode's long-video case): Q and dO are read from global
 // memory (L2) row by row instead of being staged, which leaves the LDS to K, V and the row chunk.
-template <typename T, int LPK, int KPW, bool QO_GLOBAL>
+template <typename T, int KPW, bool QO_GLOBAL>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(HeroAttn a, int R) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int DPL = DH / LPK, KPP = 64 / LPK, STR = KvLay<T>::STRIDE;
-  constexpr int MAXP = LPK == 1 ? 4 : 1;   // score passes: L <= 256 (LPK 1), <= 32 (LPK 2), <= 16 (LPK 4)
+  constexpr int STR = KvLay<T>::STRIDE;
   const int L = a.L, H = a.H, D = H * DH;
   const int s = blockIdx.x / H, h = blockIdx.x % H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -198,7 +193,6 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(HeroAttn a, int R) {
   __syncthreads();
 
   DropCtx drop(a.dropout);
-  const int g = lane / LPK, p = lane % LPK;
   const float* probs = a.probs + ((size_t)(s * H + h) * L) * L;
   T* dqkv = static_cast<T*>(a.dqkv) + (size_t)s * L * 3 * D;
 
@@ -220,22 +214,21 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(HeroAttn a, int R) {
     // ---- phase A: rows of this chunk -> dS, Pd in LDS, dQ to HBM
     for (int il = wave; il < cr; il += 4) {
       const int i = c0 + il;
-      float ov[DPL];
-      lds_row_slice<T, DPL>(Os + (size_t)i * OST, p, ov);
+      float ov[DH];
+      load_row<T>(Os + (size_t)i * OST, ov);
       float* dSr = dS + (size_t)il * Lp;
       float* Pdr = Pd + (size_t)il * Lp;
-      float prs[MAXP], dps[MAXP];
+      float prs[BWD_PASSES], dps[BWD_PASSES];   // lane owns key ps * 64 + lane of every pass
       float delta = 0.f;
 #pragma unroll
-      for (int ps = 0; ps < MAXP; ++ps) {
-        const int j = ps * KPP + g;
+      for (int ps = 0; ps < BWD_PASSES; ++ps) {
+        const int j = ps * 64 + lane;
         float dp = 0.f;
         prs[ps] = 0.f;
-        if (ps * KPP < L) {
-          if (j < L) dp = Dot<T, DPL>::run(ov, Vs + j * STR + p * DPL);
-#pragma unroll
-          for (int o = 1; o < LPK; o <<= 1) dp += __shfl_xor(dp, o, 64);
-          if (j < L && p == 0) {
+        if (ps * 64 < L) {         // wave-uniform: a pass beyond L costs one scalar branch
+          if (j < L) dp = dot_row<T>(ov, Vs + j * STR);      // dO_i . V_j
+          if (j < L) {             // a block of its own: merged with the dot, these 256-VGPR kernels allocate differently
+                                   // (+480 instructions in <float, 32>, profiles/attn_valu_refactor_ab.txt)
             const float pr = Pdr[j];
             const float m = drop.on() ? drop.mask1(((uint64_t)(s * H + h) * L + i) * (uint64_t)Lp + j) : 1.f;
             dp *= m;                 // dP_ij
@@ -248,9 +241,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(HeroAttn a, int R) {
       }
       delta = wave_sum(delta);
 #pragma unroll
-      for (int ps = 0; ps < MAXP; ++ps) {
-        const int j = ps * KPP + g;
-        if (ps * KPP < L && j < L && p == 0) dSr[j] = prs[ps] * (dps[ps] - delta) * a.scale;
+      for (int ps = 0; ps < BWD_PASSES; ++ps) {
+        const int j = ps * 64 + lane;
+        if (ps * 64 < L && j < L) dSr[j] =prs[ps] * (dps[ps] - delta) * a.scale;
       }
       wave_lds_sync();
       // dQ[i][lane] = sum_j dS_ij K[j][lane]
@@ -286,19 +279,19 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(HeroAttn a, int R) {
 }
 
 // =============================================================================================
-// Short sequences (L <= 64: every HERO training shape).  Q, K, V (and dO) of one (sequence, head)
-// are staged in LDS as fp32 with 16-byte aligned, conflict-free strides, so the inner loops are
-// ds_read_b128 + v_fma only (no bf16 unpacking); all keys fit one pass (64/LPK >= L), softmax runs
+// Short sequences (f32 parity mode, L <= 64, packed or not).  Q, K, V (and dO) of one (sequence, head)
+// are staged in LDS with 16-byte aligned, conflict-free strides, so the inner loops are
+// ds_read_b128 + v_fma only; a key is owned by LPK adjacent lanes (LPK = 4/2/1 chosen from L so
+// short sequences still fill the wave) and all keys fit one pass (64/LPK >= L), softmax runs
 // in registers with DPP reductions; the dK/dV phase walks 4 keys at a time (one broadcast b128 of
 // dS / P per query row feeds 8 FMAs).
 // =============================================================================================
 constexpr int KS = 68;   // fp32 row stride of matrices that are read row-per-lane with ds_read_b128
 
-template <typename T>
-__device__ __forceinline__ void stage_f32(const T* __restrict__ src, int ld, int L, float* dst, int stride) {
+__device__ __forceinline__ void stage_f32(const float* __restrict__ src, int ld, int L, float* dst, int stride) {
   for (int q = threadIdx.x; q < L * 16; q += blockDim.x) {
     const int r = q >> 4, c = (q & 15) * 4;
-    *reinterpret_cast<float4*>(dst + r * stride + c) = V4<T>::ld(src + (size_t)r * ld + c);
+    *reinterpret_cast<float4*>(dst + r * stride + c) = V4<float>::ld(src + (size_t)r * ld + c);
   }
 }
 
@@ -322,7 +315,7 @@ __device__ __forceinline__ float dot_regs(const float (&q)[DPL], const float* ro
   return s0 + s1;
 }
 
-template <typename T, int LPK>
+template <int LPK>
 __global__ __launch_bounds__(256) void attn_fwd_small_kernel(HeroAttn a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int DPL = DH / LPK;
@@ -342,17 +335,17 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(HeroAttn a) {
   float* Ms = Vs + L * DH;
   float* Ps = Ms + Lp + wave * Lp;
 
-  const T* qkv = static_cast<const T*>(a.qkv) + (size_t)row0 * 3 * D + h * DH;
-  stage_f32<T>(qkv, 3 * D, L, Qs, DH);
-  stage_f32<T>(qkv + D, 3 * D, L, Ks, KS);
-  stage_f32<T>(qkv + 2 * D, 3 * D, L, Vs, DH);
+  const float* qkv = static_cast<const float*>(a.qkv) + (size_t)row0 * 3 * D + h * DH;
+  stage_f32(qkv, 3 * D, L, Qs, DH);
+  stage_f32(qkv + D, 3 * D, L, Ks, KS);
+  stage_f32(qkv + 2 * D, 3 * D, L, Vs, DH);
   for (int j = threadIdx.x; j < L; j += 256) Ms[j] = a.mask ? a.mask[(size_t)s * Lm + j] : 0.f;
   __syncthreads();
 
   DropCtx drop(a.dropout);
   const int g = lane / LPK, p = lane % LPK;
   const bool valid = g < L;
-  T* ctx = static_cast<T*>(a.ctx) + (size_t)row0 * D + h * DH;
+  float* ctx = static_cast<float*>(a.ctx) + (size_t)row0 * D + h * DH;
   float* probs = a.probs ? a.probs + ((size_t)(s * H + h) * Lm) * Lm : nullptr;
   const float mj = valid ? Ms[g] : 0.f;
   const float* krow = Ks + (valid ? g : 0) * KS + p * DPL;
@@ -382,12 +375,12 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(HeroAttn a) {
       acc1 = fmaf(pj.w, Vs[(j + 3) * DH + lane], acc1);
     }
     for (; j < L; ++j) acc0 = fmaf(Ps[j], Vs[j * DH + lane], acc0);
-    st1<T>(ctx + (size_t)i * D + lane, acc0 + acc1);
+    st1<float>(ctx + (size_t)i * D + lane, acc0 + acc1);
     wave_lds_sync();
   }
 }
 
-template <typename T, int LPK>
+template <int LPK>
 __global__ __launch_bounds__(256) void attn_bwd_small_kernel(HeroAttn a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int DPL = DH / LPK;
@@ -408,12 +401,12 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(HeroAttn a) {
   float* dS = Vs + L * KS;                       // [L][Lp]  (scaled)
   float* Pd = dS + L * Lp;                       // [L][Lp]  P on entry, dropped P afterwards
 
-  const T* qkv = static_cast<const T*>(a.qkv) + (size_t)row0 * 3 * D + h * DH;
-  const T* dctx = static_cast<const T*>(a.dctx) + (size_t)row0 * D + h * DH;
-  stage_f32<T>(qkv, 3 * D, L, Qs, DH);
-  stage_f32<T>(qkv + D, 3 * D, L, Ks, KS);
-  stage_f32<T>(qkv + 2 * D, 3 * D, L, Vs, KS);
-  stage_f32<T>(dctx, D, L, Os, DH);
+  const float* qkv = static_cast<const float*>(a.qkv) + (size_t)row0 * 3 * D + h * DH;
+  const float* dctx = static_cast<const float*>(a.dctx) + (size_t)row0 * D + h * DH;
+  stage_f32(qkv, 3 * D, L, Qs, DH);
+  stage_f32(qkv + D, 3 * D, L, Ks, KS);
+  stage_f32(qkv + 2 * D, 3 * D, L, Vs, KS);
+  stage_f32(dctx, D, L, Os, DH);
   {
     const float* src = a.probs + ((size_t)(s * H + h) * Lm) * Lm;
     for (int q = threadIdx.x; q < L * L; q += 256) {
@@ -431,7 +424,7 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(HeroAttn a) {
   DropCtx drop(a.dropout);
   const int g = lane / LPK, p = lane % LPK;
   const bool valid = g < L;
-  T* dqkv = static_cast<T*>(a.dqkv) + (size_t)row0 * 3 * D + h * DH;
+  float* dqkv = static_cast<float*>(a.dqkv) + (size_t)row0 * 3 * D + h * DH;
   const float* vrow = Vs + (valid ? g : 0) * KS + p * DPL;
 
   // ---- phase A: one wave per query row -> dS row, dropped-P row (LDS), dQ row (HBM)
@@ -463,7 +456,7 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(HeroAttn a) {
       acc1 = fmaf(d4.w, Ks[(j + 3) * KS + lane], acc1);
     }
     for (; j < L; ++j) acc0 = fmaf(dSr[j], Ks[j * KS + lane], acc0);
-    st1<T>(dqkv + (size_t)i * 3 * D + lane, acc0 + acc1);
+    st1<float>(dqkv + (size_t)i * 3 * D + lane, acc0 + acc1);
   }
   __syncthreads();
   // ---- phase B: a wave owns quads of keys; lane = feature column
@@ -482,8 +475,8 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(HeroAttn a) {
 #pragma unroll
     for (int t = 0; t < 4; ++t)
       if (j0 + t < L) {
-        st1<T>(dqkv + (size_t)(j0 + t) * 3 * D + D + lane, kk[t]);
-        st1<T>(dqkv + (size_t)(j0 + t) * 3 * D + 2 * D + lane, vv[t]);
+        st1<float>(dqkv + (size_t)(j0 + t) * 3 * D + D + lane, kk[t]);
+        st1<float>(dqkv + (size_t)(j0 + t) * 3 * D + 2 * D + lane, vv[t]);
       }
   }
 }
@@ -491,68 +484,67 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(HeroAttn a) {
 static size_t small_fwd_lds(int L) { const int Lp = (L + 3) & ~3; return ((size_t)L * (DH + KS + DH) + 5 * Lp) * sizeof(float); }
 static size_t small_bwd_lds(int L) { const int Lp = (L + 3) & ~3; return ((size_t)L * (2 * DH + 2 * KS) + 2 * (size_t)L * Lp) * sizeof(float); }
 
-template <typename T, int LPK>
+template <int LPK>
 static int launch_small(const HeroAttn& a, bool bwd, hipStream_t s) {
   const size_t lds = bwd ? small_bwd_lds(a.L) : small_fwd_lds(a.L);
-  HERO_REQUIRE(lds <= 150 * 1024, "hero_attention(small): L = %d needs %zu bytes of LDS", a.L, lds);
+  HERO_REQUIRE(lds <= LDS_BUDGET, "hero_attention(small): L = %d needs %zu bytes of LDS", a.L, lds);
   if (bwd) {
-    HERO_ENSURE_LDS((&attn_bwd_small_kernel<T, LPK>), 150 * 1024, "attn_bwd_small_kernel");
-    hipLaunchKernelGGL((attn_bwd_small_kernel<T, LPK>), dim3(a.S * a.H), dim3(256), lds, s, a);
+    HERO_ENSURE_LDS((&attn_bwd_small_kernel<LPK>), LDS_BUDGET, "attn_bwd_small_kernel");
+    hipLaunchKernelGGL((attn_bwd_small_kernel<LPK>), dim3(a.S * a.H), dim3(256), lds, s, a);
   } else {
-    HERO_ENSURE_LDS((&attn_fwd_small_kernel<T, LPK>), 150 * 1024, "attn_fwd_small_kernel");
-    hipLaunchKernelGGL((attn_fwd_small_kernel<T, LPK>), dim3(a.S * a.H), dim3(256), lds, s, a);
+    HERO_ENSURE_LDS((&attn_fwd_small_kernel<LPK>), LDS_BUDGET, "attn_fwd_small_kernel");
+    hipLaunchKernelGGL((attn_fwd_small_kernel<LPK>), dim3(a.S * a.H), dim3(256), lds, s, a);
   }
   return check_launch(bwd ? "hero_attention_bwd(small)" : "hero_attention_fwd(small)");
 }
-
-constexpr size_t LDS_BUDGET = 150 * 1024;
 
 template <typename T> static size_t fwd_lds(int L) {
   const int Lp = (L + 3) & ~3;
   return (((size_t)(2 * L * KvLay<T>::STRIDE) * sizeof(T)) + 15) / 16 * 16 + (size_t)4 * Lp * sizeof(float);
 }
-template <typename T> static size_t bwd_lds_fixed(int L, bool qo_global = false) {
+template <typename T> static size_t bwd_lds_fixed(int L, bool qo_global) {
   return (((size_t)(2 * L * KvLay<T>::STRIDE + (qo_global ? 0 : 2 * L * DH)) * sizeof(T)) + 15) / 16 * 16;
 }
+static size_t bwd_lds_rows(int L, int R) { return (size_t)2 * R * ((L + 3) & ~3) * sizeof(float); }   // dS and Pd of R query rows
 template <typename T> static int max_len(int backward) {
   int L = 1;
   if (!backward) {
     while (L < 1024 && fwd_lds<T>(L + 1) <= LDS_BUDGET) ++L;
     return L;
   }
-  while (L < 256 && bwd_lds_fixed<T>(L + 1, true) + (size_t)2 * 4 * ((L + 4) & ~3) * sizeof(float) <= LDS_BUDGET) ++L;
+  while (L < 64 * BWD_PASSES && bwd_lds_fixed<T>(L + 1, true) + bwd_lds_rows(L + 1, 4) <= LDS_BUDGET) ++L;
   return L;
 }
 
-template <typename T, int LPK>
+template <typename T>
 static int launch_fwd(const HeroAttn& a, hipStream_t s) {
   const size_t lds = fwd_lds<T>(a.L);
   HERO_REQUIRE(lds <= LDS_BUDGET, "hero_attention_fwd: L = %d needs %zu bytes of LDS", a.L, lds);
-  HERO_ENSURE_LDS((&attn_fwd_kernel<T, LPK>), LDS_BUDGET, "attn_fwd_kernel");
-  hipLaunchKernelGGL((attn_fwd_kernel<T, LPK>), dim3(a.S * a.H), dim3(256), lds, s, a);
+  HERO_ENSURE_LDS((&attn_fwd_kernel<T>), LDS_BUDGET, "attn_fwd_kernel");
+  hipLaunchKernelGGL((attn_fwd_kernel<T>), dim3(a.S * a.H), dim3(256), lds, s, a);
   return check_launch("hero_attention_fwd");
 }
-template <typename T, int LPK, int KPW, bool QO_GLOBAL = false>
+template <typename T, int KPW, bool QO_GLOBAL>
 static int launch_bwd(const HeroAttn& a, hipStream_t s) {
-  const int Lp = (a.L + 3) & ~3;
   const size_t fixed = bwd_lds_fixed<T>(a.L, QO_GLOBAL);
-  if (!QO_GLOBAL && fixed + (size_t)2 * 4 * Lp * sizeof(float) > LDS_BUDGET) return launch_bwd<T, LPK, KPW, true>(a, s);
-  int R = (int)((LDS_BUDGET - fixed) / ((size_t)2 * Lp * sizeof(float)));
+  int R = (int)((LDS_BUDGET - fixed) / bwd_lds_rows(a.L, 1));
   if (R > a.L) R = a.L;
   R &= ~3;
   if (R < 4) R = a.L < 4 ? a.L : 4;
-  const size_t lds = fixed + (size_t)2 * R * Lp * sizeof(float);
+  const size_t lds = fixed + bwd_lds_rows(a.L, R);
   HERO_REQUIRE(lds <= LDS_BUDGET, "hero_attention_bwd: L = %d needs %zu bytes of LDS", a.L, lds);
-  HERO_ENSURE_LDS((&attn_bwd_kernel<T, LPK, KPW, QO_GLOBAL>), LDS_BUDGET, "attn_bwd_kernel");
-  hipLaunchKernelGGL((attn_bwd_kernel<T, LPK, KPW, QO_GLOBAL>), dim3(a.S * a.H), dim3(256), lds, s, a, R);
+  HERO_ENSURE_LDS((&attn_bwd_kernel<T, KPW, QO_GLOBAL>), LDS_BUDGET, "attn_bwd_kernel");
+  hipLaunchKernelGGL((attn_bwd_kernel<T, KPW, QO_GLOBAL>), dim3(a.S * a.H), dim3(256), lds, s, a, R);
   return check_launch("hero_attention_bwd");
 }
-template <typename T, int LPK>
+// 64 < L <= 256: a wave holds the dK / dV rows of KPW = 32 or 64 keys.  Q and dO stay in global memory where staging
+// them would leave no room for four query rows: f32 from L = 145 on; bf16 needs 141 KB at L = 256 and always stages.
+template <typename T>
 static int bwd_by_len(const HeroAttn& a, hipStream_t s) {
-  if (a.L <= 32) return launch_bwd<T, LPK, 8>(a, s);
-  if (a.L <= 64) return launch_bwd<T, LPK, 16>(a, s);
-  if (a.L <= 128) return launch_bwd<T, LPK, 32>(a, s);
-  return launch_bwd<T, LPK, 64>(a, s);
+  if (a.L <= 128) return launch_bwd<T, 32, false>(a, s);
+  if constexpr (sizeof(T) == 4)
+    if (bwd_lds_fixed<T>(a.L, false) + bwd_lds_rows(a.L, 4) > LDS_BUDGET) return launch_bwd<T, 64, true>(a, s);
+  return launch_bwd<T, 64, false>(a, s);
 }
 int attn_mfma_run(const HeroAttn& a, bool bwd, hipStream_t s);        // attention_mfma.hip (bf16, L <= 64)
 int attn_mfma_long_run(const HeroAttn& a, bool bwd, hipStream_t s);   // attention_mfma_long.hip (bf16, 64 < L <= 256)
@@ -562,7 +554,7 @@ static int run(const HeroAttn& a, bool bwd, hipStream_t s) {
   if (sizeof(T) == 2 && a.L <= 64) return attn_mfma_run(a, bwd, s);
   // longer sequences on the matrix cores too; the backward takes delta_i = dO_i . ctx_i from the forward output
   if (sizeof(T) == 2 && a.L <= 256 && (!bwd || a.ctx)) return attn_mfma_long_run(a, bwd, s);
-  if (a.seq_off && a.L > 64) {
+  if (a.seq_off && a.L > SMALL_MAX_L) {
     set_error("hero_attention_%s: packed batches with L = %d > 64 need the bf16 matrix-core kernels (and ctx in the backward)",
               bwd ? "bwd" : "fwd", a.L);
     return HERO_ERR_UNSUPPORTED;
@@ -572,10 +564,12 @@ static int run(const HeroAttn& a, bool bwd, hipStream_t s) {
     set_error("hero_attention_%s: sequence length %d exceeds the LDS-resident limit %d for this dtype", bwd ? "bwd" : "fwd", a.L, lim);
     return HERO_ERR_UNSUPPORTED;
   }
-  if (a.L <= 16) return launch_small<T, 4>(a, bwd, s);
-  if (a.L <= 32) return launch_small<T, 2>(a, bwd, s);
-  if (a.L <= 64) return launch_small<T, 1>(a, bwd, s);
-  return bwd ? bwd_by_len<T, 1>(a, s) : launch_fwd<T, 1>(a, s);
+  if constexpr (sizeof(T) == 4) {   // bf16 with L <= 64 has left for the matrix cores above
+    if (a.L <= 16) return launch_small<4>(a, bwd, s);
+    if (a.L <= 32) return launch_small<2>(a, bwd, s);
+    if (a.L <= SMALL_MAX_L) return launch_small<1>(a, bwd, s);
+  }
+  return bwd ? bwd_by_len<T>(a, s) : launch_fwd<T>(a, s);
 }
 
 }  // namespace hero
@@ -586,8 +580,8 @@ static int check_attn(const HeroAttn* a, bool bwd) {
   HERO_REQUIRE(a && a->qkv, "hero_attention: null qkv");
   HERO_REQUIRE(a->S >= 0 && a->L > 0 && a->H > 0, "hero_attention: bad dims S=%d L=%d H=%d", a->S, a->L, a->H);
   HERO_REQUIRE(a->dtype == HERO_F32 || a->dtype == HERO_BF16, "hero_attention: bad dtype %d", a->dtype);
-  HERO_REQUIRE(!a->seq_off || a->L <= (a->dtype == HERO_BF16 ? 256 : 64), "hero_attention: packed batches (seq_off) need L <= %d, got %d",
-               a->dtype == HERO_BF16 ? 256 : 64, a->L);
+  HERO_REQUIRE(!a->seq_off || a->L <= max_packed_len(a->dtype), "hero_attention: packed batches (seq_off) need L <= %d, got %d",
+               max_packed_len(a->dtype), a->L);
   if (bwd) {
     HERO_REQUIRE((a->probs || a->stats) && a->dctx && a->dqkv, "hero_attention_bwd: probs (or stats)/dctx/dqkv required");
     if (!a->probs)
@@ -599,23 +593,18 @@ static int check_attn(const HeroAttn* a, bool bwd) {
   return HERO_OK;
 }
 
-extern "C" int hero_attention_fwd(const HeroAttn* a, hero_stream_t stream) {
-  int rc = check_attn(a, false);
+static int attention(const HeroAttn* a, bool bwd, hero_stream_t stream) {
+  int rc = check_attn(a, bwd);
   if (rc) return rc;
   if (a->S == 0) return HERO_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return a->dtype == HERO_BF16 ? run<bf16_t>(*a, false, s) : run<float>(*a, false, s);
+  return a->dtype == HERO_BF16 ? run<bf16_t>(*a, bwd, s) : run<float>(*a, bwd, s);
 }
-extern "C" int hero_attention_bwd(const HeroAttn* a, hero_stream_t stream) {
-  int rc = check_attn(a, true);
-  if (rc) return rc;
-  if (a->S == 0) return HERO_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return a->dtype == HERO_BF16 ? run<bf16_t>(*a, true, s) : run<float>(*a, true, s);
-}
+extern "C" int hero_attention_fwd(const HeroAttn* a, hero_stream_t stream) { return attention(a, false, stream); }
+extern "C" int hero_attention_bwd(const HeroAttn* a, hero_stream_t stream) { return attention(a, true, stream); }
 extern "C" int hero_attention_stats_ok(int dtype, int L) { return dtype == HERO_BF16 && L >= 1 && L <= 64 ? 1 : 0; }
-extern "C" int hero_attention_max_packed_len(int dtype) { return dtype == HERO_BF16 ? 256 : 64; }
+extern "C" int hero_attention_max_packed_len(int dtype) { return max_packed_len(dtype); }
 extern "C" int hero_attention_max_len(int dtype, int backward) {
   if (dtype == HERO_BF16) return 256;       // matrix-core kernels (the backward wants a.ctx beyond 64)
-  return dtype == HERO_BF16 ? max_len<bf16_t>(backward) : max_len<float>(backward);
+  return max_len<float>(backward);
 }

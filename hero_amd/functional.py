@@ -774,7 +774,8 @@ def k_attn_fwd(qkv, mask_add, S, Lq, H, drop=None, want_probs=True, out=None, se
 def k_attn_bwd(qkv, saved, dctx, S, Lq, H, drop=None, out=None, seq_off=None, ctx=None, mask_add=None):
     """saved: k_attn_fwd's second result.  ctx: the forward output (optional).  With it the bf16 backward of
     64 < Lq <= 256 runs on the matrix-core kernels (delta_i = dO_i . ctx_i); without it those lengths take the
-    fp32-VALU path.  mask_add: the forward's additive mask - needed when `saved` holds row statistics."""
+    fp32-VALU kernels, which know no packed batches (seq_off) beyond 64 rows.  Lq <= 64 in bf16 and every f32
+    call do not read it.  mask_add: the forward's additive mask - needed when `saved` holds row statistics."""
     dqkv = out if out is not None else torch.empty_like(qkv)
     is_stats = saved.dim() == 1
     a = L.Attn(L.ptr(qkv), L.ptr(mask_add) if is_stats else None, L.ptr(ctx), None if is_stats else L.ptr(saved), L.ptr(dctx),

@@ -759,10 +759,13 @@ def test_colsum_no_rows_and_few_rows(HF, Lb, dtype):
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("S,L,H", [(3, 9, 2), (5, 24, 12), (2, 60, 12), (2, 100, 3), (1, 130, 2), (4, 15, 12),
                                    (3, 32, 4), (2, 33, 2), (2, 64, 3), (41, 24, 12), (1, 1, 1), (2, 65, 2),
-                                   (3, 128, 2), (2, 129, 3), (2, 200, 4), (3, 256, 12)])
+                                   (3, 128, 2), (2, 129, 3), (2, 200, 4), (3, 256, 12),
+                                   (1, 144, 1), (1, 145, 1), (1, 257, 1)])
 def test_attention_fwd_bwd(HF, Lb, dtype, S, L, H):
-    """fp32: exact-f32 VALU kernels (forward L <= 256; backward up to hero_attention_max_len, 148 rows);
-    bf16: matrix-core kernels for every L <= 256."""
+    """fp32: exact-f32 VALU kernels, forward at every length here, backward up to hero_attention_max_len (256 rows; Q and dO
+    are staged in LDS up to 144 rows and read from global memory from 145 on);
+    bf16: matrix-core kernels for every L <= 256, checked against the fp32-VALU backward (no ctx) beyond 64 rows.
+    257 rows are forward-only in both dtypes, and the one bf16 length here that runs the VALU forward."""
     D = H * 64
     qkv = rnd(S * L, 3 * D, dtype=dtype, seed=1)
     lens = [max(1, L - 3 * i) for i in range(S)]
