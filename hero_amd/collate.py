@@ -8,6 +8,8 @@ Host half - same names, inputs and outputs as the reference, so a reference Data
     vcmr_collate    vcmr_collate                         data/vcmr.py:140-159
     videoqa_item    VideoQaDataset.__getitem__           data/videoQA.py:62-121 (one question)
     video_qa_collate  video_qa_collate                   data/videoQA.py:155-182 (pinned by tests/golden/case_videoqa.npz)
+    violin_item     ViolinDataset.__getitem__            data/violin.py:66-110
+    violin_collate / violin_eval_collate                 data/violin.py:118-141, 163-170 (pinned by tests/golden/case_violin.npz)
 They are written over LENGTH arrays (one allocation per output, no pad_sequence / per-row python tensors) and also
 return the handful of int32 length arrays (`batch["lengths"]`) from which the device half rebuilds every index tensor.
 
@@ -194,6 +196,47 @@ def video_qa_collate(inputs):
     batch["qa_input_ids"] = _pad_rows(qa_ids, Lqa, PAD_ID, torch.long)
     batch["qa_pos_ids"] = torch.arange(Lqa, dtype=torch.long).clamp_(max=MAX_POS).unsqueeze(0)
     batch["qa_attn_masks"] = _pad_rows(qa_masks, Lqa, 0, torch.long)
+    return batch
+
+
+def violin_item(video, statements, targets, sep=2, vid=None):
+    """The statements about one video -> ViolinDataset.__getitem__'s 5-tuple (data/violin.py:66-110).
+    video: a video_item tuple; statements: token id lists (a statement and its paired one when sampled by statement);
+    targets: one truth value per statement.  Every statement gets its own copy of the video whose subtitles carry
+    `[sep] statement` behind their tokens (mask extended by ones)."""
+    ids, feats, masks, clip, clip_mask, n_subs, sub2frames = video
+    copies, q_ids, q_masks, labels = [], [], [], []
+    for toks, target in zip(statements, targets):
+        q = torch.tensor([sep] + list(toks), dtype=torch.long)
+        ones = torch.ones_like(q)
+        q_ids.append(q)
+        q_masks.append(ones)
+        copies.append(([torch.cat((t, q)) for t in ids], feats, [torch.cat((m, ones)) for m in masks],
+                       clip, clip_mask, n_subs, sub2frames))
+        labels.append(torch.tensor([1 if target else 0], dtype=torch.long))
+    return (copies, q_ids, q_masks, [vid] * len(copies), labels)
+
+
+def violin_collate(inputs):
+    """list of violin_item tuples -> the reference's batch (data/violin.py:118-141): video_collate over every statement's copy
+    (item-major), `targets` (S, 1), and the padded `[sep] statement` rows q_input_ids / q_pos_ids / q_attn_masks
+    (txt_input_collate, data/data.py:474-484)."""
+    copies = [c for it in inputs for c in it[0]]
+    q_ids = [t for it in inputs for t in it[1]]
+    q_masks = [t for it in inputs for t in it[2]]
+    batch = video_collate(copies)
+    Lq = max(t.shape[0] for t in q_ids)
+    batch["targets"] = torch.stack([t for it in inputs for t in it[4]])      # pad_sequence of one-element rows
+    batch["q_input_ids"] = _pad_rows(q_ids, Lq, PAD_ID, torch.long)
+    batch["q_pos_ids"] = torch.arange(Lq, dtype=torch.long).clamp_(max=MAX_POS).unsqueeze(0)
+    batch["q_attn_masks"] = _pad_rows(q_masks, Lq, 0, torch.long)
+    return batch
+
+
+def violin_eval_collate(inputs):
+    """list of (qids, violin_item tuple) -> violin_collate's batch plus `qids` (data/violin.py:163-170)."""
+    batch = violin_collate([item for _, item in inputs])
+    batch["qids"] = [q for ids, _ in inputs for q in ids]
     return batch
 
 

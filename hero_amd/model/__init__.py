@@ -6,3 +6,4 @@ from .model import HeroModel, HierarchicalVlModel, VideoModelConfig, VideoPreTra
 from .pretrain import HeroForPretraining  # noqa: F401
 from .vcmr import HeroForVcmr  # noqa: F401
 from .videoQA import HeroForVideoQA  # noqa: F401
+from .violin import HeroForViolin  # noqa: F401

@@ -28,7 +28,12 @@ TVQA_OPTS = dict(  # config/train-tvqa-8gpu.json: pass as `opts` with task='tvqa
     learning_rate=5e-5, lr_mul=10.0, weight_decay=0.01, optim="adamw", betas=[0.9, 0.98],
     grad_norm=1.0, warmup_steps=1000, num_train_steps=10000, gradient_accumulation_steps=2,
     train_batch_size=4, dropout=0.1, lw_st_ed=0.4)
+VIOLIN_OPTS = dict(  # config/train-violin-8gpu.json: pass as `opts` with task='violin'
+    learning_rate=3e-5, lr_mul=8.0, weight_decay=0.01, optim="adamw", betas=[0.9, 0.98],
+    grad_norm=1.0, warmup_steps=600, num_train_steps=6000, gradient_accumulation_steps=2,
+    train_batch_size=4, dropout=0.1)
 QA_TASKS = ("tvqa", "how2qa")
+HEAD_LR_TASKS = QA_TASKS + ("violin",)      # the task head's two optimiser groups keep lr * lr_mul (train_videoQA.py:185-190, train_violin.py:184)
 
 
 def qkv_groups(model):
@@ -88,7 +93,7 @@ class TrainStep:
         self.opts = SimpleNamespace(**{**TVR_OPTS, **(opts or {})})
         self.task = task
         self.optimizer = build_optimizer(model, self.opts)
-        if task in QA_TASKS:          # _set_lr / _fill_lr scale groups 0 and 1: optim/misc.py:17-22 puts the task head there
+        if task in HEAD_LR_TASKS:     # _set_lr / _fill_lr scale groups 0 and 1: optim/misc.py:17-22 puts the task head there
             head = {id(p) for n, p in model.named_parameters() if p.requires_grad and "v_encoder" not in n}
             if {id(p) for g in self.optimizer.param_groups[:2] for p in g["params"]} != head:
                 raise RuntimeError("TrainStep: build_optimizer no longer puts the task head's parameters in groups 0 and 1")
@@ -159,7 +164,7 @@ class TrainStep:
         lr = get_lr_sched(self.global_step, self.opts)
         for g in self.optimizer.param_groups:
             g["lr"] = lr                               # train_vcmr.py:248-249 (all groups)
-        if self.task in QA_TASKS:                      # train_videoQA.py:185-190: the task head's two groups keep lr_mul
+        if self.task in HEAD_LR_TASKS:                 # train_videoQA.py:185-190, train_violin.py:184: the task head's two groups keep lr_mul
             for g in self.optimizer.param_groups[:2]:
                 g["lr"] = lr * self.opts.lr_mul
         return lr
@@ -167,7 +172,7 @@ class TrainStep:
     def _fill_lr(self, lr):
         """The device-side learning rates the captured optimiser step reads (one per parameter group)."""
         self._lr_t.fill_(lr)
-        if self.task in QA_TASKS and self.opts.lr_mul != 1.0:
+        if self.task in HEAD_LR_TASKS and self.opts.lr_mul != 1.0:
             self._lr_t[:2].fill_(lr * self.opts.lr_mul)
 
     # ---- eager -------------------------------------------------------------------------------------

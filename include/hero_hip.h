@@ -43,6 +43,7 @@ const char* hero_last_error(void);
  * scalar arguments, no struct) - a backward-compatible addition, no struct moved, so the version stays.
  * Still 3: hero_moment_nms and hero_first_hit (what follows a search: NMS and recall ranks) were ADDED the same way.
  * Still 3: hero_qa_pool_fwd and hero_qa_pool_bwd (the video-QA head) were ADDED the same way.
+ * Still 3: hero_frame_pool_fwd/bwd and hero_bce_head_fwd/bwd (the VIOLIN head) were ADDED the same way.
  * INTEGRATION.md section 2 lists the breaks per version. */
 #define HERO_ABI_VERSION 3
 int hero_abi_version(void);
@@ -469,6 +470,30 @@ int hero_qa_pool_fwd(const void* x, const float* mask, const float* w_qa, const 
 int hero_qa_pool_bwd(const void* x, const float* mask, const float* w_qa, const float* w_se, const float* att_qa, const float* att_se,
                      const float* dqa, const float* dse, void* dx, float* dw_qa, float* dw_se,
                      int Nv, int A, int L, int Lt, int D, int dtype, hero_stream_t stream);
+
+/* VIOLIN head (HeroForViolin, model/violin.py:30-47 and 73-81).  Plain arguments, no struct: a backward-compatible  */
+/* addition, HERO_ABI_VERSION stays.                                                                                */
+/* Frame pool: x [S, Lt, D] dtype is the encoder output, read in place - rows l < L of every sequence are frames,  */
+/*   the statement tokens behind them are not touched.  mask [S, L] 0/1 fp32, w [D] fp32.                          */
+/*   att[s, l] = softmax_l(<x[s, l], w> * m + (1 - m) * -1e4)  [S, L] fp32;  pooled[s] = sum_l att x  [S, D] fp32. */
+/*   Backward: dx [S, Lt, D] dtype is written WHOLE (rows >= L as zeros: no memset by the caller); dw_part is      */
+/*   [S, D] per-sequence shares, OVERWRITTEN - the caller sums the rows in a fixed order (no fp atomics).          */
+/*   Envelope: S >= 0 (0: no launch), 1 <= L <= 256, L <= Lt <= 512, D % 4 == 0, 4 <= D <= 1024; else HERO_ERR_ARG.*/
+int hero_frame_pool_fwd(const void* x, const float* mask, const float* w, float* pooled, float* att,
+                        int S, int L, int Lt, int D, int dtype, hero_stream_t stream);
+int hero_frame_pool_bwd(const void* x, const float* mask, const float* w, const float* att, const float* dpooled,
+                        void* dx, float* dw_part, int S, int L, int Lt, int D, int dtype, hero_stream_t stream);
+/* Classifier tail: h [S, K] dtype (the MLP's LayerNorm output), w [K] fp32, b [1] fp32, targets [S] int64 0/1.    */
+/*   logits[s] = z = <h[s], w> + b;  term_s = min(softplus(t ? -z : z), 100), softplus(z) = max(z, 0) +            */
+/*   log1p(exp(-|z|));  loss[0] = mean_s term_s.  acc (may be NULL) is float[3] and is ACCUMULATED:                */
+/*   acc[0] += sum_s term_s, acc[1] += #{s: (z > 0) == (t == 1)} (z == 0 predicts 0), acc[2] += S.                 */
+/*   Backward: dloss is a DEVICE float[1]; dz_s = dloss * (sigmoid(z_s) - t_s) / S (also past the clamp, where the */
+/*   reference's gradient is 0); dh[s] = dz_s w [S, K] dtype, dw = sum_s dz_s h[s] [K] fp32, db = sum_s dz_s [1],  */
+/*   all OVERWRITTEN.  Sums over s run in a fixed order.  Envelope: S >= 1, K % 4 == 0, 4 <= K <= 2048.            */
+int hero_bce_head_fwd(const void* h, const float* w, const float* b, const long long* targets, float* logits, float* loss,
+                      float* acc, int S, int K, int dtype, hero_stream_t stream);
+int hero_bce_head_bwd(const void* h, const float* w, const float* logits, const long long* targets, const float* dloss,
+                      void* dh, float* dw, float* db, int S, int K, int dtype, hero_stream_t stream);
 
 /* F.normalize(x, dim=-1, eps) (model/pretrain.py:370-371): y = x / max(||x||_2, eps).           */
 /* rnorm[r] = 1/max(||x_r||, eps), negated when the clamp was active (backward then skips the   */
