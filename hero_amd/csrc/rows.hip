@@ -776,6 +776,7 @@ extern "C" int hero_fold_slabs(const float* slabs, int n_slabs, size_t stride, v
 
 extern "C" int hero_sumsq(const float* g, size_t n, float* sumsq, float* workspace, hero_stream_t stream) {
   HERO_REQUIRE(g && sumsq && workspace, "hero_sumsq: null pointer");
+  HERO_REQUIRE(((uintptr_t)g & 15) == 0, "hero_sumsq: g must be 16-byte aligned");
   if (n == 0) return HERO_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nb = grid_for(n >> 2);
@@ -786,6 +787,7 @@ extern "C" int hero_sumsq(const float* g, size_t n, float* sumsq, float* workspa
 
 extern "C" int hero_adamw(const HeroAdamW* a, hero_stream_t stream) {
   HERO_REQUIRE(a && a->p && a->g && a->m && a->v, "hero_adamw: null pointer");
+  HERO_REQUIRE((((uintptr_t)a->p | (uintptr_t)a->g | (uintptr_t)a->m | (uintptr_t)a->v) & 15) == 0 && ((uintptr_t)a->shadow & 7) == 0, "hero_adamw: p, g, m, v must be 16-byte aligned (shadow: 8)");
   HERO_REQUIRE(a->step >= 1, "hero_adamw: step must be >= 1");
   if (a->n == 0) return HERO_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);

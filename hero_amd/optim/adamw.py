@@ -59,6 +59,8 @@ class AdamW(Optimizer):
             for p in g["params"]:
                 if p.grad is not None:
                     gr = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                    if gr.data_ptr() & 15:                  # hero_sumsq reads float4: a misaligned view is copied
+                        gr = gr.clone()
                     L.check(L.lib().hero_sumsq(L.ptr(gr), gr.numel(), L.ptr(out), L.ptr(ws), L.stream()))
         return out
 

@@ -355,7 +355,8 @@ int hero_add(const void* a, const void* b, void* y, size_t n, int dtype, hero_st
 /* ------------------------------------------------------------------------------------------ */
 /* sumsq[0] += sum g^2 (fp32 device scalar; caller zeroes it).  Deterministic (fixed summation  */
 /* order): data-parallel replicas must derive the SAME clipping factor from the same gradients.  */
-/* workspace: >= 2048 floats of device scratch.                                                  */
+/* workspace: >= 2048 floats of device scratch.  `g` must be 16-byte aligned (it is read as      */
+/* float4 with no scalar fallback); anything else is rejected with HERO_ERR_ARG before a launch. */
 int hero_sumsq(const float* g, size_t n, float* sumsq, float* workspace, hero_stream_t stream);
 typedef struct HeroAdamW {
   float* p;
@@ -370,6 +371,9 @@ typedef struct HeroAdamW {
   float grad_scale;        /* extra multiplier on g (e.g. 1/world_size); 1 = none               */
   void* shadow;            /* optional bf16 copy of p refreshed in the same pass               */
 } HeroAdamW;
+/* p, g, m, v must be 16-byte aligned and shadow 8-byte aligned (float4 / packed-bf16 accesses    */
+/* with no scalar fallback); anything else is rejected with HERO_ERR_ARG before a launch.  The    */
+/* multi-tensor form below tests its pointers itself and falls back to scalar accesses.          */
 int hero_adamw(const HeroAdamW* a, hero_stream_t stream);
 
 /* Multi-tensor form: ONE launch updates every tensor in a device-resident descriptor table (one
