@@ -10,6 +10,8 @@ Host half - same names, inputs and outputs as the reference, so a reference Data
     video_qa_collate  video_qa_collate                   data/videoQA.py:155-182 (pinned by tests/golden/case_videoqa.npz)
     violin_item     ViolinDataset.__getitem__            data/violin.py:66-110
     violin_collate / violin_eval_collate                 data/violin.py:118-141, 163-170 (pinned by tests/golden/case_violin.npz)
+    tvc_st_ed_label, tvc_item, tvc_val_item              data/tvc.py:39-49, 100-138, 170-190, 246-265
+    tvc_collate / tvc_val_collate / tvc_eval_collate     data/tvc.py:140-161, 192-218, 267-291 (+ `cap_frame_index`)
 They are written over LENGTH arrays (one allocation per output, no pad_sequence / per-row python tensors) and also
 return the handful of int32 length arrays (`batch["lengths"]`) from which the device half rebuilds every index tensor.
 
@@ -238,6 +240,102 @@ def violin_eval_collate(inputs):
     batch = violin_collate([item for _, item in inputs])
     batch["qids"] = [q for ids, _ in inputs for q in ids]
     return batch
+
+
+def tvc_st_ed_label(ts, nframes, frame_interval=1.5):
+    """[start s, end s] -> the frames [st, ed) of a caption's segment, TvcTrainDataset.get_st_ed_label (data/tvc.py:119-138):
+    Python `round` (half to even) on the end, at least one frame, both clamped at the video's end - so a caption that starts
+    at or past the end gets the EMPTY segment (nframes, nframes)."""
+    import math
+    st = min(math.floor(ts[0] / frame_interval), nframes)
+    return st, min(max(round(ts[1] / frame_interval), st + 1), nframes)
+
+
+def tvc_frame_index(clip_ranges, n_frames):
+    """clip_ranges: per video the (st, ed) of its captions -> int32 [Ncap, Lv], Lv = the longest segment (at least 1): the
+    flat row video * n_frames + frame behind every position of the zero-padded segments of model/tvc.py:219-238, -1 = pad."""
+    segs = [(v, st, ed) for v, rs in enumerate(clip_ranges) for st, ed in rs]
+    Lv = max([ed - st for _, st, ed in segs] + [1])
+    idx = torch.full((len(segs), Lv), -1, dtype=torch.int32)
+    for r, (v, st, ed) in enumerate(segs):
+        if not 0 <= st <= ed <= n_frames:
+            raise IndexError("tvc_frame_index: segment [%d, %d) outside a video of %d frames" % (st, ed, n_frames))
+        idx[r, :ed - st] = torch.arange(v * n_frames + st, v * n_frames + ed, dtype=torch.int32)
+    return idx
+
+
+def tvc_item(video, captions, bos=0, eos=2, max_txt_len=-1, frame_interval=1.5):
+    """One video and its captions -> TvcTrainDataset.__getitem__'s (video, clip_ranges, cap_inputs) (data/tvc.py:100-114 with
+    CaptionTokLmdb.get_caption, data/tvc.py:39-49).  video: a video_item tuple; captions: [(token id list, [start s, end s])]."""
+    nframes = len(video[4])
+    clip_ranges, cap_inputs = [], []
+    for toks, ts in captions:
+        input_ids, tgt_ids = [bos] + list(toks), list(toks) + [eos]
+        if max_txt_len != -1:
+            input_ids, tgt_ids = input_ids[:max_txt_len], tgt_ids[:max_txt_len]
+        st, ed = tvc_st_ed_label(ts, nframes, frame_interval)
+        clip_ranges.append((st, ed))
+        cap_inputs.append((torch.tensor(input_ids, dtype=torch.long), torch.tensor(tgt_ids, dtype=torch.long),
+                           torch.ones(ed - st, dtype=torch.long)))
+    return (video, clip_ranges, cap_inputs)
+
+
+def tvc_val_item(video, clips, vid, frame_interval=1.5, with_gts=True):
+    """One video and its clips -> TvcValDataset / TvcEvalDataset.__getitem__ (data/tvc.py:170-190, 246-265).
+    clips: [(clip id, [start s, end s], ground-truth text)] (the text is ignored without with_gts)."""
+    nframes = len(video[4])
+    ranges = [tvc_st_ed_label(c[1], nframes, frame_interval) for c in clips]
+    masks = [torch.ones(ed - st, dtype=torch.long) for st, ed in ranges]
+    meta = (vid, [c[0] for c in clips], [c[1] for c in clips]) + (([c[2] for c in clips],) if with_gts else ())
+    return (video, ranges, masks, meta)
+
+
+def _tvc_video_part(batch, inputs):
+    batch["clip_ranges"] = tuple(tuple(it[1]) for it in inputs)
+    batch.update(video_collate([it[0] for it in inputs]))
+    # hero_amd only: the segments' rows as a tensor, so that a captured step reads them from the device
+    batch["cap_frame_index"] = tvc_frame_index(batch["clip_ranges"], batch["c_v_feats"].shape[1])
+    return batch
+
+
+def tvc_collate(inputs):
+    """list of tvc_item tuples -> the reference's training batch (TvcTrainDataset.collate, data/tvc.py:140-161): cap_input_ids
+    padded with 1, cap_tgt_ids padded with -1, cap_pos_ids (1, Lt), cap_attn_mask over the segment frames, clip_ranges as
+    tuples, the video_collate keys - plus the one extra key `cap_frame_index` (tvc_frame_index)."""
+    caps = [c for it in inputs for c in it[2]]
+    Lt = max(c[0].shape[0] for c in caps)
+    Lv = max(c[2].shape[0] for c in caps)
+    batch = {"cap_input_ids": _pad_rows([c[0] for c in caps], Lt, PAD_ID, torch.long),
+             "cap_pos_ids": torch.arange(0, Lt, dtype=torch.long).unsqueeze(0),
+             "cap_tgt_ids": _pad_rows([c[1] for c in caps], Lt, -1, torch.long),
+             "cap_attn_mask": _pad_rows([c[2] for c in caps], Lv, 0, torch.long)}
+    return _tvc_video_part(batch, inputs)
+
+
+def tvc_val_collate(inputs, with_gts=True):
+    """list of tvc_val_item tuples -> TvcValDataset.collate's batch (data/tvc.py:192-218): cap_attn_mask, clip_ranges, the
+    video keys and the meta lists vid_names / clip_ids / all_ts / gts - plus `cap_frame_index`."""
+    masks = [m for it in inputs for m in it[2]]
+    Lv = max(m.shape[0] for m in masks)
+    batch = _tvc_video_part({"cap_attn_mask": _pad_rows(masks, Lv, 0, torch.long)}, inputs)
+    vids, clip_ids, all_ts, all_gts = [], [], [], []
+    for it in inputs:
+        meta = it[3]
+        for j, (cid, ts) in enumerate(zip(meta[1], meta[2])):
+            vids.append(meta[0])
+            clip_ids.append(int(cid))
+            all_ts.append(ts)
+            if with_gts:
+                all_gts.append(meta[3][j])
+    batch.update(vid_names=vids, clip_ids=clip_ids, all_ts=all_ts)
+    if with_gts:
+        batch["gts"] = all_gts
+    return batch
+
+
+def tvc_eval_collate(inputs):
+    """TvcEvalDataset.collate (data/tvc.py:267-291): tvc_val_collate without the ground-truth texts."""
+    return tvc_val_collate(inputs, with_gts=False)
 
 
 def _lengths(num_subs, sub2frm, sub_nfrm, sub_ntok, n_frames):

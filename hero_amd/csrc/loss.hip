@@ -9,6 +9,7 @@
 // them once more and writes the gradient in the logits' dtype (may alias the logits):
 //   loss_r = lse_r - x[r, y_r],   dx[r, c] = (exp(x[r, c] - lse_r) - [c == y_r]) * g_r * inv_temp
 // with x = logits * inv_temp; rows whose label equals ignore_index give loss 0 and a zero gradient row.
+#include <math.h>
 #include "common.h"
 
 namespace hero {
@@ -103,6 +104,126 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(HeroCrossEntropy a) {
   }
 }
 
+// ---- label-smoothed loss of the captioning decoder (model/tvc.py:19-64) -------------------------
+// KL(smoothed one-hot || softmax(x)) of a row with label t, C = cols, s = eps / (C - 1), conf = 1 - eps, in closed form:
+//   loss = H0 - (conf - s) (x_t - lse) - s (sum_c x_c - C lse),   H0 = conf ln conf + (C - 1) s ln s   (0 ln 0 = 0)
+//   dx_c = (softmax(x)_c - s - (conf - s) [c == t]) * upstream
+// so no [rows, C] target matrix exists.  Forward: one pass over the row (online max / sum of exponentials as above, plus
+// sum_c x_c in fp32), then ONE workgroup folds the row losses and counts the valid rows in a fixed order into a device pair.
+// Backward: upstream is a device scalar (times an optional per-row factor); in mean mode it is divided by the valid count
+// read from that pair - no host synchronisation.  Zero valid rows: loss 0, zero gradients.
+struct SmoothCe {
+  const void* logits;
+  const long long* labels;
+  float *loss, *lse, *sum_cnt;
+  const float *dloss, *dloss_rows, *mean_cnt;
+  void* dlogits;
+  int rows, cols, ld;
+  long long ignore_index;
+  double cms, s, h0;                                  // conf - s, s, H0
+};
+
+// ms_merge with the accurate exponential: the loss is judged at a few 2^-24
+__device__ __forceinline__ void ms_merge_acc(float& m, float& s, float m2, float s2) {
+  const float mx = fmaxf(m, m2);
+  s = s * expf(m - mx) + s2 * expf(m2 - mx);
+  m = mx;
+}
+__device__ __forceinline__ float sum8(const float (&v)[8]) { return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7])); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void smooth_ce_fwd_kernel(SmoothCe a) {
+  __shared__ float sm[4], ss[4], sx[4];
+  const int row = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const T* x = static_cast<const T*>(a.logits) + (size_t)row * a.ld;
+  float m = -3.0e38f, s = 0.f, tot = 0.f;
+  const int vec_end = ((a.ld & 7) == 0) ? (a.cols & ~7) : 0;
+  for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
+    float v[8];
+    ld8<T>(x + c, v);
+    float mx = v[0];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) mx = fmaxf(mx, v[k]);
+    float e = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) e += expf(v[k] - mx);
+    ms_merge_acc(m, s, mx, e);
+    tot += sum8(v);
+  }
+  for (int c = vec_end + threadIdx.x; c < a.cols; c += 256) {
+    const float v = ld1<T>(x + c);
+    ms_merge_acc(m, s, v, 1.f);
+    tot += v;
+  }
+  const float wm = wave_max(m);
+  s = wave_sum(s * expf(m - wm));
+  tot = wave_sum(tot);
+  if (lane == 0) { sm[wave] = wm; ss[wave] = s; sx[wave] = tot; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float M = sm[0], S = ss[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) ms_merge_acc(M, S, sm[w], ss[w]);
+    const float lse = M + logf(S);
+    const long long y = a.labels[row];
+    a.lse[row] = lse;
+    float loss = 0.f;
+    if (!(y == a.ignore_index || y < 0 || y >= a.cols)) {
+      const double all = ((double)sx[0] + (double)sx[1]) + ((double)sx[2] + (double)sx[3]) - (double)a.cols * (double)lse;
+      loss = (float)(a.h0 - a.cms * ((double)ld1<T>(x + y) - (double)lse) - a.s * all);
+    }
+    a.loss[row] = loss;
+  }
+}
+
+// sum_cnt = (sum of the row losses, number of valid rows): one workgroup, strided partial sums, a fixed tree
+__global__ __launch_bounds__(256) void smooth_ce_fold_kernel(SmoothCe a) {
+  __shared__ float ps[256], pc[256];
+  float s = 0.f, c = 0.f;
+  for (int r = threadIdx.x; r < a.rows; r += 256) {
+    const long long y = a.labels[r];
+    if (!(y == a.ignore_index || y < 0 || y >= a.cols)) { s += a.loss[r]; c += 1.f; }
+  }
+  ps[threadIdx.x] = s;
+  pc[threadIdx.x] = c;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) { ps[threadIdx.x] += ps[threadIdx.x + w]; pc[threadIdx.x] += pc[threadIdx.x + w]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { a.sum_cnt[0] = ps[0]; a.sum_cnt[1] = pc[0]; }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void smooth_ce_bwd_kernel(SmoothCe a) {
+  const int row = blockIdx.x;
+  const T* x = static_cast<const T*>(a.logits) + (size_t)row * a.ld;
+  T* dx = static_cast<T*>(a.dlogits) + (size_t)row * a.ld;
+  const long long y = a.labels[row];
+  const bool live = !(y == a.ignore_index || y < 0 || y >= a.cols);
+  const float lse = a.lse[row];
+  float g = 0.f;
+  if (live) {
+    g = a.dloss[0];
+    if (a.dloss_rows) g *= a.dloss_rows[row];
+    if (a.mean_cnt) g /= fmaxf(a.mean_cnt[1], 1.f);
+  }
+  const float s = (float)a.s, cms = (float)a.cms;
+  const int vec_end = ((a.ld & 7) == 0) ? (a.cols & ~7) : 0;
+  for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
+    float v[8];
+    ld8<T>(x + c, v);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = live ? ((expf(v[k] - lse) - s) - ((long long)(c + k) == y ? cms : 0.f)) * g : 0.f;
+    st8<T>(dx + c, v);
+  }
+  for (int c = vec_end + threadIdx.x; c < a.ld; c += 256) {
+    float v = 0.f;
+    if (live && c < a.cols) v = ((expf(ld1<T>(x + c) - lse) - s) - ((long long)c == y ? cms : 0.f)) * g;
+    st1<T>(dx + c, v);                                               // padding columns get a zero gradient
+  }
+}
+
 }  // namespace
 }  // namespace hero
 
@@ -136,4 +257,51 @@ extern "C" int hero_cross_entropy_bwd(const HeroCrossEntropy* a, hero_stream_t s
   if (a->dtype == HERO_BF16) hipLaunchKernelGGL(ce_bwd_kernel<bf16_t>, dim3(a->rows), dim3(256), 0, s, *a);
   else hipLaunchKernelGGL(ce_bwd_kernel<float>, dim3(a->rows), dim3(256), 0, s, *a);
   return check_launch("hero_cross_entropy_bwd");
+}
+
+static int check_smooth(const char* what, const void* logits, const long long* labels, const float* lse, int rows, int cols, int ld, int dtype,
+                        double eps) {
+  HERO_REQUIRE(logits && labels && lse, "%s: null pointer", what);
+  HERO_REQUIRE(rows >= 0 && cols >= 2 && ld >= cols, "%s: bad dims rows=%d cols=%d ld=%d", what, rows, cols, ld);
+  HERO_REQUIRE(dtype == HERO_F32 || dtype == HERO_BF16, "%s: bad dtype %d", what, dtype);
+  HERO_REQUIRE(eps > 0.0 && eps <= 1.0, "%s: smoothing must be in (0, 1], got %g", what, eps);
+  HERO_REQUIRE((((uintptr_t)logits) & 15) == 0, "%s: logits must be 16-byte aligned", what);
+  return HERO_OK;
+}
+
+static void smooth_consts(SmoothCe& a, double eps) {
+  const double C = a.cols, e = eps, s = e / (C - 1.0), conf = 1.0 - e;
+  a.s = s;
+  a.cms = conf - s;
+  a.h0 = (conf > 0.0 ? conf * log(conf) : 0.0) + (C - 1.0) * s * log(s);
+}
+
+extern "C" int hero_smooth_ce_fwd(const void* logits, const long long* labels, float* loss, float* lse, float* sum_cnt, int rows, int cols,
+                                  int ld, int dtype, double eps, long long ignore_index, hero_stream_t stream) {
+  if (const int rc = check_smooth("hero_smooth_ce_fwd", logits, labels, lse, rows, cols, ld, dtype, eps)) return rc;
+  HERO_REQUIRE(loss && sum_cnt, "hero_smooth_ce_fwd: loss and sum_cnt required");
+  SmoothCe a = {logits, labels, loss, lse, sum_cnt, nullptr, nullptr, nullptr, nullptr, rows, cols, ld, ignore_index, 0.0, 0.0, 0.0};
+  smooth_consts(a, eps);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (rows > 0) {
+    if (dtype == HERO_BF16) hipLaunchKernelGGL(smooth_ce_fwd_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(smooth_ce_fwd_kernel<float>, dim3(rows), dim3(256), 0, s, a);
+  }
+  hipLaunchKernelGGL(smooth_ce_fold_kernel, dim3(1), dim3(256), 0, s, a);     // rows == 0: the pair is (0, 0)
+  return check_launch("hero_smooth_ce_fwd");
+}
+
+extern "C" int hero_smooth_ce_bwd(const void* logits, const long long* labels, const float* lse, const float* dloss, const float* dloss_rows,
+                                  const float* mean_cnt, void* dlogits, int rows, int cols, int ld, int dtype, double eps,
+                                  long long ignore_index, hero_stream_t stream) {
+  if (const int rc = check_smooth("hero_smooth_ce_bwd", logits, labels, lse, rows, cols, ld, dtype, eps)) return rc;
+  HERO_REQUIRE(dloss && dlogits && (((uintptr_t)dlogits) & 15) == 0, "hero_smooth_ce_bwd: dloss / dlogits required (16-byte aligned)");
+  if (rows == 0) return HERO_OK;
+  SmoothCe a = {logits, labels, nullptr, const_cast<float*>(lse), nullptr, dloss, dloss_rows, mean_cnt, dlogits, rows, cols, ld, ignore_index,
+                0.0, 0.0, 0.0};
+  smooth_consts(a, eps);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == HERO_BF16) hipLaunchKernelGGL(smooth_ce_bwd_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(smooth_ce_bwd_kernel<float>, dim3(rows), dim3(256), 0, s, a);
+  return check_launch("hero_smooth_ce_bwd");
 }

@@ -7,3 +7,4 @@ from .pretrain import HeroForPretraining  # noqa: F401
 from .vcmr import HeroForVcmr  # noqa: F401
 from .videoQA import HeroForVideoQA  # noqa: F401
 from .violin import HeroForViolin  # noqa: F401
+from .tvc import HeroForTvc, TvcGenerator  # noqa: F401

@@ -1,0 +1,303 @@
+"""HERO for video captioning, TVC (reference: model/tvc.py).
+
+The hierarchical encoder produces the frame representations of every video; the frames of each caption's segment are
+gathered into a zero-padded [Ncap, Lv, D] tensor, and a BERT decoder (causal self-attention, attention over the segment's
+frames, feed-forward; the reference's module names, `intermidiate` included) predicts the caption's tokens through the
+word-embedding table it shares with the encoder.  Both attentions run on one HIP kernel family
+(hero_amd.tvc.DecAttentionFn) and the label-smoothed loss over the vocabulary is one kernel each way
+(hero_amd.tvc.SmoothCeFn): no [rows, vocab] target matrix, no [N, H, Lq, Lk] probability tensor."""
+import math
+
+import torch
+from torch import nn
+from torch.nn import functional as F
+
+from .. import functional as HF
+from .. import tvc as T
+from .layers import BertIntermediate, BertLayerNorm, BertOutput, BertSelfAttention, BertSelfOutput, _drop
+from .model import HeroModel
+
+
+class BertDecEncAttention(BertSelfAttention):
+    """model/tvc.py:67-104: query from the decoder states, key / value from the encoder outputs (parameter holder; the
+    decoder layer runs it through hero_amd.tvc.DecAttentionFn or the PyTorch formulation)."""
+
+
+def _attention_torch(att, x, kv, mask_add, drop_p, training):
+    """BertSelfAttention / BertDecEncAttention.forward of the reference, op for op.  mask_add broadcasts over the scores."""
+    H = att.num_attention_heads
+
+    def split(t):
+        return t.view(t.shape[0], t.shape[1], H, att.attention_head_size).permute(0, 2, 1, 3)
+    q, k, v = split(att.query(x)), split(att.key(kv)), split(att.value(kv))
+    scores = torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(att.attention_head_size)
+    if mask_add is not None:
+        scores = scores + mask_add
+    probs = F.dropout(torch.softmax(scores, dim=-1), drop_p, training)
+    ctx = torch.matmul(probs, v).permute(0, 2, 1, 3).contiguous()
+    return ctx.view(ctx.shape[0], ctx.shape[1], att.all_head_size)
+
+
+def _add_norm_torch(mod, hidden, residual):
+    """BertSelfOutput / BertOutput.forward of the reference."""
+    h = F.dropout(mod.dense(hidden), mod.dropout.p, mod.training)
+    ln = mod.LayerNorm
+    return F.layer_norm(h + residual, ln.normalized_shape, ln.weight, ln.bias, ln.eps)
+
+
+class BertDecoderLayer(nn.Module):
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        self.self_attention = BertSelfAttention(config)
+        self.add_norm_1 = BertSelfOutput(config)
+        self.dec_enc_attention = BertDecEncAttention(config)
+        self.add_norm_2 = BertSelfOutput(config)
+        self.intermidiate = BertIntermediate(config)
+        self.add_norm_3 = BertOutput(config)
+
+    def forward(self, dec_hidden_states, enc_outputs, enc_mask_add):
+        """Fused: dec_hidden_states (N, Lt, D) and enc_outputs (N, Lv, D) in the compute dtype, enc_mask_add (N, Lv) fp32."""
+        sa, ca, dev = self.self_attention, self.dec_enc_attention, dec_hidden_states.device
+        a = T.DecAttentionFn.apply(dec_hidden_states, None, None, sa.num_attention_heads, _drop(sa.dropout, dev), *sa.qkv_params())
+        a = self.add_norm_1(a, dec_hidden_states)
+        c = T.DecAttentionFn.apply(a, enc_outputs, enc_mask_add, ca.num_attention_heads, _drop(ca.dropout, dev), *ca.qkv_params())
+        c = self.add_norm_2(c, a)
+        o = self.add_norm_3
+        return HF.FfnBlockFn.apply(c, o.LayerNorm.eps, _drop(o.dropout, dev), self.intermidiate.dense.weight,
+                                   self.intermidiate.dense.bias, o.dense.weight, o.dense.bias, o.LayerNorm.weight, o.LayerNorm.bias)
+
+    def forward_torch(self, dec_hidden_states, enc_outputs, enc_mask, tri_mask):
+        """model/tvc.py:118-154 in PyTorch ops; enc_mask (N, 1, 1, Lv) and tri_mask (1, 1, Lt, Lt) additive."""
+        sa, ca = self.self_attention, self.dec_enc_attention
+        a = _attention_torch(sa, dec_hidden_states, dec_hidden_states, tri_mask, sa.dropout.p, self.training)
+        a = _add_norm_torch(self.add_norm_1, a, dec_hidden_states)
+        c = _attention_torch(ca, a, enc_outputs, enc_mask, ca.dropout.p, self.training)
+        c = _add_norm_torch(self.add_norm_2, c, a)
+        h = F.gelu(self.intermidiate.dense(c))
+        return _add_norm_torch(self.add_norm_3, h, c)
+
+
+class BertDecoder(nn.Module):
+    def __init__(self, config):
+        super().__init__()
+        self.layer = nn.ModuleList([BertDecoderLayer(config) for _ in range(config.num_hidden_layers)])
+        tri_mask = torch.tril(torch.ones(1024, 1024), diagonal=0)
+        self.register_buffer("tri_mask", (1.0 - tri_mask) * -10000.0)          # in the reference's state dict
+
+    def forward(self, dec_hidden_states, enc_outputs, enc_mask_add):
+        for layer in self.layer:
+            dec_hidden_states = layer(dec_hidden_states, enc_outputs, enc_mask_add)
+        return dec_hidden_states
+
+    def forward_torch(self, dec_hidden_states, enc_outputs, enc_mask):
+        len_ = dec_hidden_states.size(1)
+        tri_mask = self.tri_mask[:len_, :len_].unsqueeze(0).unsqueeze(1).to(dec_hidden_states)
+        enc_mask = (1.0 - enc_mask.unsqueeze(1).unsqueeze(2).to(dec_hidden_states)) * -10000.0
+        for layer in self.layer:
+            dec_hidden_states = layer.forward_torch(dec_hidden_states, enc_outputs, enc_mask, tri_mask)
+        return dec_hidden_states
+
+
+def smooth_loss_torch(output, target, eps, vocab_size, ignore_index=-1):
+    """LabelSmoothingLoss.forward (model/tvc.py:42-64), reduction 'none': the losses of the valid rows."""
+    valid = target != ignore_index
+    target = target[valid]
+    output = torch.log_softmax(output[valid], dim=-1)
+    model_prob = torch.full((1, vocab_size), eps / (vocab_size - 1), dtype=output.dtype, device=output.device).repeat(target.size(0), 1)
+    model_prob.scatter_(1, target.unsqueeze(1), 1.0 - eps)
+    return F.kl_div(output, model_prob, reduction="none").sum(dim=1)
+
+
+class LabelSmoothingLoss(nn.Module):
+    """model/tvc.py:19-64.  Keeps the reference's `one_hot` buffer (1, vocab) because it is in the reference's state dict; the
+    fused path never expands it to (rows, vocab) - hero_smooth_ce_* use the closed form."""
+
+    def __init__(self, label_smoothing, tgt_vocab_size, ignore_index=-100, reduction="none"):
+        assert 0.0 < label_smoothing <= 1.0
+        super().__init__()
+        self.ignore_index, self.reduction = ignore_index, reduction
+        self.register_buffer("one_hot", torch.full((1, tgt_vocab_size), label_smoothing / (tgt_vocab_size - 1)))
+        self.label_smoothing, self.confidence = label_smoothing, 1.0 - label_smoothing
+
+    def forward(self, output, target):
+        loss = smooth_loss_torch(output, target, self.label_smoothing, output.shape[-1], self.ignore_index)
+        return loss.mean() if self.reduction == "mean" else loss.sum() if self.reduction == "sum" else loss
+
+
+class HeroForTvc(HeroModel):
+    def __init__(self, config, vfeat_dim, max_frm_seq_len, lsr=0.1):
+        super().__init__(config, vfeat_dim, max_frm_seq_len)
+        self.config = config
+        d = config.d_config
+        if d is None:
+            raise ValueError("HeroForTvc: the model config has no d_config (config/hero_tvc.json)")
+        if d.hidden_size != config.f_config.hidden_size:
+            raise ValueError("HeroForTvc: the decoder shares the encoder's word embedding, hidden sizes must agree")
+        self.position_embeddings = nn.Embedding(d.max_position_embeddings, d.hidden_size)
+        self.emb_LayerNorm = BertLayerNorm(d.hidden_size, eps=1e-5)
+        self.decoder = BertDecoder(d)
+        if not 0.0 <= lsr <= 1.0:
+            raise ValueError("HeroForTvc: label smoothing must be in [0, 1]")
+        self.lsr = float(lsr)
+        if lsr > 0:
+            self.loss_func = LabelSmoothingLoss(lsr, config.f_config.vocab_size, ignore_index=-1, reduction="none")
+        else:
+            self.loss_func = nn.CrossEntropyLoss(ignore_index=-1, reduction="none")
+        self._cap_index = {}
+        self.v_encoder.initialize()
+
+    fused_decoder = True    # decoder attentions and the smoothed loss on the HIP kernels (hero_dec_attention_*, hero_smooth_ce_*);
+                            # False / shapes outside their envelope / CPU tensors: the PyTorch formulation below
+    max_lq, max_lk = T.MAX_LQ, T.MAX_LK       # Python-side limits of the fused route (never above the kernels' envelope)
+
+    # ---- encoder side --------------------------------------------------------------------------------------------------
+    def _cap_frame_index(self, batch, n_frames, device):
+        """Flat row of the (B * n_frames) frame representations behind every position of the padded segments, -1 = pad:
+        the batch's own device tensor `cap_frame_index` (hero_amd.collate.tvc_collate) or built from `clip_ranges` once."""
+        idx = batch.get("cap_frame_index") if hasattr(batch, "get") else None
+        if idx is not None:
+            return idx
+        ranges = batch["clip_ranges"]
+        key = (id(ranges), n_frames, str(device))
+        hit = self._cap_index.get(key)
+        if hit is None or hit[0] is not ranges:
+            from ..collate import tvc_frame_index
+            if len(self._cap_index) > 64:
+                self._cap_index.clear()
+            hit = (ranges, tvc_frame_index(ranges, n_frames).to(device))
+            self._cap_index[key] = hit
+        return hit[1]
+
+    def encode(self, batch):
+        """(Ncap, Lv, D): frame_embeddings[i, st:ed] of every caption, zero-padded (model/tvc.py:219-238)."""
+        frame_embeddings = self.v_encoder(batch, "repr")
+        B, NF, D = frame_embeddings.shape
+        idx = self._cap_frame_index(batch, NF, frame_embeddings.device)
+        n_cap, Lv = idx.shape
+        if not frame_embeddings.is_cuda:
+            flat = F.pad(frame_embeddings.reshape(B * NF, D), (0, 0, 0, 1))      # row -1: zeros
+            return flat[idx.reshape(-1).long()].view(n_cap, Lv, D)
+        return HF.ExpandRowsFn.apply(frame_embeddings.reshape(B * NF, D), idx).view(n_cap, Lv, D)
+
+    # ---- decoder side --------------------------------------------------------------------------------------------------
+    def _fused(self, encoder_outputs, caption_ids):
+        f_enc = self.v_encoder.f_encoder
+        if f_enc.vocab_pad:
+            raise ValueError("HeroForTvc: the vocabulary (%d) is not a multiple of 8; the reference's own "
+                             ".view(-1, vocab_size) of the padded prediction scores fails there too"
+                             % self.config.f_config.vocab_size)
+        Lt, Lv = caption_ids.shape[1], encoder_outputs.shape[1]
+        return (self.fused_decoder and encoder_outputs.is_cuda and Lt <= self.max_lq and Lv <= self.max_lk and Lt <= self.max_lk
+                and T.in_envelope(HF.compute_dtype(), Lt, Lv) and T.in_envelope(HF.compute_dtype(), Lt, Lt))
+
+    def _decoder_states(self, encoder_outputs, encoder_masks, caption_ids, pos_ids, fused):
+        emb = self.v_encoder.f_encoder.embeddings
+        N, Lt = caption_ids.shape
+        if fused:
+            from .embed import _row_index
+            wid, pid = _row_index(caption_ids, N, Lt), _row_index(pos_ids, N, Lt)
+            x = HF.embed_ln(None, self.emb_LayerNorm.weight, self.emb_LayerNorm.bias, self.emb_LayerNorm.eps, None,
+                            HF.compute_dtype(), tables=(emb.word_embeddings.weight, self.position_embeddings.weight),
+                            idxs=(wid, pid), skip_idx=(emb.padding_idx, -1)).view(N, Lt, -1)
+            enc = HF.cast(encoder_outputs, HF.compute_dtype())
+            return self.decoder(x, enc, HF.as_mask_add(encoder_masks, N, encoder_outputs.shape[1]))
+        x = emb.word_embeddings(caption_ids) + self.position_embeddings(pos_ids)
+        ln = self.emb_LayerNorm
+        x = F.layer_norm(x, ln.normalized_shape, ln.weight, ln.bias, ln.eps)
+        return self.decoder.forward_torch(x, encoder_outputs.to(x.dtype), encoder_masks)
+
+    def _scores_torch(self, states):
+        """BertLMPredictionHead.forward of the reference in PyTorch ops (the tied projection)."""
+        head = self.v_encoder.f_encoder.lm_head
+        h = F.gelu(head.dense(states))
+        h = F.layer_norm(h, head.LayerNorm.normalized_shape, head.LayerNorm.weight, head.LayerNorm.bias, head.LayerNorm.eps)
+        return F.linear(h, head.decoder.weight, head.bias)
+
+    def decode(self, encoder_outputs, encoder_masks, caption_ids, pos_ids, label_ids, compute_loss=True):
+        """model/tvc.py:240-266.  With compute_loss the reference's loss VECTOR: the smoothed losses of the valid positions
+        (boolean compaction: not capturable) or, with lsr == 0, plain cross-entropy over ALL positions with zeros at the ignored
+        ones - the reference's `.mean()` therefore divides by different counts in the two modes."""
+        fused = self._fused(encoder_outputs, caption_ids)
+        states = self._decoder_states(encoder_outputs, encoder_masks, caption_ids, pos_ids, fused)
+        V = self.config.f_config.vocab_size
+        if not fused:
+            scores = self._scores_torch(states)
+            if not compute_loss:
+                return scores
+            flat, labels = scores.view(-1, V), label_ids.reshape(-1)
+            return self.loss_func(flat, labels)
+        head = self.v_encoder.f_encoder.lm_head
+        if not compute_loss:
+            return head(states).view(states.shape[0], states.shape[1], V)
+        logits, labels = head(states.reshape(-1, states.shape[-1]), raw=True), label_ids.reshape(-1)
+        if self.lsr > 0:
+            rows, _ = T.smooth_ce(logits, labels, self.lsr, ncols=V, ignore_index=-1)
+            return rows[labels != -1]
+        return HF.cross_entropy(logits, labels, ncols=V, ignore_index=-1)
+
+    def forward(self, batch, mode="train", compute_loss=True, task=None):
+        if task not in (None, "tvc"):
+            raise ValueError(f"Unrecognized task: {task}")
+        encoder_outputs = self.encode(batch)
+        return self.decode(encoder_outputs, batch["cap_attn_mask"], batch["cap_input_ids"], batch["cap_pos_ids"],
+                           batch.get("cap_tgt_ids"), compute_loss)
+
+    def caption_loss(self, batch):
+        """The scalar train_tvc.py:172-173 trains on - `forward(batch).mean()` - without the boolean compaction: the mean over
+        the valid positions (lsr > 0) or over all positions (lsr == 0) is taken on the device, nothing synchronises."""
+        encoder_outputs = self.encode(batch)
+        caption_ids, label_ids = batch["cap_input_ids"], batch["cap_tgt_ids"]
+        if not self._fused(encoder_outputs, caption_ids):
+            return self.decode(encoder_outputs, batch["cap_attn_mask"], caption_ids, batch["cap_pos_ids"], label_ids, True).mean()
+        states = self._decoder_states(encoder_outputs, batch["cap_attn_mask"], caption_ids, batch["cap_pos_ids"], True)
+        V = self.config.f_config.vocab_size
+        logits = self.v_encoder.f_encoder.lm_head(states.reshape(-1, states.shape[-1]), raw=True)
+        labels = label_ids.reshape(-1)
+        if self.lsr > 0:
+            return T.smooth_ce_mean(logits, labels, self.lsr, ncols=V, ignore_index=-1, inplace=True)
+        return HF.cross_entropy(logits, labels, ncols=V, ignore_index=-1).mean()
+
+
+class TvcGenerator(object):
+    """Greedy decoding (model/tvc.py:293-338) on a fixed [N, max_step] id buffer: the encoder runs once; every step runs the
+    decoder over the whole buffer under the causal mask - positions past the current one cannot influence it - projects ONLY
+    the current position through the vocabulary GEMM and takes the arg-max on the device.  One host transfer, at the end."""
+
+    def __init__(self, model, max_step, bos, eos):
+        self.model, self.max_step, self.bos, self.eos = model, max_step, bos, eos
+
+    @torch.no_grad()
+    def greedy_decode(self, batch, encoder_outputs=None):
+        """encoder_outputs: what model.encode(batch) returned, when the caller already has it."""
+        model = self.model
+        if encoder_outputs is None:
+            encoder_outputs = model.encode(batch)
+        enc_mask = batch["cap_attn_mask"]
+        N, dev = enc_mask.size(0), encoder_outputs.device
+        # the buffer is padded with the pad id, whose embedding row and positions the causal mask hides from every earlier step
+        input_ids = torch.full((N, self.max_step), model.v_encoder.f_encoder.embeddings.padding_idx, dtype=torch.long, device=dev)
+        pos_ids = torch.arange(0, self.max_step, dtype=torch.long, device=dev).unsqueeze(0)
+        output_ids = torch.empty((N, self.max_step), dtype=torch.long, device=dev)
+        last_out = torch.full((N,), self.bos, dtype=torch.long, device=dev)
+        fused = model._fused(encoder_outputs, input_ids)
+        head = model.v_encoder.f_encoder.lm_head
+        for step in range(self.max_step):
+            input_ids[:, step] = last_out
+            if fused:
+                states = model._decoder_states(encoder_outputs, enc_mask, input_ids, pos_ids, True)
+                scores = head(states[:, step].contiguous(), raw=True)
+            else:                                    # the reference's growing prefix
+                states = model._decoder_states(encoder_outputs, enc_mask, input_ids[:, :step + 1], pos_ids[:, :step + 1], False)
+                scores = model._scores_torch(states[:, -1])
+            last_out = scores[:, :model.config.f_config.vocab_size].float().argmax(dim=-1)
+            output_ids[:, step] = last_out
+        return [self.cut_eos(ids) for ids in output_ids.tolist()]
+
+    def cut_eos(self, ids):
+        out_ids = []
+        for i in ids:
+            if i == self.eos:
+                break
+            out_ids.append(i)
+        return out_ids

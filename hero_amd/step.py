@@ -32,8 +32,14 @@ VIOLIN_OPTS = dict(  # config/train-violin-8gpu.json: pass as `opts` with task='
     learning_rate=3e-5, lr_mul=8.0, weight_decay=0.01, optim="adamw", betas=[0.9, 0.98],
     grad_norm=1.0, warmup_steps=600, num_train_steps=6000, gradient_accumulation_steps=2,
     train_batch_size=4, dropout=0.1)
+TVC_OPTS = dict(  # config/train-tvc-8gpu.json: pass as `opts` with task='tvc'
+    learning_rate=1e-4, lr_mul=10.0, weight_decay=0.01, optim="adamw", betas=[0.9, 0.98],
+    grad_norm=1.0, warmup_steps=700, num_train_steps=7000, gradient_accumulation_steps=2,
+    train_batch_size=4, dropout=0.1, lsr=0.1)
 QA_TASKS = ("tvqa", "how2qa")
-HEAD_LR_TASKS = QA_TASKS + ("violin",)      # the task head's two optimiser groups keep lr * lr_mul (train_videoQA.py:185-190, train_violin.py:184)
+# the task head's two optimiser groups keep lr * lr_mul (train_videoQA.py:185-190, train_violin.py:184, train_tvc.py:193-197: for
+# captioning the "head" is everything outside v_encoder - the decoder, its position embedding and emb_LayerNorm)
+HEAD_LR_TASKS = QA_TASKS + ("violin", "tvc")
 
 
 def qkv_groups(model):
@@ -134,7 +140,12 @@ class TrainStep:
         # masks), the per-step seed word keeps the steps apart - graph replay and eager runs follow one trajectory
         HF.RNG.site = 0
         with _packing(_packing_mode_of(batch)), HF.weights_frozen(), D.uniform_shapes(self.uniform_shapes):
-            out = self.model(batch, task=task or self.task, compute_loss=True)
+            if (task or self.task) == "tvc":          # train_tvc.py:172-173: the mean of the caption losses, taken on the device
+                if not hasattr(self.model, "caption_loss"):
+                    raise ValueError("task 'tvc' needs a captioning model (hero_amd.model.HeroForTvc), got %s" % type(self.model).__name__)
+                out = self.model.caption_loss(batch)
+            else:
+                out = self.model(batch, task=task or self.task, compute_loss=True)
             # 'tvr' / 'vsm': (loss_st_ed, loss_neg_ctx, loss_neg_q) summed (train_vcmr.py:216-226, pretrain.py:283-290);
             # 'mlm' / 'mfm-nce' / 'fom': one loss tensor
             if (task or self.task) in QA_TASKS:       # (qa_loss, temporal_loss), train_videoQA.py:157-166

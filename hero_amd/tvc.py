@@ -1,0 +1,218 @@
+"""Autograd nodes of the captioning decoder (TVC) on the libhero_hip.so kernels hero_dec_attention_fwd / _bwd and
+hero_smooth_ce_fwd / _bwd (include/hero_hip.h "Decoder attention", "Label-smoothed loss"; reference: model/tvc.py:19-154).
+
+    DecAttnCoreFn     the attention kernel on projected operands: a fused [N*L, 3*H*64] Q|K|V buffer (causal self-attention) or a
+                      [N*Lq, H*64] query and a [N*Lk, 2*H*64] K|V buffer (decoder-encoder attention, key mask per caption)
+    DecAttentionFn    the same with its projections: BertSelfAttention under tri_mask / BertDecEncAttention of a decoder layer
+    SmoothCeFn        LabelSmoothingLoss in closed form: per-row losses plus the device pair (sum, number of valid rows)
+
+There is no PyTorch route in here: outside the kernels' envelope the nodes raise."""
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib as L
+from . import functional as HF
+
+MAX_LQ, MAX_LK, HEAD = 64, 128, 64                     # hero_amd/csrc/dec_attention.hip
+
+
+def in_envelope(dtype, Lq, Lk):
+    """The library's own answer (hero_dec_attention_in_envelope) for a torch dtype and the two sequence lengths."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return bool(L.lib().hero_dec_attention_in_envelope(L.F32 if dtype == torch.float32 else L.BF16, int(Lq), int(Lk)))
+
+
+def _f32c(t):
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _operands(qbuf, kvbuf, H):
+    """(q, k, v pointers, ldq, ldkv) of the two operand forms; kvbuf None = one fused Q|K|V buffer."""
+    D, es = H * HEAD, qbuf.element_size()
+    if kvbuf is None:
+        if qbuf.shape[1] != 3 * D:
+            raise ValueError("decoder attention: fused operand must be [rows, 3 * H * 64], got %s" % (tuple(qbuf.shape),))
+        p = L.ptr(qbuf)
+        return p, p + D * es, p + 2 * D * es, 3 * D, 3 * D
+    if qbuf.shape[1] != D or kvbuf.shape[1] != 2 * D or kvbuf.dtype != qbuf.dtype:
+        raise ValueError("decoder attention: operands must be [rows, H * 64] and [rows, 2 * H * 64] of one dtype, got %s %s"
+                         % (tuple(qbuf.shape), tuple(kvbuf.shape)))
+    p = L.ptr(kvbuf)
+    return L.ptr(qbuf), p, p + D * es, D, 2 * D
+
+
+def _drop_ref(drop):
+    return C.byref(drop) if drop is not None else None
+
+
+def k_dec_attn_fwd(qbuf, kvbuf, key_mask_add, N, Lq, Lk, H, causal, drop=None):
+    """-> (ctx [N*Lq, H*64] in the operands' dtype, stats [N, H, Lq, 2] fp32)."""
+    if not in_envelope(qbuf.dtype, Lq, Lk):
+        raise ValueError("decoder attention: %s, Lq=%d, Lk=%d is outside the kernels' envelope (fp32 / bf16, 1 <= Lq <= %d, "
+                         "1 <= Lk <= %d)" % (qbuf.dtype, Lq, Lk, MAX_LQ, MAX_LK))
+    q, k, v, ldq, ldkv = _operands(qbuf, kvbuf, H)
+    if qbuf.shape[0] != N * Lq or (kvbuf is not None and kvbuf.shape[0] != N * Lk) or (kvbuf is None and Lq != Lk):
+        raise ValueError("decoder attention: operand rows do not match N=%d Lq=%d Lk=%d" % (N, Lq, Lk))
+    if key_mask_add is not None and tuple(key_mask_add.shape) != (N, Lk):
+        raise ValueError("decoder attention: key mask must be [N, Lk], got %s" % (tuple(key_mask_add.shape),))
+    ctxt = torch.empty((N * Lq, H * HEAD), dtype=qbuf.dtype, device=qbuf.device)
+    stats = torch.empty((N, H, Lq, 2), dtype=torch.float32, device=qbuf.device)
+    L.check(L.lib().hero_dec_attention_fwd(q, k, v, L.ptr(key_mask_add), L.ptr(ctxt), L.ptr(stats), N, Lq, Lk, H, ldq, ldkv,
+                                           1 if causal else 0, 1.0 / math.sqrt(HEAD), L.dt(qbuf), _drop_ref(drop), L.stream()))
+    return ctxt, stats
+
+
+def k_dec_attn_bwd(qbuf, kvbuf, key_mask_add, stats, dctx, N, Lq, Lk, H, causal, drop=None):
+    """-> (dqbuf, dkvbuf) shaped like the operands (dkvbuf None in the fused form); every element is written by the kernel."""
+    q, k, v, ldq, ldkv = _operands(qbuf, kvbuf, H)
+    dqbuf = torch.empty_like(qbuf)
+    dkvbuf = torch.empty_like(kvbuf) if kvbuf is not None else None
+    dq, dk, dv, _, _ = _operands(dqbuf, dkvbuf, H)
+    L.check(L.lib().hero_dec_attention_bwd(q, k, v, L.ptr(key_mask_add), L.ptr(stats), L.ptr(dctx), dq, dk, dv, N, Lq, Lk, H, ldq, ldkv,
+                                           1 if causal else 0, 1.0 / math.sqrt(HEAD), L.dt(qbuf), _drop_ref(drop), L.stream()))
+    return dqbuf, dkvbuf
+
+
+class DecAttnCoreFn(torch.autograd.Function):
+    """(qbuf, kvbuf | None, key_mask_add [N, Lk] | None, N, Lq, Lk, H, causal, drop) -> ctx [N*Lq, H*64]."""
+
+    @staticmethod
+    def forward(ctx, qbuf, kvbuf, key_mask_add, N, Lq, Lk, H, causal, drop):
+        qbuf = qbuf.contiguous()
+        kvbuf = kvbuf.contiguous() if kvbuf is not None else None
+        mask = _f32c(key_mask_add) if key_mask_add is not None else None
+        out, stats = k_dec_attn_fwd(qbuf, kvbuf, mask, N, Lq, Lk, H, causal, drop)
+        ctx.save_for_backward(qbuf, kvbuf, mask, stats)
+        ctx.meta = (N, Lq, Lk, H, causal, drop)
+        return out
+
+    @staticmethod
+    def backward(ctx, dctx):
+        qbuf, kvbuf, mask, stats = ctx.saved_tensors
+        N, Lq, Lk, H, causal, drop = ctx.meta
+        dq, dkv = k_dec_attn_bwd(qbuf, kvbuf, mask, stats, dctx.contiguous().to(qbuf.dtype), N, Lq, Lk, H, causal, drop)
+        return (dq, dkv) + (None,) * 7
+
+
+class DecAttentionFn(torch.autograd.Function):
+    """One attention of a decoder layer with its projections, ctx = MHA(x | enc):
+        enc None   BertSelfAttention under the causal mask: one packed QKV GEMM on x [N, Lq, D], the kernel with causal = 1
+        enc given  BertDecEncAttention: the Q GEMM on x, one packed K|V GEMM on enc [N, Lk, D], the kernel with the caption's
+                   additive key mask [N, Lk]
+    Weight and bias gradients go to the gradient sink, as in SelfAttentionFn."""
+
+    @staticmethod
+    def forward(ctx, x, enc, key_mask_add, H, drop, wq, bq, wk, bk, wv, bv):
+        N, Lq, D = x.shape
+        x2 = HF._as2d(x)
+        cross = enc is not None
+        if cross:
+            Lk = enc.shape[1]
+            e2 = HF._as2d(enc)
+            qbuf = HF.k_linear(x2, HF.packed((wq,), x2.dtype), HF.packed((bq,), torch.float32))
+            kvbuf = HF.k_linear(e2, HF.packed((wk, wv), e2.dtype), HF.packed((bk, bv), torch.float32))
+            wt = (HF.packed_t((wq,), x2.dtype), HF.packed_t((wk, wv), x2.dtype))
+            mask = _f32c(key_mask_add) if key_mask_add is not None else None
+        else:
+            Lk, e2, kvbuf, mask = Lq, None, None, None
+            qbuf = HF.k_linear(x2, HF.packed((wq, wk, wv), x2.dtype), HF.packed((bq, bk, bv), torch.float32))
+            wt = (HF.packed_t((wq, wk, wv), x2.dtype), None)
+        out, stats = k_dec_attn_fwd(qbuf, kvbuf, mask, N, Lq, Lk, H, not cross, drop)
+        ctx.meta = (N, Lq, Lk, H, D, cross, drop)
+        ctx.params = (wq, bq, wk, bk, wv, bv)
+        HF._use(*ctx.params)
+        ctx.save_for_backward(x2, e2, qbuf, kvbuf, mask, stats, wt[0], wt[1])
+        return out.view(N, Lq, D)
+
+    @staticmethod
+    def backward(ctx, dctx):
+        x2, e2, qbuf, kvbuf, mask, stats, wt_q, wt_kv = ctx.saved_tensors
+        N, Lq, Lk, H, D, cross, drop = ctx.meta
+        wq, bq, wk, bk, wv, bv = ctx.params
+        dq, dkv = k_dec_attn_bwd(qbuf, kvbuf, mask, stats, HF._as2d(dctx), N, Lq, Lk, H, not cross, drop)
+        dx = HF.k_dgrad_t(dq, wt_q).view(N, Lq, D) if ctx.needs_input_grad[0] else None
+        denc = None
+        if cross:
+            if ctx.needs_input_grad[1]:
+                denc = HF.k_dgrad_t(dkv, wt_kv).view(N, Lk, D)
+            HF.acc_linear_grads(dq, x2, wq, bq)
+            HF.acc_linear_grads(dkv, e2, wk, bk, col0=0, ncols=D)
+            HF.acc_linear_grads(dkv, e2, wv, bv, col0=D, ncols=D)
+        else:
+            HF._qkv_bwd(dq, x2, ctx.params, D)
+        return (dx, denc) + (None,) * 9
+
+
+class SmoothCeFn(torch.autograd.Function):
+    """(logits [rows, ld], labels [rows], ncols, eps, ignore_index) -> (loss [rows] fp32, sum_cnt [2] fp32):
+        loss_r   the KL divergence of softmax(logits[r, :ncols]) to the smoothed one-hot of labels[r] (0 for ignored rows)
+        sum_cnt  (sum_r loss_r, number of valid rows), folded on the device in a fixed order
+    The gradient of `sum_cnt[0]` and of `loss` reach the logits in ONE pass; both upstream gradients are read on the device."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ncols, eps, ignore_index):
+        x2 = logits.contiguous()
+        rows, ld = x2.shape
+        lab = labels.contiguous().to(torch.int64)
+        loss, lse = (torch.empty((rows,), dtype=torch.float32, device=x2.device) for _ in range(2))
+        sum_cnt = torch.empty((2,), dtype=torch.float32, device=x2.device)
+        L.check(L.lib().hero_smooth_ce_fwd(L.ptr(x2), L.ptr(lab), L.ptr(loss), L.ptr(lse), L.ptr(sum_cnt), rows, ncols, ld, L.dt(x2),
+                                           float(eps), int(ignore_index), L.stream()))
+        ctx.save_for_backward(x2, lab, lse)
+        ctx.meta = (ncols, float(eps), int(ignore_index))
+        return loss, sum_cnt
+
+    @staticmethod
+    def backward(ctx, dloss, dsum_cnt):
+        x2, lab, lse = ctx.saved_tensors
+        ncols, eps, ignore_index = ctx.meta
+        rows, ld = x2.shape
+        # d / d logits = (dloss[r] + dsum_cnt[0]) * d loss_r: one factor per row, the scalar upstream of the kernel is 1
+        g = (_f32c(dloss) + _f32c(dsum_cnt)[0]).contiguous()
+        one = torch.ones((1,), dtype=torch.float32, device=x2.device)
+        dx = torch.empty_like(x2)
+        L.check(L.lib().hero_smooth_ce_bwd(L.ptr(x2), L.ptr(lab), L.ptr(lse), L.ptr(one), L.ptr(g), None, L.ptr(dx), rows, ncols, ld,
+                                           L.dt(x2), eps, ignore_index, L.stream()))
+        return dx, None, None, None, None
+
+
+class SmoothCeMeanFn(torch.autograd.Function):
+    """(logits, labels, ncols, eps, ignore_index) -> the mean of the smoothed loss over the valid rows, a 0-d fp32 tensor (0 when
+    no row is valid).  The valid count never leaves the device: forward divides by it there and backward reads it from the
+    forward's pair, so the node can be captured into a hipGraph.  The gradient overwrites nothing the caller still owns: it is a
+    new tensor unless `inplace`, which hands the logits' storage to the gradient (for logits nothing else reads)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ncols, eps, ignore_index, inplace):
+        x2 = logits.contiguous()
+        rows, ld = x2.shape
+        lab = labels.contiguous().to(torch.int64)
+        loss, lse = (torch.empty((rows,), dtype=torch.float32, device=x2.device) for _ in range(2))
+        sum_cnt = torch.empty((2,), dtype=torch.float32, device=x2.device)
+        L.check(L.lib().hero_smooth_ce_fwd(L.ptr(x2), L.ptr(lab), L.ptr(loss), L.ptr(lse), L.ptr(sum_cnt), rows, ncols, ld, L.dt(x2),
+                                           float(eps), int(ignore_index), L.stream()))
+        ctx.save_for_backward(x2, lab, lse, sum_cnt)
+        ctx.meta = (ncols, float(eps), int(ignore_index), bool(inplace))
+        return sum_cnt[0] / sum_cnt[1].clamp_min(1.0)
+
+    @staticmethod
+    def backward(ctx, dmean):
+        x2, lab, lse, sum_cnt = ctx.saved_tensors
+        ncols, eps, ignore_index, inplace = ctx.meta
+        rows, ld = x2.shape
+        dx = x2 if inplace else torch.empty_like(x2)
+        L.check(L.lib().hero_smooth_ce_bwd(L.ptr(x2), L.ptr(lab), L.ptr(lse), L.ptr(_f32c(dmean).view(1)), None, L.ptr(sum_cnt),
+                                           L.ptr(dx), rows, ncols, ld, L.dt(x2), eps, ignore_index, L.stream()))
+        return dx, None, None, None, None, None
+
+
+def smooth_ce(logits, labels, eps, ncols=None, ignore_index=-1):
+    """Per-row smoothed losses [rows] and the device pair (their sum, the number of valid rows)."""
+    return SmoothCeFn.apply(logits, labels, logits.shape[1] if ncols is None else ncols, eps, ignore_index)
+
+
+def smooth_ce_mean(logits, labels, eps, ncols=None, ignore_index=-1, inplace=False):
+    return SmoothCeMeanFn.apply(logits, labels, logits.shape[1] if ncols is None else ncols, eps, ignore_index, inplace)

@@ -44,6 +44,8 @@ const char* hero_last_error(void);
  * Still 3: hero_moment_nms and hero_first_hit (what follows a search: NMS and recall ranks) were ADDED the same way.
  * Still 3: hero_qa_pool_fwd and hero_qa_pool_bwd (the video-QA head) were ADDED the same way.
  * Still 3: hero_frame_pool_fwd/bwd and hero_bce_head_fwd/bwd (the VIOLIN head) were ADDED the same way.
+ * Still 3: hero_dec_attention_fwd/bwd/in_envelope and hero_smooth_ce_fwd/bwd, the captioning decoder's kernels, were ADDED the
+ * same way (a POINTER to the existing HeroDropout is an argument; the struct itself is unchanged).
  * INTEGRATION.md section 2 lists the breaks per version. */
 #define HERO_ABI_VERSION 3
 int hero_abi_version(void);
@@ -293,6 +295,33 @@ int hero_attention_force_ppw(int ppw); /* tuning hook: (sequence, head) pairs pe
 /* 1 when forward + backward of this dtype / length run from `stats` without saved probabilities (bf16 matrix-core */
 /* kernels, L <= 64)                                                                                               */
 int hero_attention_stats_ok(int dtype, int L);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Decoder attention, head size 64 - model/tvc.py:67-104 and the decoder's causal self-attention */
+/*   scores = Q K^T * scale + key_mask_add[n, key] + (causal and key > query ? -10000 : 0)      */
+/*   P = softmax(scores) in fp32; ctx = dropout(P) V                                            */
+/* Query and key/value sequences are separate operands: q rows [N*Lq] with leading dimension   */
+/* ldq, k and v rows [N*Lk] with leading dimension ldkv, head h at columns h*64 of each.  The    */
+/* self-attention call passes the three column blocks of a fused [N*L, 3*H*64] projection        */
+/* (ldq = ldkv = 3*H*64), the decoder-encoder call a [N*Lq, H*64] query and the halves of a      */
+/* [N*Lk, 2*H*64] key/value projection.  dq / dk / dv follow q / k / v; ctx and dctx are         */
+/* [N*Lq, H*64].  key_mask_add is [N, Lk] fp32 or NULL.  The masks are ADDITIVE, as in the        */
+/* reference: a caption whose keys are all masked attends uniformly to its Lk keys.             */
+/* Dropout on P (NULL: none): element index ((n*H + h)*Lq + i) * round_up(Lk, 4) + j; the         */
+/* backward regenerates the mask.  fwd writes stats [N, H, Lq, 2] fp32 = (row maximum, 1 / row    */
+/* sum); bwd recomputes P from q, k, the mask and stats and writes EVERY element of dq, dk, dv    */
+/* of the H head blocks (no zero-fill by the caller, no atomics: two runs give the same bits).   */
+/* Envelope: fp32 / bf16, 1 <= Lq <= 64, 1 <= Lk <= 128, H >= 1, N >= 0 (0: no launch); ldq, ldkv */
+/* multiples of 8 and >= H*64; pointers 16-byte aligned.  Outside it HERO_ERR_ARG, no launch.    */
+/* Plain arguments: a backward-compatible addition, HERO_ABI_VERSION stays.                     */
+/* ------------------------------------------------------------------------------------------ */
+int hero_dec_attention_in_envelope(int dtype, int Lq, int Lk);
+int hero_dec_attention_fwd(const void* q, const void* k, const void* v, const float* key_mask_add, void* ctx, float* stats,
+                           int N, int Lq, int Lk, int H, int ldq, int ldkv, int causal, float scale, int dtype,
+                           const HeroDropout* dropout, hero_stream_t stream);
+int hero_dec_attention_bwd(const void* q, const void* k, const void* v, const float* key_mask_add, const float* stats,
+                           const void* dctx, void* dq, void* dk, void* dv, int N, int Lq, int Lk, int H, int ldq, int ldkv,
+                           int causal, float scale, int dtype, const HeroDropout* dropout, hero_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Row gathers / scatters                                                                       */
@@ -679,6 +708,22 @@ typedef struct HeroCrossEntropy {
 } HeroCrossEntropy;
 int hero_cross_entropy_fwd(const HeroCrossEntropy* a, hero_stream_t stream);
 int hero_cross_entropy_bwd(const HeroCrossEntropy* a, hero_stream_t stream);
+
+/* Label-smoothed loss of the captioning decoder (model/tvc.py:19-64): the KL divergence of softmax(x) to the smoothed one-hot */
+/* of label t, over the first `cols` columns of [rows, ld] logits, in closed form - no [rows, cols] target matrix:            */
+/*   C = cols, s = eps / (C - 1), conf = 1 - eps, H0 = conf ln conf + (C - 1) s ln s with 0 ln 0 = 0 (eps = 1 is allowed)       */
+/*   loss = H0 - (conf - s) (x_t - lse) - s (sum_c x_c - C lse),   dx_c = (softmax(x)_c - s - (conf - s) [c == t]) * g           */
+/* Rows whose label equals ignore_index (or lies outside [0, cols)) give loss 0 and a zero gradient row; columns >= cols get   */
+/* a zero gradient.  fwd: loss [rows], lse [rows], and sum_cnt [2] = (sum of the row losses, number of valid rows), folded by   */
+/* one workgroup in a fixed order (rows == 0 gives (0, 0)).  bwd: g = dloss[0] (device scalar) * dloss_rows[r] (optional) /      */
+/* max(mean_cnt[1], 1) (optional: pass the forward's sum_cnt for the gradient of the MEAN over the valid rows; the count is     */
+/* read on the device, nothing synchronises, both calls can be captured into a hipGraph).  dlogits may alias logits.            */
+/* 0 < eps <= 1, cols >= 2, logits / dlogits 16-byte aligned; plain arguments, HERO_ABI_VERSION stays.                         */
+int hero_smooth_ce_fwd(const void* logits, const long long* labels, float* loss, float* lse, float* sum_cnt, int rows, int cols,
+                       int ld, int dtype, double eps, long long ignore_index, hero_stream_t stream);
+int hero_smooth_ce_bwd(const void* logits, const long long* labels, const float* lse, const float* dloss, const float* dloss_rows,
+                       const float* mean_cnt, void* dlogits, int rows, int cols, int ld, int dtype, double eps,
+                       long long ignore_index, hero_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Collate on the device: the index tensors of a batch from per-subtitle / per-video length      */
