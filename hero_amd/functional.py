@@ -9,10 +9,12 @@ Block structure (one autograd node each, residual fan-in fused into GEMM epilogu
   attn_block : LN(drop(ctx Wo^T + bo) + x),  ctx = MHA(x Wqkv^T + bqkv)     model/layers.py:217-222
   ffn_block  : LN(drop(gelu(a W1^T + b1) W2^T + b2) + a)                    model/layers.py:264-272
 """
+import bisect
 import ctypes as C
 import math
 import os
 import weakref
+from typing import Any, NamedTuple
 
 import numpy as np
 import torch
@@ -397,56 +399,130 @@ def _split_for(n_out, n_in, rows, bk):
     return best
 
 
-# Weight gradients that ACCUMULATE into the gradient sink are not launched one by one: inside a backward pass they
-# are queued and launched together.  Round 3: the queue holds up to WGRAD_BATCH[0] problems - the weight gradients of
-# ALL the BertLayers of an encoder reduce over the same rows - and goes out as ONE whole-tile launch
-# (hero_wgrad_batch: 6 x 192 = 1152 tiles = 4.5 rounds of the chip, no atomics in the full rounds, bit-reproducible);
-# groups with fewer tiles than the chip has CUs, and the boundary micro-steps of a data-parallel run (where a layer's
-# gradients must become final - and their bucket's all-reduce start - while backward is still running), go four at a
-# time through the stream-K launch of round 2 (hero_wgrad_group).  The queue is flushed when it is full, when the row
-# count changes, and by an autograd-engine callback at the end of the backward pass, so nothing outside ever sees a
-# pending gradient.  `on_done` (gradient-sink finality for the bucketed all-reduce) runs when the launch is issued.
-# The queue keeps dY / X alive until then (~1 GB for HERO-base at 12000 rows).
-# Module-level switches below are for lab scripts and tests (set from Python); none of them is read from the environment.
-# The package's environment variables are listed in README.md ("Environment variables") and checked by
-# tests/test_cpu_boundary.py::test_the_package_reads_only_documented_environment_variables.
-_WQ = []
-_WQ_TASK = [-1]          # autograd graph task the queued problems belong to
-GROUP_WGRADS = [True]       # False: one launch per weight gradient (lab A/B)
-WGRAD_BATCH = [32]          # 4: the per-layer stream-K launches of round 2 (lab A/B)
-WGRAD_DBIAS_RIDE = [True]   # False: bias gradients as (deferred) column sums of their own instead of riding on hero_wgrad_batch (lab A/B)
-# ... and only for reductions of at most this many rows (lab A/B: 0 = never ride).  History: rounds 4-5 summed the dY panels with the
-# kernel's LOADER waves (24 KB more LDS reads per k-step on an LDS-bound loop): the tiles that did it ran ~20 % slower and gated
-# their round - config 5's 397056-row launches 8.0-8.6 ms against 6.9-7.0 without, so round 6 first took the sums out (-4.2 %
-# on config 5, +-0.3 % on the TVR batch; profiles/r06_d4_ride_ab.txt).  Round 6, late: the sums come from the COMPUTE waves - one
-# extra MFMA per row block against a constant selector operand, no LDS traffic (csrc/gemm_ws.hip) - and the ride wins at every
-# size: D2 6.070 -> 6.005 ms, ragged 7.92 -> 7.86, config 5 (256 videos) 150.3 -> 148.8 (tools/lab/ab_ride.py, same process,
-# alternating; profiles/r06_mfma_ride_ab.txt): the 55 MB re-read of dqkv per layer is gone.
+# Weight gradients that ACCUMULATE into the gradient sink are queued inside a backward pass and launched together.  Those
+# of all the BertLayers of an encoder reduce over the same rows, so up to 32 go out as ONE whole-tile launch
+# (hero_wgrad_batch: no atomics in the full rounds, bit-reproducible); groups with fewer tiles than the chip has CUs, and
+# the boundary micro-steps of a data-parallel run (where a layer's gradients must become final - and their bucket's
+# all-reduce start - while backward is still running), go four at a time through the stream-K launch (hero_wgrad_group).
+# The queue is flushed when it is full, when the row count changes, and by an autograd-engine callback at the end of the
+# backward pass, so nothing outside ever sees a pending gradient.  `on_done` (gradient-sink finality for the bucketed
+# all-reduce) runs when the launch is issued.  The queue keeps dY / X alive until then (~1 GB for HERO-base at 12000 rows).
+# Column sums into the sink (bias gradients, LayerNorm gamma / beta / fused-bias partial folds) are queued the same way
+# and go out as hero_colsum_multi: two launches for up to 64 sums, in a fixed summation order.
+class WgradJob(NamedTuple):
+    """out[ncols, K] += dy[:, col0:col0 + ncols]^T @ x and, where given, dbias[ncols] += the column sums of the same dY."""
+    dy: Any
+    x: Any
+    out: Any
+    col0: int
+    ncols: int
+    on_done: Any
+    dbias: Any
+    dbias_done: Any
+
+
+class ColsumJob(NamedTuple):
+    keep: Any           # the tensors the launch reads, alive until it is issued
+    prob: Any           # L.Colsum
+    dst: Any
+    on_done: Any
+
+
+class _GradQueue:
+    """Jobs deferred inside one backward pass (autograd graph task `task`); `nbytes` is what they keep alive."""
+    flush_task = -1         # shared by the queues: ONE engine callback per backward pass flushes whatever is still queued
+
+    def __init__(self, request_flush=lambda: torch.autograd.Variable._execution_engine.queue_callback(deferred_flush)):
+        self.jobs, self.task, self.nbytes, self.request_flush = [], -1, 0, request_flush
+
+    def clear(self):
+        del self.jobs[:]
+        self.nbytes = 0
+
+    def push(self, job, task, nbytes=0):
+        if self.task != task:
+            self.clear()        # left behind by a backward pass that raised: never launch them into this one
+            self.task = task
+        if _GradQueue.flush_task != task:
+            _GradQueue.flush_task = task
+            self.request_flush()
+        self.jobs.append(job)
+        self.nbytes += nbytes
+
+    def take(self, n):
+        group = self.jobs[:n]
+        del self.jobs[:n]
+        if not self.jobs:
+            self.nbytes = 0
+        return group
+
+
+_WQ, _CQ = _GradQueue(), _GradQueue()
+# Switches are set from Python by lab scripts and tests; the environment variables are listed in README.md, which
+# tests/test_cpu_boundary.py::test_the_package_reads_only_documented_environment_variables checks.  Bias gradients ride on
+# hero_wgrad_batch (its compute waves sum the dY panels: one extra MFMA per row block, no LDS traffic) for reductions of at
+# most this many rows; 0: never, they become deferred column sums.  It wins at every size (profiles/r06_mfma_ride_ab.txt).
 WGRAD_RIDE_MAX_ROWS = [1 << 30]
-B1_EPILOGUE = [False]       # True: the FFN1 bias gradient from the gelu' GEMM epilogue's fp32 atomics, as in rounds 1-3 (lab A/B)
-B1_PARTIALS = [True]        # False: round 4's ride on hero_wgrad_batch (lab A/B); True: per-tile partial sums from the gelu' epilogue
-WGRAD_QUEUE_BYTES = [int(os.environ.get("HERO_WGRAD_QUEUE_MB", "4096")) << 20]   # dY bytes the queue may keep alive (config 5
-_WQ_BYTES = [0]                                                  # sizes its batch to 90 % of HBM: there it flushes at once)
+WGRAD_QUEUE_BYTES = [int(os.environ.get("HERO_WGRAD_QUEUE_MB", "4096")) << 20]   # dY bytes the queue may keep alive
+_WQ_HARD = {}            # device index -> hard cap in bytes (_wgrad_queue_full)
 _WPLANS = {}             # (rows, ((M, N), ...)) -> (device int32 plan, words) or None when the group is too small
 _WPLANS_PINNED = set()   # keys whose plan tensor a captured graph references by address
 
 
-def _wgrad_queue_full(device):
+def _take_dst(seen, dst):
+    """One launch never holds the same fp32 destination twice (its read-add-write of dst is not atomic): a parameter used
+    twice in one backward pass (a tied nn.Linear, the LayerNorm that subtitles and queries share) goes into consecutive
+    launches, which the stream orders.  "The same" means overlapping ADDRESS RANGES, not equal pointers: a column sum with
+    indexed rows (HeroColsum.dst_rows) covers its table from the base, one into a constant row starts at base + row * D.
+    `seen`: the disjoint ranges already in the launch as ONE sorted list of their bounds [lo0, hi0, lo1, hi1, ...] (plain
+    ints: nothing for the cyclic GC to track).  Returns False if dst overlaps one of them; else dst is added."""
+    lo = dst.data_ptr()
+    hi = lo + 4 * dst.numel()
+    i = bisect.bisect_right(seen, lo)               # odd: lo lies inside a range; else seen[i] is the next range's start
+    if i % 2 or (i < len(seen) and seen[i] < hi):
+        return False
+    seen[i:i] = lo, hi
+    return True
+
+
+def _next_wgrad_launch(jobs):
+    """How many leading jobs form the next weight-gradient launch: equal row count and dtype, at most 32 (the batch
+    kernel's limit), cut before a job whose dW or dbias overlaps one already taken (a grouped [Wq;Wk;Wv] holds its thirds)."""
+    rows, dtype = jobs[0].dy.shape[0], jobs[0].dy.dtype
+    seen, n = [], 0
+    for j in jobs[:32]:
+        if (j.dy.shape[0] != rows or j.dy.dtype != dtype or not _take_dst(seen, j.out)
+                or (j.dbias is not None and not _take_dst(seen, j.dbias))):
+            break
+        n += 1
+    return n
+
+
+def _next_colsum_launch(jobs):
+    """How many leading jobs form the next hero_colsum_multi launch: at most 64, cut before an overlapping destination."""
+    seen, n = [], 0
+    for j in jobs[:64]:
+        if not _take_dst(seen, j.dst):
+            break
+        n += 1
+    return n
+
+
+def _wgrad_queue_full(jobs, nbytes, device):
     """Byte budget of the queue (it keeps dY / X alive).  Past the soft cap (HERO_WGRAD_QUEUE_MB, 4 GB) the queue is
     flushed as soon as its tiles fill whole rounds of the chip - or a tail the plan can slice evenly; past the hard cap
     (15 % of the device memory) in any case.  Config 5 is what this is for: one BertLayer there is 5-20 GB of dY and 192
-    tiles = 3/4 of a round; round 3 flushed wherever the byte cap fell (192 tiles at the 256-video profiling size), round 4
-    waits for the next whole round (256 tiles = a layer and the first weight of the next one)."""
-    if _WQ_BYTES[0] <= WGRAD_QUEUE_BYTES[0]:
+    tiles = 3/4 of a round, so the queue waits for a whole round (256 tiles = a layer and the next one's first weight)."""
+    if nbytes <= WGRAD_QUEUE_BYTES[0]:
         return False
     hard = _WQ_HARD.get(device.index)
     if hard is None:
         env = os.environ.get("HERO_WGRAD_QUEUE_HARD_MB")
         hard = (int(env) << 20) if env else max(2 * WGRAD_QUEUE_BYTES[0], int(0.15 * torch.cuda.get_device_properties(device).total_memory))
         _WQ_HARD[device.index] = hard
-    if _WQ_BYTES[0] > hard:
+    if nbytes > hard:
         return True
-    tiles = sum(-(-e[4] // 192) * -(-e[1].shape[1] // 192) for e in _WQ)
+    tiles = sum(-(-j.ncols // 192) * -(-j.x.shape[1] // 192) for j in jobs)
     full, rem = divmod(tiles, 256)
     if rem == 0:
         return True
@@ -457,11 +533,8 @@ def _wgrad_queue_full(device):
     return tiles / 256.0 >= 0.9 * (full + (1.4 if slices > 1 else 1.0) / slices)
 
 
-_WQ_HARD = {}
-
-
 def _wgrad_limit():
-    return 4 if (WGRAD_BATCH[0] <= 4 or SINK.wants_overlap()) else min(WGRAD_BATCH[0], 32)
+    return 4 if SINK.wants_overlap() else 32
 
 
 def _wgrad_plan(probs, n, rows, device):
@@ -485,121 +558,68 @@ def _wgrad_plan(probs, n, rows, device):
     return hit
 
 
-_CB_TASK = [-1]
-
-
-def _ensure_flush_callback(task):
-    """One engine callback per backward pass flushes whatever is still queued (weight gradients, column sums)."""
-    if _CB_TASK[0] != task:
-        _CB_TASK[0] = task
-        torch.autograd.Variable._execution_engine.queue_callback(deferred_flush)
-
-
 def deferred_flush():
-    _CB_TASK[0] = -1
+    _GradQueue.flush_task = -1
     wgrad_flush()
     colsum_flush()
 
 
-# Column sums that ACCUMULATE into the gradient sink (bias gradients of the nn.Linear layers, LayerNorm gamma / beta /
-# fused-bias partial folds) are queued the same way and go out as hero_colsum_multi: two launches for up to 64 sums
-# instead of two or three tiny launches each (72 launches, 0.39 ms per micro-step in round 2), in a fixed summation
-# order (the per-call folds used 8-way fp32 atomics).  Entries keep their source tensors alive.
-_CQ = []
-_CQ_TASK = [-1]
-
-
 def _colsum_defer_ok():
-    return GROUP_WGRADS[0] and not SINK.wants_overlap() and torch._C._current_graph_task_id() != -1
+    return not SINK.wants_overlap() and torch._C._current_graph_task_id() != -1
 
 
 def _colsum_queue(keep, src_ptr, dst, rows, cols, ld, dtype, on_done=None, dst_rows=None, row_cols=0):
     """dst_rows (int32 [cols / row_cols]) + row_cols: the column sums are added to dst's ROWS dst_rows[j] (hero_hip.h)."""
-    task = torch._C._current_graph_task_id()
-    if _CQ and _CQ_TASK[0] != task:
-        del _CQ[:]                      # left behind by a backward pass that raised
-    _CQ_TASK[0] = task
-    _ensure_flush_callback(task)
-    _CQ.append(((keep, dst_rows), L.Colsum(src_ptr, L.ptr(dst), rows, cols, ld, dtype, 1.0, row_cols, L.ptr(dst_rows)), dst, on_done))
-    if len(_CQ) >= 64:
+    prob = L.Colsum(src_ptr, L.ptr(dst), rows, cols, ld, dtype, 1.0, row_cols, L.ptr(dst_rows))
+    _CQ.push(ColsumJob((keep, dst_rows), prob, dst, on_done), torch._C._current_graph_task_id())
+    if len(_CQ.jobs) >= 64:
         colsum_flush()
 
 
 def colsum_flush():
-    while _CQ:
-        # one launch must not hold the same destination twice (the fold's read-add-write of dst is not atomic): a
-        # parameter used twice in the forward pass (the sub-token embedding LayerNorm: subtitles and queries) goes into
-        # consecutive launches, which the stream orders
-        # ... and "the same destination" means overlapping ADDRESS RANGES, not equal pointers (ADVICE r4): a problem with
-        # indexed destination rows (HeroColsum.dst_rows) covers its whole table from the table base, a constant-row
-        # problem on the same table starts at base + row * D - one launch would mix the former's atomicAdd with the
-        # latter's plain read-add-write on the same addresses
-        part, seen = [], []
-        while _CQ and len(part) < 64:
-            lo = _CQ[0][1].dst
-            hi = lo + 4 * _CQ[0][2].numel()
-            if any(lo < b and a < hi for a, b in seen):
-                break
-            seen.append((lo, hi))
-            part.append(_CQ.pop(0))
+    while _CQ.jobs:
+        part = _CQ.take(_next_colsum_launch(_CQ.jobs))
         n = len(part)
-        probs = (L.Colsum * n)(*[e[1] for e in part])
+        probs = (L.Colsum * n)(*[j.prob for j in part])
         need = L.lib().hero_colsum_multi_workspace_bytes(probs, n) // 4
-        ws = _workspace(max(need, 1), part[0][2].device, slot="colsum_multi")
+        ws = _workspace(max(need, 1), part[0].dst.device, slot="colsum_multi")
         L.check(L.lib().hero_colsum_multi(probs, n, L.ptr(ws), L.stream()))
-        for e in part:
-            if e[3] is not None:
-                e[3]()
+        for j in part:
+            if j.on_done is not None:
+                j.on_done()
 
 
 def wgrad_flush():
-    _WQ_BYTES[0] = 0
-    while _WQ:
-        rows, dtype = _WQ[0][0].shape[0], _WQ[0][0].dtype
-        # One launch never holds the same destination twice: full-round tiles of hero_wgrad_batch do a plain (non-atomic)
-        # read-add-write of dW and of the riding bias sums, so a parameter used twice in one backward pass with equal row
-        # counts (a shared / tied nn.Linear, fuse_query_pass=False with coinciding row counts) goes into consecutive
-        # launches, which the stream orders - as colsum_flush does.
-        dst_key = lambda e: (e[2].data_ptr(), e[6].data_ptr() if e[6] is not None else None)     # noqa: E731
-        seen_w, seen_b = {_WQ[0][2].data_ptr()}, {dst_key(_WQ[0])[1]} - {None}
-        n = 1
-        while n < len(_WQ) and n < 32 and _WQ[n][0].shape[0] == rows and _WQ[n][0].dtype == dtype:
-            kw, kb = dst_key(_WQ[n])
-            if kw in seen_w or (kb is not None and kb in seen_b):
-                break
-            seen_w.add(kw)
-            if kb is not None:
-                seen_b.add(kb)
-            n += 1
-        group, rest = _WQ[:n], _WQ[n:]
-        del _WQ[:]
-        _WQ.extend(rest)
+    while _WQ.jobs:
+        group = _WQ.take(_next_wgrad_launch(_WQ.jobs))
+        n, dy0 = len(group), group[0].dy
+        rows, dtype = dy0.shape[0], dy0.dtype
         probs = (L.WgradProblem * n)()
-        for i, (dy2, x2, out, col0, N, _, _, _) in enumerate(group):
-            K = x2.shape[1]
-            probs[i] = L.WgradProblem(L.ptr(dy2) + col0 * dy2.element_size(), L.ptr(x2), L.ptr(out), N, K,
-                                      dy2.shape[1], K, K, _split_for(N, K, rows, 64 if dtype == torch.bfloat16 else 32), None)
-        plan = _wgrad_plan(probs, n, rows, group[0][0].device) if dtype == torch.bfloat16 else None
+        for i, j in enumerate(group):
+            K = j.x.shape[1]
+            probs[i] = L.WgradProblem(L.ptr(j.dy) + j.col0 * j.dy.element_size(), L.ptr(j.x), L.ptr(j.out), j.ncols, K,
+                                      j.dy.shape[1], K, K, _split_for(j.ncols, K, rows, 64 if dtype == torch.bfloat16 else 32), None)
+        plan = _wgrad_plan(probs, n, rows, dy0.device) if dtype == torch.bfloat16 else None
         if plan is not None:
-            ride = WGRAD_DBIAS_RIDE[0] and rows <= WGRAD_RIDE_MAX_ROWS[0]
-            for i, e in enumerate(group):                   # bias gradients ride on the dY panels of the batch kernel
-                probs[i].dbias = L.ptr(e[6]) if ride else None
-                if not ride and e[6] is not None:
-                    k_colsum(e[0], out=e[6], beta=1.0, col0=e[3], ncols=e[4], on_done=lambda: None)
+            ride = rows <= WGRAD_RIDE_MAX_ROWS[0]
+            for i, j in enumerate(group):                   # bias gradients ride on the dY panels of the batch kernel
+                probs[i].dbias = L.ptr(j.dbias) if ride else None
+                if not ride and j.dbias is not None:
+                    k_colsum(j.dy, out=j.dbias, beta=1.0, col0=j.col0, ncols=j.ncols, on_done=lambda: None)
             L.check(L.lib().hero_wgrad_batch(probs, n, rows, L.BF16, L.ptr(plan[0]), plan[1], L.stream()))
-            for e in group:
-                if e[6] is not None and e[7] is not None:
-                    e[7]()
+            for j in group:
+                if j.dbias is not None and j.dbias_done is not None:
+                    j.dbias_done()
         else:
             for g0 in range(0, n, 4):
                 sub = (L.WgradProblem * min(4, n - g0))(*[probs[i] for i in range(g0, min(g0 + 4, n))])
-                L.check(L.lib().hero_wgrad_group(sub, len(sub), rows, L.dt(group[0][0]), L.stream()))
-            for dy2, _, _, col0, N, _, dbias, dbias_done in group:
-                if dbias is not None:
-                    k_colsum(dy2, out=dbias, beta=1.0, col0=col0, ncols=N, on_done=dbias_done or (lambda: None))
-        for e in group:
-            if e[5] is not None:
-                e[5]()
+                L.check(L.lib().hero_wgrad_group(sub, len(sub), rows, L.dt(dy0), L.stream()))
+            for j in group:
+                if j.dbias is not None:
+                    k_colsum(j.dy, out=j.dbias, beta=1.0, col0=j.col0, ncols=j.ncols, on_done=j.dbias_done or (lambda: None))
+        for j in group:
+            if j.on_done is not None:
+                j.on_done()
 
 
 def k_wgrad(dy2, x2, out=None, beta=0.0, col0=0, ncols=None, on_done=None, dbias=None, dbias_done=None):
@@ -610,20 +630,12 @@ def k_wgrad(dy2, x2, out=None, beta=0.0, col0=0, ncols=None, on_done=None, dbias
     M, ld = dy2.shape
     N = ld - col0 if ncols is None else ncols
     K = x2.shape[1]
-    if (out is not None and beta == 1.0 and GROUP_WGRADS[0] and out.is_contiguous() and dy2.is_contiguous()
-            and x2.is_contiguous() and torch._C._current_graph_task_id() != -1):
-        task = torch._C._current_graph_task_id()
-        if _WQ and _WQ_TASK[0] != task:
-            del _WQ[:]                  # left behind by a backward pass that raised: never launch them into this one
-            _WQ_BYTES[0] = 0
-        if _WQ and (_WQ[0][0].shape[0] != M or _WQ[0][0].dtype != dy2.dtype):
+    task = torch._C._current_graph_task_id()
+    if out is not None and beta == 1.0 and out.is_contiguous() and dy2.is_contiguous() and x2.is_contiguous() and task != -1:
+        if _WQ.jobs and _WQ.task == task and (_WQ.jobs[0].dy.shape[0] != M or _WQ.jobs[0].dy.dtype != dy2.dtype):
             wgrad_flush()
-        if not _WQ:
-            _WQ_TASK[0] = task
-        _ensure_flush_callback(task)
-        _WQ.append((dy2, x2, out, col0, N, on_done, dbias, dbias_done))
-        _WQ_BYTES[0] += dy2.numel() * dy2.element_size()
-        if len(_WQ) >= _wgrad_limit() or _wgrad_queue_full(dy2.device):
+        _WQ.push(WgradJob(dy2, x2, out, col0, N, on_done, dbias, dbias_done), task, dy2.numel() * dy2.element_size())
+        if len(_WQ.jobs) >= _wgrad_limit() or _wgrad_queue_full(_WQ.jobs, _WQ.nbytes, dy2.device):
             wgrad_flush()
         return out
     if dbias is not None:
@@ -678,6 +690,15 @@ def acc_linear_grads(dy2, x2, weight, bias, col0=0, ncols=None):
                 dbias=SINK.dst(bias) if want_b else None, dbias_done=(lambda: SINK.done(bias)) if want_b else None)
     elif want_b:
         k_colsum(dy2, out=SINK.dst(bias), beta=1.0, col0=col0, ncols=N, on_done=lambda: SINK.done(bias))
+
+
+def fold_param_shares(part, w):
+    """part [n, numel(w)] fp32: per-sequence shares of w's gradient, folded in a fixed order - into the gradient sink (a
+    deferred column sum; returns None) when w is a parameter, else into the returned gradient (None if w needs none)."""
+    if _is_param(w):
+        k_colsum(part, out=SINK.dst(w).view(-1), beta=1.0, on_done=lambda: SINK.done(w))
+        return None
+    return k_colsum(part).view_as(w) if w.requires_grad else None
 
 
 def k_ln_fwd(x2, gamma, beta, eps, out_dtype, rows, cols, tabs=(), idxs=(), want_pre=False,
@@ -917,8 +938,8 @@ def reset_caches():
     _WPLANS_PINNED.clear()
     _SEQ_OFF.clear()
     _SLACK.clear()
-    del _WQ[:]
-    del _CQ[:]
+    _WQ.clear()
+    _CQ.clear()
     set_grad_sink(None)
     from .model.layers import BertEncoder          # pack plans keep their mask tensors (whole batches) alive
     BertEncoder._PLANS.clear()
@@ -1686,16 +1707,14 @@ class FfnBlockFn(torch.autograd.Function):
         if fuse_b:
             SINK.done(b2)
         acc_linear_grads(dy2d, hg, w2, None if fuse_b else b2)
-        # db1 = column sums of du.  Rounds 1-3: fp32 atomics from this GEMM's gelu' epilogue (order-dependent).  Round 4: they
-        # rode on the batched weight-gradient launch (deterministic, but 3072 more bias columns through hero_wgrad_batch's
-        # loader waves cost that launch +0.09 ms per micro-step: tools/lab/ab_wgrad.py, profiles/r05_wgrad_ab.txt).  Round 5:
-        # the epilogue writes each tile's column sums to a [rows / 64, 3072] table (HeroGemmEpilogue.colsum_partial: plain
-        # stores, no atomics) and the table is folded in fixed order - by the deferred multi-sum of the backward pass, or at
-        # once where gradients must become final layer by layer (boundary micro-steps of a data-parallel run).
+        # db1 = column sums of du.  bf16: the gelu' epilogue writes each tile's column sums to a [rows / 64, 3072] table
+        # (HeroGemmEpilogue.colsum_partial: plain stores, no atomics), folded in fixed order by the deferred multi-sum - or at
+        # once where gradients must become final layer by layer; riding on hero_wgrad_batch cost that launch +0.09 ms per
+        # micro-step (profiles/r05_wgrad_ab.txt).  fp32: the epilogue's atomics on that overlap path, else the ride.
         part = None
-        if b1.requires_grad and B1_PARTIALS[0] and dy2d.dtype == torch.bfloat16:
+        if b1.requires_grad and dy2d.dtype == torch.bfloat16:
             part = torch.empty((-(-dy2d.shape[0] // 64), W2_t.shape[0]), dtype=torch.float32, device=dy2d.device)
-        fuse_b1 = part is None and b1.requires_grad and (SINK.wants_overlap() or not GROUP_WGRADS[0] or B1_EPILOGUE[0])
+        fuse_b1 = part is None and b1.requires_grad and SINK.wants_overlap()
         du = k_dgrad_t(dy2d, W2_t, act=L.ACT_MUL_AUX, aux=u,    # * gelu'(pre-activation) = the saved tensor, fused
                        colsum=part if part is not None else (SINK.dst(b1) if fuse_b1 else None), colsum_partial=part is not None)
         if part is not None:

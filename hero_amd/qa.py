@@ -61,11 +61,4 @@ class QaPoolFn(torch.autograd.Function):
                                          L.ptr(w_se.detach().reshape(-1).contiguous()), L.ptr(att[0]), L.ptr(att[1]),
                                          L.ptr(_f32c(dqa)), L.ptr(_f32c(dse)), L.ptr(dx), L.ptr(part[0]), L.ptr(part[1]),
                                          Nv, A, Lf, Lt, D, L.dt(seq), L.stream()))
-        grads = []
-        for w, p in ((w_qa, part[0]), (w_se, part[1])):
-            if HF._is_param(w):
-                HF.k_colsum(p, out=HF.SINK.dst(w).view(-1), beta=1.0, on_done=lambda w=w: HF.SINK.done(w))
-                grads.append(None)
-            else:
-                grads.append(HF.k_colsum(p).view_as(w) if w.requires_grad else None)
-        return dx, None, grads[0], grads[1], None, None
+        return dx, None, HF.fold_param_shares(part[0], w_qa), HF.fold_param_shares(part[1], w_se), None, None

@@ -65,12 +65,7 @@ class FramePoolFn(torch.autograd.Function):
         part = torch.empty((S, D), dtype=torch.float32, device=seq.device)        # per-sequence shares of dw, folded in a fixed order
         L.check(L.lib().hero_frame_pool_bwd(L.ptr(seq), L.ptr(mask), L.ptr(_flat(w)), L.ptr(att), L.ptr(_f32c(dpooled)), L.ptr(dx),
                                             L.ptr(part), S, Lf, Lt, D, L.dt(seq), L.stream()))
-        if HF._is_param(w):
-            HF.k_colsum(part, out=HF.SINK.dst(w).view(-1), beta=1.0, on_done=lambda: HF.SINK.done(w))
-            dw = None
-        else:
-            dw = HF.k_colsum(part).view_as(w) if w.requires_grad else None
-        return dx, None, dw, None
+        return dx, None, HF.fold_param_shares(part, w), None
 
 
 class BceHeadFn(torch.autograd.Function):
@@ -110,11 +105,7 @@ class BceHeadFn(torch.autograd.Function):
         dw, db = dwb[:K], dwb[K:K + 1]
         L.check(L.lib().hero_bce_head_bwd(L.ptr(h), L.ptr(_flat(w2)), L.ptr(logits), L.ptr(targets), L.ptr(_f32c(dloss).view(1)),
                                           L.ptr(dh), L.ptr(dw), L.ptr(db), S, K, L.dt(h), L.stream()))
-        if HF._is_param(w2):
-            HF.k_colsum(dw.view(1, K), out=HF.SINK.dst(w2).view(-1), beta=1.0, on_done=lambda: HF.SINK.done(w2))
-            gw = None
-        else:
-            gw = dw.view_as(w2) if w2.requires_grad else None
+        gw = HF.fold_param_shares(dw.view(1, K), w2)
         if HF._is_param(b2):                                                      # one float: hero_colsum takes widths that are multiples of 4
             HF.SINK.dst(b2).view(-1).add_(db)
             HF.SINK.done(b2)

@@ -518,10 +518,8 @@ def test_wgrad_queue_flushes_at_whole_round_points(monkeypatch):
     layer = [(768, 3072), (3072, 768), (768, 768), (2304, 768)]          # 64 + 64 + 16 + 48 tiles of 192 x 192
 
     def queue(shapes, nbytes):
-        q = [(None, types.SimpleNamespace(shape=(1, k)), None, 0, n, None, None, None) for n, k in shapes]
-        monkeypatch.setattr(HF, "_WQ", q)
-        monkeypatch.setattr(HF, "_WQ_BYTES", [nbytes])
-        return HF._wgrad_queue_full(dev)
+        jobs = [HF.WgradJob(None, types.SimpleNamespace(shape=(1, k)), None, 0, n, None, None, None) for n, k in shapes]
+        return HF._wgrad_queue_full(jobs, nbytes, dev)
 
     assert not queue(layer, 5 << 20)                       # under the soft cap
     assert not queue(layer, 20 << 20)                      # 192 tiles: 3/4 of a round - wait for more

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Same-process A/B of a functional.* lab switch on the replayed D2 / D2r micro-step: alternating, twice, 60 steps each.
-python tools/lab/ab_switch.py NAME VALUE_A VALUE_B   (e.g. B1_PARTIALS 1 0)"""
+python tools/lab/ab_switch.py NAME VALUE_A VALUE_B   (e.g. WGRAD_RIDE_MAX_ROWS 1073741824 0)"""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

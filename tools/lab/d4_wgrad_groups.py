@@ -44,11 +44,11 @@ def plan_logged(probs, n, rows, device):
 
 
 def _WQB():
-    return HF._WQ_BYTES[0] >> 20
+    return HF._WQ.nbytes >> 20
 
 
 if "noride" in sys.argv:
-    HF.WGRAD_DBIAS_RIDE[0] = False                   # bias sums as column sums of their own instead of riding on the loader waves
+    HF.WGRAD_RIDE_MAX_ROWS[0] = 0                    # bias sums as column sums of their own instead of riding on the loader waves
 HF._wgrad_plan = plan_logged
 _wf = HF.wgrad_flush
 

@@ -30,7 +30,7 @@ def main():
     arena.done = dbg_done
     orig_flush = HF.wgrad_flush
     def dbg_flush():
-        log.append(("FLUSH", len(HF._WQ), [tuple(e[2].shape) for e in HF._WQ]))
+        log.append(("FLUSH", len(HF._WQ.jobs), [tuple(j.out.shape) for j in HF._WQ.jobs]))
         return orig_flush()
     HF.wgrad_flush = dbg_flush
     batch = make_batch("D1", vfeat_dim=96, vocab=160, seed=1 + rank, device=dev)
