@@ -798,16 +798,16 @@ struct ProfSlot {
   std::vector<hipEvent_t> ev;  // start/stop pairs
   std::vector<double> flops;
 };
-static ProfSlot g_prof[11];   // 0-7: (dtype, layouts) of the 4-wave kernels; 8 / 9: wave-specialised 192 x 192 K,K / O,O kernels; 10: 128 x 192 K,K
+static ProfSlot g_prof[PROF_SLOTS];   // GemmProfSlot (gemm_route.h)
 static bool g_prof_on = false;
-static int g_force_cfg = -1;   // tuning hook: force a geometry (0,1,2,3), 8 / 9: wave-specialised kernels never / always; -1 = heuristic
+static GemmForce g_force;             // tuning hook: hero_gemm_force_config, decoded
 
-int gemm_forced_config() { return g_force_cfg; }
+const GemmForce& gemm_force() { return g_force; }
 
 struct ProfToken { ProfSlot* ps; hipEvent_t e0; };
 void* gemm_prof_begin(int slot, hipStream_t s) {
   if (!g_prof_on) return nullptr;
-  ProfSlot* ps = &g_prof[slot < 11 ? slot : 0];
+  ProfSlot* ps = &g_prof[slot < PROF_SLOTS ? slot : 0];
   hipEvent_t e0 = nullptr;
   if (ps->flops.size() >= 16384 || hipEventCreate(&e0) != hipSuccess) return nullptr;
   (void)hipEventRecord(e0, s);
@@ -825,121 +825,58 @@ void gemm_prof_end(void* token, double flops, hipStream_t s) {
   }
   delete t;
 }
-static int g_group = 0;        // tuning hook: M-tiles per locality group (0 = heuristic)
 
 typedef Cfg<2, 2, 2, 2> Cfg128;
 typedef Cfg<2, 4, 4, 2> Cfg256;
 typedef Cfg<2, 2, 3, 2> Cfg192;    // 192x128: 20 % more FLOP per staged byte, 2 x 80 KB = the whole LDS of a CU
 typedef Cfg<2, 2, 1, 1> Cfg64;     // 64x64 tiles for problems that leave most CUs idle at 128x128
 
-// the launch of a 4-wave kernel: one workgroup of NT threads per (tile of CF, reduction split); slot: see g_prof
-template <typename CF>
-static int launch_tiles(void (*kernel)(GemmArgs), GemmArgs g, int nt, int lds, int slot, const char* what, hipStream_t s) {
-  g.tiles_m = (g.M + CF::BM - 1) / CF::BM;
-  g.tiles_n = (g.N + CF::BN - 1) / CF::BN;
-  const int split = g.epi.split_k > 1 ? g.epi.split_k : 1;
-  const int grid = g.tiles_m * g.tiles_n * split;
-  void* tok = gemm_prof_begin(slot, s);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(nt), lds, s, g);
-  gemm_prof_end(tok, 2.0 * (double)g.M * (double)g.N * (double)g.K, s);
-  return check_launch(what);
+template <typename CF> constexpr bool tile4_is(int i) {
+  return GEMM_TILE4[i].bm == CF::BM && GEMM_TILE4[i].bn == CF::BN && GEMM_TILE4[i].threads == CF::NT &&
+         tile4_staged_lds(GEMM_TILE4[i]) == CF::LDS && tile4_glds_lds(GEMM_TILE4[i]) == GldsRing<CF>::LDS;
 }
+static_assert(tile4_is<Cfg128>(0) && tile4_is<Cfg192>(1) && tile4_is<Cfg256>(2) && tile4_is<Cfg64>(3), "gemm_route.h");
 
-template <typename T, int AL, int BL, typename CF>
-static int launch(const GemmArgs& g, hipStream_t s) {
-  HERO_ENSURE_LDS((&gemm_kernel<T, AL, BL, CF>), CF::LDS, "gemm_kernel");
-  return launch_tiles<CF>(gemm_kernel<T, AL, BL, CF>, g, CF::NT, CF::LDS, (sizeof(T) == 2 ? 4 : 0) + AL * 2 + BL, "hero_gemm", s);
-}
+// (family, dtype, layouts, tile, EK) of a route -> the instantiation.  Nothing is decided here (gemm_route.h).
+struct Entry4 { int family, dtype, al, bl, bm, bn, ek; void (*kernel)(GemmArgs); std::atomic<uint64_t> lds_ok; };
+// One list, expanded twice: explicit instantiations (hipcc emits no host stub for a kernel template whose address is only
+// taken in an initialiser) and the table rows.
+#define HERO_GLDS_LIST(X, CF)                                                                                              \
+  X(bf16_t, HERO_BF16, CF, EK_GENERIC) X(bf16_t, HERO_BF16, CF, 0) X(bf16_t, HERO_BF16, CF, EK_BIAS)                       \
+  X(bf16_t, HERO_BF16, CF, EK_BIAS | EK_RES | EK_DROP) X(bf16_t, HERO_BF16, CF, EK_BIAS | EK_GELU) X(bf16_t, HERO_BF16, CF, EK_RES) \
+  X(bf16_t, HERO_BF16, CF, EK_GELU_BWD) X(float, HERO_F32, CF, EK_GENERIC)
+#define HERO_STAGED_LIST(X, T, DT, CF)                                                                  \
+  X(T, DT, HERO_LAYOUT_K, HERO_LAYOUT_K, CF) X(T, DT, HERO_LAYOUT_K, HERO_LAYOUT_O, CF) X(T, DT, HERO_LAYOUT_O, HERO_LAYOUT_K, CF) \
+  X(T, DT, HERO_LAYOUT_O, HERO_LAYOUT_O, CF)
+#define HERO_4WAVE_LIST(G, S)                                                                           \
+  HERO_GLDS_LIST(G, Cfg128) HERO_GLDS_LIST(G, Cfg192) HERO_GLDS_LIST(G, Cfg256) HERO_GLDS_LIST(G, Cfg64)   \
+  HERO_STAGED_LIST(S, bf16_t, HERO_BF16, Cfg128) HERO_STAGED_LIST(S, bf16_t, HERO_BF16, Cfg256)         \
+  HERO_STAGED_LIST(S, float, HERO_F32, Cfg128) HERO_STAGED_LIST(S, float, HERO_F32, Cfg256)
+#define HERO_GLDS_INST(T, DT, CF, EK) template __global__ void gemm_glds_kernel<T, CF, EK>(GemmArgs);
+#define HERO_STAGED_INST(T, DT, AL, BL, CF) template __global__ void gemm_kernel<T, AL, BL, CF>(GemmArgs);
+HERO_4WAVE_LIST(HERO_GLDS_INST, HERO_STAGED_INST)
+#define HERO_GLDS_ROW(T, DT, CF, EK) {GEMM_GLDS_KK, DT, HERO_LAYOUT_K, HERO_LAYOUT_K, CF::BM, CF::BN, EK, gemm_glds_kernel<T, CF, EK>, {0}},
+#define HERO_STAGED_ROW(T, DT, AL, BL, CF) {GEMM_STAGED, DT, AL, BL, CF::BM, CF::BN, EK_GENERIC, gemm_kernel<T, AL, BL, CF>, {0}},
+static Entry4 g_table4[] = {HERO_4WAVE_LIST(HERO_GLDS_ROW, HERO_STAGED_ROW)
+                            {GEMM_GLDS_OO, HERO_BF16, HERO_LAYOUT_O, HERO_LAYOUT_O, 128, 128, EK_GENERIC, gemm_glds_tr_kernel, {0}}};
 
-// Geometry choice (measured on MI355X, tools/gemm_bench.py): the 128x128 tile with two resident
-// workgroups per CU is the best or within a few % of the best on every shape of the HERO step; the
-// 256x256 tile wins ~5 % on the largest K-contiguous problems only.
-static int pick_cfg(int M, int N, int split, bool k_contig) {
-  if (g_force_cfg >= 0 && g_force_cfg < 8) return g_force_cfg;
-  if (!k_contig || split != 1) return 0;
-  const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
-  if (t128 <= 192) return 3;                                                // under one 128^2 tile per CU
-  // a little over ONE round of the 512 resident slots (N = 768 at M = 12000: 564 tiles): 192x128 tiles
-  // fit in a single round (378) - measured 12-18 % faster there, 5 % slower where 128^2 needs 3+ rounds
-  if (t128 > 512 && t128 <= 700 && (long long)((M + 191) / 192) * ((N + 127) / 128) <= 512) return 1;
-  // one 256x256 workgroup per CU: only worth it when the tiles fill whole rounds of the 256 CUs
-  const long long tiles = (long long)((M + 255) / 256) * ((N + 255) / 256);
-  const long long rounds = (tiles + 255) / 256;
-  return (tiles >= 256 && tiles * 10 >= rounds * 256 * 9) ? 2 : 0;
-}
-
-static int g_use_glds = 1;   // tuning hook
-
-// explicit instantiations (hipcc does not emit the host stubs for kernels that are only reached
-// through two levels of host-side templates)
-#define HERO_GLDS_INST(T, CF)                                                       \
-  template __global__ void gemm_glds_kernel<T, CF, EK_GENERIC>(GemmArgs);           \
-  template __global__ void gemm_glds_kernel<T, CF, 0>(GemmArgs);                    \
-  template __global__ void gemm_glds_kernel<T, CF, EK_BIAS>(GemmArgs);              \
-  template __global__ void gemm_glds_kernel<T, CF, EK_BIAS | EK_RES | EK_DROP>(GemmArgs); \
-  template __global__ void gemm_glds_kernel<T, CF, EK_BIAS | EK_GELU>(GemmArgs);    \
-  template __global__ void gemm_glds_kernel<T, CF, EK_RES>(GemmArgs);               \
-  template __global__ void gemm_glds_kernel<T, CF, EK_GELU_BWD>(GemmArgs);
-HERO_GLDS_INST(bf16_t, Cfg128)
-HERO_GLDS_INST(bf16_t, Cfg256)
-HERO_GLDS_INST(bf16_t, Cfg64)
-HERO_GLDS_INST(bf16_t, Cfg192)
-template __global__ void gemm_glds_kernel<float, Cfg192, EK_GENERIC>(GemmArgs);
-template __global__ void gemm_glds_kernel<float, Cfg64, EK_GENERIC>(GemmArgs);
-template __global__ void gemm_glds_kernel<float, Cfg128, EK_GENERIC>(GemmArgs);
-template __global__ void gemm_glds_kernel<float, Cfg256, EK_GENERIC>(GemmArgs);
-
-template <typename T, typename CF, int EK>
-static int launch_glds_ek(const GemmArgs& g, hipStream_t s) {
-  HERO_ENSURE_LDS((&gemm_glds_kernel<T, CF, EK>), GldsRing<CF>::LDS, "gemm_glds_kernel");
-  return launch_tiles<CF>(gemm_glds_kernel<T, CF, EK>, g, CF::NT, GldsRing<CF>::LDS, sizeof(T) == 2 ? 4 : 0, "hero_gemm(glds)", s);
-}
-
-// epilogue specialisation: the hot-path combinations of the bf16 training step get their own
-// instantiation, everything else (and all of f32) the generic one
-template <typename T, typename CF>
-static int launch_glds(const GemmArgs& g, hipStream_t s) {
-  const HeroGemmEpilogue& e = g.epi;
-  if constexpr (sizeof(T) == 2) if (!e.out_f32 && e.split_k <= 1) {
-    const bool b = e.bias != nullptr, r = e.residual != nullptr, d = e.dropout.threshold16 != 0;
-    if (e.act == HERO_ACT_NONE && b && !r && !d) return launch_glds_ek<T, CF, EK_BIAS>(g, s);
-    if (e.act == HERO_ACT_NONE && b && r) return launch_glds_ek<T, CF, EK_BIAS | EK_RES | EK_DROP>(g, s);
-    if ((e.act == HERO_ACT_GELU || e.act == HERO_ACT_GELU_DG) && b && !r && !d) return launch_glds_ek<T, CF, EK_BIAS | EK_GELU>(g, s);
-    if (e.act == HERO_ACT_NONE && !b && !r && !d) return launch_glds_ek<T, CF, 0>(g, s);
-    if (e.act == HERO_ACT_NONE && !b && r && !d) return launch_glds_ek<T, CF, EK_RES>(g, s);
-    if ((e.act == HERO_ACT_GELU_BWD || e.act == HERO_ACT_MUL_AUX) && !b && !r && !d) return launch_glds_ek<T, CF, EK_GELU_BWD>(g, s);
+// the launch of a 4-wave kernel: one workgroup per (tile, reduction split)
+static int launch_tiles(const GemmRoute& r, GemmArgs g, int al, int bl, int dtype, hipStream_t s) {
+  static const char* const kernel_name[] = {"", "", "", "", "gemm_glds_kernel", "gemm_glds_tr_kernel", "gemm_kernel"};
+  static const char* const what[] = {"", "", "", "", "hero_gemm(glds)", "hero_gemm(glds_tr)", "hero_gemm"};
+  for (Entry4& e : g_table4) {
+    if (e.family != r.family || e.dtype != dtype || e.al != al || e.bl != bl || e.bm != r.tile_m || e.bn != r.tile_n || e.ek != r.ek) continue;
+    g.tiles_m = r.tiles_m; g.tiles_n = r.tiles_n; g.k_per_split = r.k_per_split; g.group = r.group;
+    g.epi.split_k = r.splits;
+    const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(e.kernel), r.lds, e.lds_ok, kernel_name[r.family]);
+    if (rc != HERO_OK) return rc;
+    void* tok = gemm_prof_begin(r.slot, s);
+    hipLaunchKernelGGL(e.kernel, dim3(r.grid), dim3(r.threads), r.lds, s, g);
+    gemm_prof_end(tok, r.flops, s);
+    return check_launch(what[r.family]);
   }
-  return launch_glds_ek<T, CF, EK_GENERIC>(g, s);
-}
-
-static int launch_glds_tr(const GemmArgs& g, hipStream_t s) {
-  HERO_ENSURE_LDS(&gemm_glds_tr_kernel, 65536, "gemm_glds_tr_kernel");
-  return launch_tiles<Cfg128>(gemm_glds_tr_kernel, g, 256, 65536, 7, "hero_gemm(glds_tr)", s);
-}
-
-template <typename T, int AL, int BL>
-static int launch_cfg(const GemmArgs& g, int cfg, hipStream_t s) {
-  if (AL == HERO_LAYOUT_O && BL == HERO_LAYOUT_O && sizeof(T) == 2 && g_use_glds && g.K > 0 && g.k_per_split % 64 == 0)
-    return launch_glds_tr(g, s);
-  if (AL == HERO_LAYOUT_K && BL == HERO_LAYOUT_K && g_use_glds && g.K > 0 && g.K % Tr<T>::BK == 0 &&
-      g.k_per_split % Tr<T>::BK == 0) {
-    if (cfg == 2) return launch_glds<T, Cfg256>(g, s);
-    if (cfg == 3) return launch_glds<T, Cfg64>(g, s);
-    if (cfg == 1) return launch_glds<T, Cfg192>(g, s);
-    return launch_glds<T, Cfg128>(g, s);
-  }
-  if (cfg == 2) return launch<T, AL, BL, Cfg256>(g, s);
-  return launch<T, AL, BL, Cfg128>(g, s);
-}
-
-template <typename T>
-static int dispatch(const GemmArgs& g, int al, int bl, int cfg, hipStream_t s) {
-  if (al == HERO_LAYOUT_K && bl == HERO_LAYOUT_K) return launch_cfg<T, HERO_LAYOUT_K, HERO_LAYOUT_K>(g, cfg, s);
-  if (al == HERO_LAYOUT_K && bl == HERO_LAYOUT_O) return launch_cfg<T, HERO_LAYOUT_K, HERO_LAYOUT_O>(g, cfg, s);
-  if (al == HERO_LAYOUT_O && bl == HERO_LAYOUT_O) return launch_cfg<T, HERO_LAYOUT_O, HERO_LAYOUT_O>(g, cfg, s);
-  if (al == HERO_LAYOUT_O && bl == HERO_LAYOUT_K) return launch_cfg<T, HERO_LAYOUT_O, HERO_LAYOUT_K>(g, cfg, s);
-  set_error("hero_gemm: bad layout (%d, %d)", al, bl);
-  return HERO_ERR_ARG;
+  set_error("hero_gemm: no 4-wave kernel for family %d, tile %d x %d, epilogue kind %d", r.family, r.tile_m, r.tile_n, r.ek);
+  return HERO_ERR_UNSUPPORTED;
 }
 
 }  // namespace hero
@@ -1059,20 +996,12 @@ __global__ __launch_bounds__(256) void gemm_skinny_f32_kernel(const float* __res
   }
 }
 
-// Reduction splits a request for split_k gets: at most one per k-tile, rounded so that no split is empty (*per: k-tiles each).
-static int split_count(int K, int split_k, int bk, int* per) {
-  const int ktiles = (K + bk - 1) / bk;
-  int split = split_k < ktiles ? split_k : ktiles;
-  if (split <= 1) return 1;
-  *per = (ktiles + split - 1) / split;
-  return (ktiles + *per - 1) / *per;
-}
-
-extern "C" int hero_gemm(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
-                         int a_layout, int b_layout, int dtype, const HeroGemmEpilogue* epi, hero_stream_t stream) {
-  HERO_REQUIRE(A && B && C && epi, "hero_gemm: null pointer");
+// The shape checks of hero_gemm (*empty: nothing to compute); with A == nullptr the pointer checks are left out (hero_gemm_route).
+static int check_problem(const void* A, const void* B, const void* C, int M, int N, int K, int lda, int ldb, int ldc, int a_layout,
+                         int b_layout, int dtype, const HeroGemmEpilogue* epi, bool* empty) {
   HERO_REQUIRE(dtype == HERO_F32 || dtype == HERO_BF16, "hero_gemm: bad dtype %d", dtype);
-  if (M <= 0 || N <= 0) return HERO_OK;
+  *empty = M <= 0 || N <= 0;
+  if (*empty) return HERO_OK;
   HERO_REQUIRE(K >= 0, "hero_gemm: K < 0");
   const int vec = dtype == HERO_BF16 ? 8 : 4;
   HERO_REQUIRE(N % 4 == 0 && ldc % 4 == 0, "hero_gemm: N (%d) and ldc (%d) must be multiples of 4", N, ldc);
@@ -1081,59 +1010,63 @@ extern "C" int hero_gemm(const void* A, const void* B, void* C, int M, int N, in
                "hero_gemm: A contiguous dim must be a multiple of %d (M=%d K=%d layout=%d)", vec, M, K, a_layout);
   HERO_REQUIRE(b_layout == HERO_LAYOUT_K ? K % vec == 0 : N % vec == 0,
                "hero_gemm: B contiguous dim must be a multiple of %d (N=%d K=%d layout=%d)", vec, N, K, b_layout);
-  HERO_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0, "hero_gemm: operands must be 16-byte aligned");
-  HERO_REQUIRE(!epi->residual || (((uintptr_t)epi->residual) & 7) == 0, "hero_gemm: residual misaligned");
+  if (A) {
+    HERO_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0, "hero_gemm: operands must be 16-byte aligned");
+    HERO_REQUIRE(!epi->residual || (((uintptr_t)epi->residual) & 7) == 0, "hero_gemm: residual misaligned");
+  }
   HERO_REQUIRE(!(epi->act == HERO_ACT_GELU || epi->act == HERO_ACT_GELU_BWD || epi->act == HERO_ACT_RELU_BWD || epi->act == HERO_ACT_GELU_DG ||
                  epi->act == HERO_ACT_MUL_AUX) || epi->aux,
                "hero_gemm: activation %d needs aux", epi->act);
   HERO_REQUIRE(!epi->colsum || (epi->split_k <= 1 && !epi->out_f32), "hero_gemm: epilogue.colsum excludes split_k / out_f32");
   HERO_REQUIRE(epi->split_stride == 0 || (epi->split_k > 1 && epi->split_stride >= (long long)(M - 1) * ldc + N),
                "hero_gemm: split_stride needs split_k > 1 and slabs that hold [M, ldc]");
+  // (the wave-specialised O,O kernel takes split_k as a hint; what it accepts passes this check)
+  HERO_REQUIRE(epi->split_k <= 1 || (epi->out_f32 && epi->act == HERO_ACT_NONE && !epi->bias && !epi->residual && epi->dropout.threshold16 == 0),
+               "hero_gemm: split_k supports only a plain fp32 accumulate epilogue");
+  HERO_REQUIRE((unsigned)a_layout <= 1u && (unsigned)b_layout <= 1u, "hero_gemm: bad layout (%d, %d)", a_layout, b_layout);
+  return HERO_OK;
+}
+
+// validate, route, pre-scale, launch
+extern "C" int hero_gemm(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
+                         int a_layout, int b_layout, int dtype, const HeroGemmEpilogue* epi, hero_stream_t stream) {
+  HERO_REQUIRE(A && B && C && epi, "hero_gemm: null pointer");
+  bool empty = false;
+  const int bad = check_problem(A, B, C, M, N, K, lda, ldb, ldc, a_layout, b_layout, dtype, epi, &empty);
+  if (bad || empty) return bad;
+  const GemmRoute r = gemm_route(M, N, K, lda, ldb, ldc, a_layout, b_layout, dtype, *epi, g_force, num_cus());
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (r.prescale) {
+    const int rc = gemm_scale_f32(static_cast<float*>(C), M, N, ldc, epi->beta, s);
+    if (rc) return rc;
+  }
+  if (r.family == GEMM_WS_KK || r.family == GEMM_WS_OO) return gemm_ws_launch(r, A, B, C, M, N, K, lda, ldb, ldc, *epi, s);
+  if (r.family == GEMM_SKINNY_F32) {
+    HERO_ENSURE_LDS(&gemm_skinny_f32_kernel, 32 * 1024 * 4 + 16, "gemm_skinny_f32_kernel");
+    void* tok = gemm_prof_begin(r.slot, s);
+    hipLaunchKernelGGL(gemm_skinny_f32_kernel, dim3(r.grid), dim3(r.threads), r.lds, s, static_cast<const float*>(A), static_cast<const float*>(B),
+                       static_cast<float*>(C), epi->bias, M, N, K, lda, ldb, ldc);
+    gemm_prof_end(tok, r.flops, s);
+    return check_launch("hero_gemm(skinny f32)");
+  }
   GemmArgs g;
   g.A = A; g.B = B; g.C = C;
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.tiles_m = g.tiles_n = 0;
-  // M-tiles per L2 locality group (tools/gemm_group_sweep.py): wide outputs like 16 (N = 3072: -4 %),
-  // narrow ones 4 (N = 768: -2 %), 8 in between
-  g.group = g_group ? g_group : (N >= 2560 ? 16 : (N <= 1024 ? 4 : 8));
   g.epi = *epi;
-  const int bk = dtype == HERO_BF16 ? 64 : 32;
-  const bool k_contig = a_layout == HERO_LAYOUT_K && b_layout == HERO_LAYOUT_K;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == HERO_F32 && k_contig && M <= 32 && K >= 256 && g_force_cfg == -1 && epi->act == HERO_ACT_NONE && !epi->residual && !epi->colsum &&
-      !epi->out_f32 && epi->split_k <= 1 && epi->dropout.threshold16 == 0) {
-    void* tok = gemm_prof_begin(3, s);
-    const int lds = 32 * (K < 1024 ? K : 1024) * 4 + 16;       // + the dummy slot of the copy
-    HERO_ENSURE_LDS(&gemm_skinny_f32_kernel, 32 * 1024 * 4 + 16, "gemm_skinny_f32_kernel");
-    hipLaunchKernelGGL(gemm_skinny_f32_kernel, dim3((N + 7) / 8), dim3(256), lds, s, static_cast<const float*>(A), static_cast<const float*>(B),
-                       static_cast<float*>(C), epi->bias, M, N, K, lda, ldb, ldc);
-    gemm_prof_end(tok, 2.0 * (double)M * (double)N * (double)K, s);
-    return check_launch("hero_gemm(skinny f32)");
-  }
-  if (dtype == HERO_BF16) {        // large problems: wave-specialised persistent 192 x 192 tiles (gemm_ws.hip)
-    const int rc = gemm_ws_run(A, B, C, M, N, K, lda, ldb, ldc, a_layout, b_layout, *epi, g_force_cfg, s);
-    if (rc != -1) return rc;
-  }
-  if (epi->split_k > 1) {
-    HERO_REQUIRE(epi->out_f32 && epi->act == HERO_ACT_NONE && !epi->bias && !epi->residual && epi->dropout.threshold16 == 0,
-                 "hero_gemm: split_k supports only a plain fp32 accumulate epilogue");
-    int per = 0;
-    const int split = split_count(K, epi->split_k, bk, &per);
-    if (split > 1) {
-      if (epi->split_stride == 0 && epi->beta != 1.f) {  // atomics accumulate into beta * C (slabs are overwritten)
-        const int rc = gemm_scale_f32(static_cast<float*>(C), M, N, ldc, epi->beta, s);
-        if (rc) return rc;
-      }
-      g.k_per_split = per * bk;
-      g.epi.split_k = split;
-      const int cfg = pick_cfg(M, N, split, k_contig);
-      return dtype == HERO_BF16 ? dispatch<bf16_t>(g, a_layout, b_layout, cfg, s) : dispatch<float>(g, a_layout, b_layout, cfg, s);
-    }
-  }
-  g.k_per_split = K > 0 ? ((K + bk - 1) / bk) * bk : bk;
-  g.epi.split_k = 1;
-  const int cfg = pick_cfg(M, N, 1, k_contig);
-  return dtype == HERO_BF16 ? dispatch<bf16_t>(g, a_layout, b_layout, cfg, s) : dispatch<float>(g, a_layout, b_layout, cfg, s);
+  return launch_tiles(r, g, a_layout, b_layout, dtype, s);
+}
+
+// The route hero_gemm would take right now, as HERO_GEMM_ROUTE_WORDS int32 words (hero_hip.h); no device work.
+extern "C" int hero_gemm_route(int M, int N, int K, int lda, int ldb, int ldc, int a_layout, int b_layout, int dtype,
+                               const HeroGemmEpilogue* epi, int32_t* out, int capacity_words) {
+  HERO_REQUIRE(epi && out && capacity_words >= HERO_GEMM_ROUTE_WORDS, "hero_gemm_route: null pointer or fewer than %d words", HERO_GEMM_ROUTE_WORDS);
+  bool empty = false;
+  const int bad = check_problem(nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc, a_layout, b_layout, dtype, epi, &empty);
+  if (bad) return bad;
+  const GemmRoute r = gemm_route(M, N, K, lda, ldb, ldc, a_layout, b_layout, dtype, *epi, g_force, num_cus());
+  const int32_t words[HERO_GEMM_ROUTE_WORDS] = {r.family, r.tile_m, r.tile_n, r.ek, r.grid, r.threads, r.lds, r.splits, r.k_per_split, r.group, r.prescale, r.slot};
+  for (int i = 0; i < HERO_GEMM_ROUTE_WORDS; ++i) out[i] = words[i];
+  return HERO_GEMM_ROUTE_WORDS;
 }
 
 extern "C" int hero_gemm_splits(int K, int split_k, int dtype) {
@@ -1141,22 +1074,14 @@ extern "C" int hero_gemm_splits(int K, int split_k, int dtype) {
   return split_count(K, split_k, dtype == HERO_BF16 ? 64 : 32, &per);
 }
 
-// Tuning hook: force a tile geometry (0: 128x128, 1: 192x128, 2: 256x256, 3: 64x64 [1 and 3: direct-to-LDS path only], -1: heuristic).
+// Tuning hook (hero_hip.h has the table of values); decoded once, here.
 extern "C" int hero_gemm_force_config(int cfg) {
-  if (cfg >= 8 && cfg <= 14 && cfg != 11 && cfg != 12) {     // wave-specialised kernels: 8 never, 9 / 10 always 192 x 192 / 128 x 192, 13 / 14 the 64 x 128 / 64 x 192 geometries (small-M, long-K GEMMs)
-    g_force_cfg = cfg;
-    g_use_glds = 1;
-    g_group = 0;
-    return HERO_OK;
-  }
-  g_force_cfg = cfg >= 0 ? (cfg & 3) : -1;
-  g_use_glds = cfg >= 0 ? !(cfg & 4) : 1;      // bit 2 set: register staging even for K,K operands
-  g_group = cfg >= 0 ? (cfg >> 8) : 0;         // bits 8+: M-tiles per locality group (0 = heuristic)
+  g_force = decode_force(cfg);
   return HERO_OK;
 }
 
 // Per-launch timing of the GEMM kernels with HIP events on the launch stream (used by bench.py
-// for the roofline leg). slot = (dtype == BF16 ? 4 : 0) + a_layout * 2 + b_layout.
+// for the roofline leg). slot: GemmProfSlot.
 extern "C" int hero_prof_enable(int on) {
   for (auto& p : g_prof) {
     for (hipEvent_t e : p.ev) (void)hipEventDestroy(e);
@@ -1167,7 +1092,7 @@ extern "C" int hero_prof_enable(int on) {
   return HERO_OK;
 }
 extern "C" int hero_prof_read(int slot, double* total_ms, double* total_flops, long long* launches) {
-  HERO_REQUIRE(slot >= 0 && slot < 11 && total_ms && total_flops && launches, "hero_prof_read: bad arguments");
+  HERO_REQUIRE(slot >= 0 && slot < PROF_SLOTS && total_ms && total_flops && launches, "hero_prof_read: bad arguments");
   ProfSlot& p = g_prof[slot];
   double ms = 0.0, fl = 0.0;
   for (size_t i = 0; i < p.flops.size(); ++i) {

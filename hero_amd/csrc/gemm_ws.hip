@@ -491,50 +491,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-// explicit instantiations (hipcc does not emit the host stubs of kernels that are only reached through two
-// levels of host-side templates)
-#define HERO_WS_INST(TM, TN)                                                                  \
-  template __global__ void gemm_ws_kernel<TM, TN, false, 0>(WsArgs);                          \
-  template __global__ void gemm_ws_kernel<TM, TN, false, EK_BIAS>(WsArgs);                    \
-  template __global__ void gemm_ws_kernel<TM, TN, false, EK_BIAS | EK_RES | EK_DROP>(WsArgs); \
-  template __global__ void gemm_ws_kernel<TM, TN, false, EK_BIAS | EK_GELU>(WsArgs);          \
-  template __global__ void gemm_ws_kernel<TM, TN, false, EK_RES>(WsArgs);                     \
-  template __global__ void gemm_ws_kernel<TM, TN, false, EK_GELU_BWD>(WsArgs);                \
-  template __global__ void gemm_ws_kernel<TM, TN, true, 0>(WsArgs);
-HERO_WS_INST(3, 3)
-HERO_WS_INST(2, 3)
-
 // ------------------------------------------------------------------------------------------------
-// host side
+// host side: (geometry, transposed, EK) of a route -> the instantiation.  Nothing is decided here (gemm_route.h).
 // ------------------------------------------------------------------------------------------------
-template <int TM, int TN, bool TR, int EK>
-static int launch(WsArgs g, int slot, hipStream_t s) {
-  typedef Geo<TM, TN> G;
-  HERO_ENSURE_LDS((&gemm_ws_kernel<TM, TN, TR, EK>), G::LDS, "gemm_ws_kernel");
-  const int grid = g.nwork < num_cus() ? g.nwork : num_cus();
-  void* tok = gemm_prof_begin(slot, s);
-  hipLaunchKernelGGL((gemm_ws_kernel<TM, TN, TR, EK>), dim3(grid), dim3(512), G::LDS, s, g);
-  gemm_prof_end(tok, 2.0 * (double)g.M * (double)g.N * (double)g.K, s);
-  return check_launch("hero_gemm(ws)");
-}
-
-template <int TM, int TN>
-static int launch_kk(const WsArgs& g, hipStream_t s) {
-  const HeroGemmEpilogue& e = g.epi;
-  const bool b = e.bias != nullptr, r = e.residual != nullptr, d = e.dropout.threshold16 != 0;
-  if (e.colsum != nullptr && e.act != HERO_ACT_GELU_BWD && e.act != HERO_ACT_MUL_AUX) return -1;     // column sums exist in the gelu' epilogue only: 4-wave path
-  if (e.act == HERO_ACT_NONE && b && !r && !d) return launch<TM, TN, false, EK_BIAS>(g, TM == 3 ? 8 : 10, s);
-  if (e.act == HERO_ACT_NONE && b && r) return launch<TM, TN, false, EK_BIAS | EK_RES | EK_DROP>(g, TM == 3 ? 8 : 10, s);
-  if ((e.act == HERO_ACT_GELU || e.act == HERO_ACT_GELU_DG) && b && !r && !d) return launch<TM, TN, false, EK_BIAS | EK_GELU>(g, TM == 3 ? 8 : 10, s);
-  if (e.act == HERO_ACT_RELU && b && !r && !d && e.aux) return launch<TM, TN, false, EK_BIAS | EK_GELU>(g, TM == 3 ? 8 : 10, s);
-  if constexpr (TM == 1) {         // LinearLayer (frame_transform, model/layers.py:86-93 + model/model.py:211-212): relu(x W^T + b) + matched features
-    if (e.act == HERO_ACT_RELU && b && r && !d && e.aux) return launch<TM, TN, false, EK_BIAS | EK_GELU | EK_RES>(g, 10, s);
-  }
-  if (e.act == HERO_ACT_NONE && !b && !r && !d) return launch<TM, TN, false, 0>(g, TM == 3 ? 8 : 10, s);
-  if (e.act == HERO_ACT_NONE && !b && r && !d) return launch<TM, TN, false, EK_RES>(g, TM == 3 ? 8 : 10, s);
-  if ((e.act == HERO_ACT_GELU_BWD || e.act == HERO_ACT_MUL_AUX) && !b && !r && !d) return launch<TM, TN, false, EK_GELU_BWD>(g, TM == 3 ? 8 : 10, s);
-  return -1;
-}
+struct WsEntry { int tm, tn; bool tr; int ek; void (*kernel)(WsArgs); std::atomic<uint64_t> lds_ok; };
+// One list, expanded twice: explicit instantiations (hipcc emits no host stub for a kernel template whose address is only
+// taken in an initialiser) and the table rows.  <2, 3, true, 0> is instantiated and reached by no route.
+#define HERO_WS_KK_LIST(X, TM, TN)                                                                                   \
+  X(TM, TN, false, 0) X(TM, TN, false, EK_BIAS) X(TM, TN, false, EK_BIAS | EK_RES | EK_DROP) X(TM, TN, false, EK_BIAS | EK_GELU) \
+  X(TM, TN, false, EK_RES) X(TM, TN, false, EK_GELU_BWD)
+#define HERO_WS_LIST(X)                                                                                              \
+  HERO_WS_KK_LIST(X, 3, 3) X(3, 3, true, 0) HERO_WS_KK_LIST(X, 2, 3) X(2, 3, true, 0)                                   \
+  HERO_WS_KK_LIST(X, 1, 2) X(1, 2, false, EK_BIAS | EK_GELU | EK_RES) HERO_WS_KK_LIST(X, 1, 3) X(1, 3, false, EK_BIAS | EK_GELU | EK_RES)
+#define HERO_WS_INST(TM, TN, TR, EK) template __global__ void gemm_ws_kernel<TM, TN, TR, EK>(WsArgs);
+HERO_WS_LIST(HERO_WS_INST)
+#define HERO_WS_ROW(TM, TN, TR, EK) {TM, TN, TR, EK, gemm_ws_kernel<TM, TN, TR, EK>, {0}},
+static WsEntry g_ws_table[] = {HERO_WS_LIST(HERO_WS_ROW)};
+static_assert(Geo<3, 3>::LDS == WS_LDS && Geo<2, 3>::LDS == WS_LDS && Geo<1, 2>::LDS == WS_LDS && Geo<1, 3>::LDS == WS_LDS, "gemm_route.h");
 
 }  // namespace ws
 
@@ -547,105 +520,26 @@ int num_cus() {
   return n;
 }
 
-// Problems this family takes: bf16, K,K operands with one of the six hot-path epilogues, or the O,O
-// wgrad accumulate; large enough to fill the chip with 192 x 192 (or, under one round, 128 x 192) tiles.
-// force_cfg: -1 heuristic, 8 never, 9 always 192 x 192, 10 always 128 x 192, 13 / 14 always 64 x 128 / 64 x 192 (when the shape
-// is legal).  (Round 4's deferred-epilogue variant - the finished tile parked in the loader waves' registers and drained
-// during the next main loop, bit-exact and 1.0-1.3x SLOWER, profiles/r04_wsd_ab.txt - lives in tools/lab/gemm_wsd.hip.)
-int gemm_ws_run(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, int a_layout,
-                int b_layout, const HeroGemmEpilogue& epi, int force_cfg, hipStream_t s) {
+int gemm_ws_launch(const GemmRoute& r, const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
+                   const HeroGemmEpilogue& epi, hipStream_t s) {
   using namespace ws;
-  if (force_cfg == 8) return -1;
-  if ((force_cfg < 9 || force_cfg > 14 || force_cfg == 11 || force_cfg == 12) && force_cfg != -1) return -1;      // a forced 4-wave geometry
-  typedef Geo<3, 3> G;
-  const bool kk = a_layout == HERO_LAYOUT_K && b_layout == HERO_LAYOUT_K;
-  const bool oo = a_layout == HERO_LAYOUT_O && b_layout == HERO_LAYOUT_O;
-  if (!kk && !oo) return -1;
-  if (K < 64 || N % 8 != 0 || M < 8) return -1;
-  if ((force_cfg == 10 || force_cfg == 13 || force_cfg == 14) && !kk) return -1;
-  WsArgs g;
-  g.A = A; g.B = B; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.tiles_m = (M + G::BM - 1) / G::BM;
-  g.tiles_n = (N + G::BN - 1) / G::BN;
-  g.epi = epi;
-  const int ntile = g.tiles_m * g.tiles_n;
-  const int cus = num_cus();
-  if (kk) {
-    if (K % 64 != 0 || epi.out_f32 || epi.split_k > 1) return -1;
-    // every per-lane offset of this family is relative to its tile (operand panels, residual / saved pre-activation reads,
-    // stores); only the weight matrix B is addressed from its base
-    if ((size_t)N * ldb * 2 >= 0x7fffffffull || (size_t)192 * lda * 2 >= 0x7fffffffull || (size_t)192 * ldc * 2 >= 0x7fffffffull) return -1;
-    g.nsplit = 1;
-    g.k_per_split = K;
-    g.group = 8;
-    // Geometry by rounds: the persistent workgroups walk ceil(tiles / CUs) tiles each, and a 128 x 192 tile (Geo<2, 3>)
-    // costs ~0.75-0.8 of a 192 x 192 one (tools/lab/geo_ab.py: 11 vs 15 us per round at K = 768, 30 vs 40 at K = 3072).
-    // The smaller tile wins where it does not need proportionally more rounds:
-    //  * under one round (M = 1920, N = 3072: 240 instead of 160 tiles; N = 2304: 180 instead of 120);
-    //  * just over a round boundary of the 192 x 192 grid - the usual case of a ragged batch: M = 14450 rows, N = 768
-    //    = 304 tiles = 2 rounds at 59 % against 452 tiles of 128 x 192 = 2 rounds at 88 %: 32.4 -> 25.4 us (K = 768),
-    //    80.7 -> 67.0 (K = 3072).  The bench batch sits ON the boundary (12000 rows x 768 = 252 tiles) and keeps 192 x 192.
-    typedef Geo<2, 3> G2;
-    const int t23 = ((M + G2::BM - 1) / G2::BM) * g.tiles_n;
-    const int r33 = (ntile + cus - 1) / cus, r23 = (t23 + cus - 1) / cus;
-    const bool small = force_cfg == 10 || (force_cfg == -1 && r23 * 4 < r33 * 5 && t23 * 5 >= cus * 2);
-    if (small) {
-      g.tiles_m = (M + G2::BM - 1) / G2::BM;
-      g.nwork = t23;
-      return launch_kk<2, 3>(g, s);
-    }
-    // Under half a round of 192 x 192 tiles - the Temporal Transformer's 1920 rows into N = 768: 40 tiles - the 64-row
-    // geometries: 64 x 128 tiles (180 workgroups, 24 KB per step, a 6-deep ring so that as many bytes are in flight as the
-    // large tiles keep with three stages).  The 4-wave 64 x 64 kernels put 360 workgroups of 16 KB steps on 256 CUs and are
-    // bound by the busiest CU's L2 -> LDS fill (two tiles x 48 steps: 26 us at K = 3072, the vendor library 17.7,
-    // profiles/r04_vs_library.txt); 18.2 us with this geometry, 6.7 vs 8.0 at K = 768 (tools/lab/smallm_ws.py).
-    if (force_cfg == 13 || force_cfg == 14 || (force_cfg == -1 && ntile * 2 < cus && K >= 512)) {
-      typedef Geo<1, 2> G12;
-      const int rows64 = (M + 63) / 64;
-      const int t12 = rows64 * ((N + G12::BN - 1) / G12::BN), t13 = rows64 * g.tiles_n;
-      // 64 x 192 (four stages) where 64 x 128 tiles would spill into a second round: the ragged batch's ~3100 padded frame rows
-      // (49 x 6 = 294 tiles against 49 x 4 = 196); per tile it is ~20 % behind 64 x 128, a partial second round costs more
-      if (force_cfg == 14 || (force_cfg == -1 && t12 > cus && t13 <= cus)) {
-        g.tiles_m = rows64; g.nwork = t13;
-        return launch_kk<1, 3>(g, s);
-      }
-      if (force_cfg == 13 || (t12 * 8 >= cus && t12 <= cus)) {        // down to the 480 query rows (48 tiles: 12.0 vs 13.7 us at K = 2304)
-        g.tiles_m = rows64; g.tiles_n = (N + G12::BN - 1) / G12::BN; g.nwork = t12;
-        return launch_kk<1, 2>(g, s);
-      }
-    }
-    // worth it from about half a round of tiles; below that the 4-wave 64 x 64 / 128 x 128 tiles fill the chip better
-    if (force_cfg != 9 && ntile * 2 < cus) return -1;
-    g.nwork = ntile;
-    return launch_kk<3, 3>(g, s);
+  for (WsEntry& e : g_ws_table) {
+    if (e.tm * 64 != r.tile_m || e.tn * 64 != r.tile_n || e.tr != (r.family == GEMM_WS_OO) || e.ek != r.ek) continue;
+    WsArgs g;
+    g.A = A; g.B = B; g.C = C;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.tiles_m = r.tiles_m; g.tiles_n = r.tiles_n; g.group = r.group;
+    g.nsplit = r.splits; g.k_per_split = r.k_per_split; g.nwork = r.tiles_m * r.tiles_n * r.splits;
+    g.epi = epi;
+    const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(e.kernel), r.lds, e.lds_ok, "gemm_ws_kernel");
+    if (rc != HERO_OK) return rc;
+    void* tok = gemm_prof_begin(r.slot, s);
+    hipLaunchKernelGGL(e.kernel, dim3(r.grid), dim3(r.threads), r.lds, s, g);
+    gemm_prof_end(tok, r.flops, s);
+    return check_launch("hero_gemm(ws)");
   }
-  // O,O: fp32 accumulate, reduction split so that the items fill the CUs
-  if (!epi.out_f32 || epi.act != HERO_ACT_NONE || epi.bias || epi.residual || epi.dropout.threshold16 != 0 || epi.colsum) return -1;
-  if (M % 8 != 0) return -1;
-  if ((size_t)K * lda * 2 >= 0xffffffffull || (size_t)K * ldb * 2 >= 0xffffffffull) return -1;
-  const int ksteps = (K + 63) / 64;
-  // The fp32-atomic merge costs ~split x output bytes at ~1.2 TB/s (measured: 31 us for 4 x 9.4 MB) and is paid
-  // after the last k-step by every item at once: worth it only where few splits fill the chip (>= 64 tiles of
-  // 192 x 192, i.e. the 3072 x 768 weights: 77 vs 84 us); smaller outputs stay on the 128 x 128 kernel's finer
-  // split.  (Tried and dropped: 96 x 96 tiles with the reduction split across the four compute waves of a
-  // workgroup and no cross-workgroup merge - 104 vs 82 us: four times the LDS-DMA bytes per flop, and the
-  // direct-to-LDS path of a CU saturates near 50 GB/s while MFMAs and fragment reads are running.)
-  if (force_cfg != 9 && (ksteps < 32 || ntile < 64)) return -1;
-  int split = cus / ntile;                               // at most one round of items
-  if (split > ksteps / 4) split = ksteps / 4;
-  if (split < 1) split = 1;
-  const int per = (ksteps + split - 1) / split;
-  split = (ksteps + per - 1) / per;
-  g.nsplit = split;
-  g.k_per_split = per * 64;
-  g.nwork = ntile * split;
-  g.group = 8;
-  if (epi.beta != 1.f) {
-    const int rc = gemm_scale_f32(static_cast<float*>(C), M, N, ldc, epi.beta, s);
-    if (rc) return rc;
-  }
-  return launch<3, 3, true, 0>(g, 9, s);
+  set_error("hero_gemm: no wave-specialised kernel for tile %d x %d, epilogue kind %d", r.tile_m, r.tile_n, r.ek);
+  return HERO_ERR_UNSUPPORTED;
 }
 
 }  // namespace hero
@@ -664,7 +558,7 @@ extern "C" int hero_wgrad_group(const HeroWgradProblem* probs, int n, int K, int
   HERO_REQUIRE(dtype == HERO_BF16 || dtype == HERO_F32, "hero_wgrad_group: bad dtype %d", dtype);
   hipStream_t s = static_cast<hipStream_t>(stream);
   typedef Geo<3, 3> G;
-  bool ok = dtype == HERO_BF16 && K >= 64 * 16 && gemm_forced_config() != 8;
+  bool ok = dtype == HERO_BF16 && K >= 64 * 16 && gemm_force().allow_ws;
   WsgArgs g;
   int tiles = 0;
   for (int i = 0; i < n && ok; ++i) {
@@ -689,7 +583,7 @@ extern "C" int hero_wgrad_group(const HeroWgradProblem* probs, int n, int K, int
     HERO_ENSURE_LDS(&gemm_wsg_kernel, G::LDS, "gemm_wsg_kernel");
     double flops = 0.0;
     for (int i = 0; i < n; ++i) flops += 2.0 * probs[i].M * (double)probs[i].N * K;
-    void* tok = gemm_prof_begin(9, s);
+    void* tok = gemm_prof_begin(PROF_WS_OO, s);
     hipLaunchKernelGGL(gemm_wsg_kernel, dim3(cus), dim3(512), G::LDS, s, g);
     gemm_prof_end(tok, flops, s);
     return check_launch("hero_wgrad_group");
@@ -883,7 +777,7 @@ extern "C" int hero_wgrad_batch(const HeroWgradProblem* probs, int n, int K, int
                                    "hero_wgrad_batch: flag storage");
   g.flags = flags_of[dev];
   HERO_ENSURE_LDS(&gemm_wsb_kernel, G::LDS, "gemm_wsb_kernel");
-  void* tok = gemm_prof_begin(9, s);
+  void* tok = gemm_prof_begin(PROF_WS_OO, s);
   hipLaunchKernelGGL(gemm_wsb_kernel, dim3(num_cus()), dim3(512), G::LDS, s, g);
   gemm_prof_end(tok, flops, s);
   return check_launch("hero_wgrad_batch");

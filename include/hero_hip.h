@@ -46,6 +46,8 @@ const char* hero_last_error(void);
  * Still 3: hero_frame_pool_fwd/bwd and hero_bce_head_fwd/bwd (the VIOLIN head) were ADDED the same way.
  * Still 3: hero_dec_attention_fwd/bwd/in_envelope and hero_smooth_ce_fwd/bwd, the captioning decoder's kernels, were ADDED the
  * same way (a POINTER to the existing HeroDropout is an argument; the struct itself is unchanged).
+ * Still 3: hero_gemm_route (host-only query of hero_gemm's kernel choice) was ADDED the same way (a pointer to the unchanged
+ * HeroGemmEpilogue).
  * INTEGRATION.md section 2 lists the breaks per version. */
 #define HERO_ABI_VERSION 3
 int hero_abi_version(void);
@@ -129,10 +131,26 @@ int hero_gemm_splits(int K, int split_k, int dtype);
 /* out[i] = sum_{s < n_slabs} slabs[s * stride + i], s ascending (fixed order), i < n (n % 4 == 0); out_dtype F32 / BF16. */
 int hero_fold_slabs(const float* slabs, int n_slabs, size_t stride, void* out, size_t n, int out_dtype, hero_stream_t stream);
 
+/* The route hero_gemm takes for a problem RIGHT NOW (the hero_gemm_force_config state, the current device's compute units;
+ * 256 where there is no device) - host only, no device work, pointers of `epi` are read as null / non-null only.  Same
+ * shape checks and error codes as hero_gemm (no pointer-alignment checks).  Writes HERO_GEMM_ROUTE_WORDS int32 words and
+ * returns that number:
+ *   0 family     0 nothing to launch, 1 skinny fp32, 2 wave-specialised K,K, 3 wave-specialised O,O,
+ *                4 4-wave direct-to-LDS K,K, 5 4-wave direct-to-LDS O,O, 6 4-wave register-staged
+ *   1, 2 tile rows, tile columns        3 compile-time epilogue kind (0x100 generic; 1 bias, 2 GELU, 4 residual, 8 dropout, 16 gelu')
+ *   4 workgroups   5 threads per workgroup   6 dynamic LDS bytes   7 reduction splits   8 reduction length per split
+ *   9 M-tiles per L2 locality group   10 1: C is pre-scaled by beta in a launch of its own first   11 hero_prof_read slot
+ * Plain arguments and an existing struct: a backward-compatible addition, HERO_ABI_VERSION stays. */
+#define HERO_GEMM_ROUTE_WORDS 12
+int hero_gemm_route(int M, int N, int K, int lda, int ldb, int ldc, int a_layout, int b_layout, int dtype,
+                    const HeroGemmEpilogue* epi, int32_t* out, int capacity_words);
+
 /* Per-launch timing of hero_gemm with HIP events recorded on the launch stream (bench.py's
- * roofline leg; off by default, never enable inside graph capture).
- * slot = (dtype == HERO_BF16 ? 4 : 0) + a_layout * 2 + b_layout for the 4-wave kernels, 8 / 9 for the
- * wave-specialised 192x192 K,K / O,O kernels, 10 for the 128x192 K,K tiles (gemm_ws.hip). hero_prof_read synchronises. */
+ * roofline leg; off by default, never enable inside graph capture).  Slots (word 11 of hero_gemm_route):
+ *   0-7  (dtype == HERO_BF16 ? 4 : 0) + a_layout * 2 + b_layout: the 4-wave kernels (3 also holds the skinny fp32 kernel)
+ *   8    wave-specialised 192x192 K,K        9  wave-specialised O,O (hero_gemm, hero_wgrad_group, hero_wgrad_batch)
+ *   10   wave-specialised 128x192 / 64x128 / 64x192 K,K (gemm_ws.hip)
+ * hero_prof_read synchronises. */
 /* Grouped weight gradient: dw_p[M_p, N_p] (fp32) += dy_p[K, :M_p]^T x_p[K, :N_p] for 1..4 problems that reduce over
  * the same K rows - the four nn.Linear weights of a BertLayer (model/layers.py:125-127, 176, 237, 251) - in ONE
  * launch (stream-K over the (tile, k) space of the whole group, fp32 atomics into dw).  Small / unaligned / fp32
@@ -163,14 +181,17 @@ int hero_wgrad_group(const HeroWgradProblem* probs, int n, int K, int dtype, her
 int hero_wgrad_batch_plan(const HeroWgradProblem* probs, int n, int K, int32_t* plan, int capacity_words);
 int hero_wgrad_batch(const HeroWgradProblem* probs, int n, int K, int dtype, const int32_t* plan_dev, int plan_words,
                      hero_stream_t stream);
-int hero_gemm_force_config(int cfg); /* tuning hook, bits 0-1 tile geometry: 0 128x128, 1 192x128, 2 256x256,
-                                      * 3 64x64 (1 and 3: direct-to-LDS path only); bit 2: register staging;
-                                      * bits 8+: M-tiles per L2 locality group; 8 / 9 / 10: the wave-specialised
-                                      * kernels never / always with 192x192 / always with 128x192 tiles (11 / 12 were
-                                      * round 4's deferred-epilogue lab variant: now plain 4-wave); 13 / 14: 64x128 (six-deep ring) / 64x192
-                                      * (four-deep) tiles - what small-M GEMMs (the Temporal Transformer's 1920 rows into
-                                      * N = 768, the 480 query rows) take by default;
-                                      * -1 heuristic (fp32 GEMMs with M <= 32 then run a skinny VALU kernel) */
+/* Tuning hook: which kernels hero_gemm may choose.
+ *   -1        heuristic (only then fp32 GEMMs with M <= 32 run the skinny VALU kernel)
+ *   0..7      4-wave kernels only; bits 0-1 tile geometry: 0 128x128, 1 192x128, 2 256x256, 3 64x64 (1 and 3: direct-to-LDS
+ *             path only); bit 2: register staging
+ *   8         4-wave kernels only, geometry by shape
+ *   9 / 10    wave-specialised kernels always, 192x192 / 128x192 tiles (where the shape is legal)
+ *   13 / 14   wave-specialised 64x128 (six-deep ring) / 64x192 (four-deep) tiles - what small-M GEMMs (the Temporal
+ *             Transformer's 1920 rows into N = 768, the 480 query rows) take by default
+ *   11, 12, 15 and up: read as bits like 0..7 (11 / 12 were round 4's deferred-epilogue lab variant: now plain 4-wave);
+ *             bits 8+: M-tiles per L2 locality group */
+int hero_gemm_force_config(int cfg);
 int hero_prof_enable(int on);
 int hero_prof_read(int slot, double* total_ms, double* total_flops, long long* launches);
 
