@@ -20,6 +20,9 @@
 // memory.  dK / dV are summed over the queries inside the workgroup in a fixed order: no atomics, two runs give the same
 // bits; every element of dq / dk / dv is written, the caller does no zero-fill.  In the backward dS takes V's place in LDS
 // once dP = dO V^T is in registers.
+//
+// Incremental decoding has its own kernel further down (dec_attn_row_kernel: one query row per (caption, head), one wave each,
+// keys straight from global memory or from a key/value cache that the kernel extends; inference only).
 #include "common.h"
 
 namespace hero {
@@ -276,6 +279,153 @@ __global__ __launch_bounds__(256) void dec_attn_bwd_kernel(DecAttn a) {
     }
 }
 
+// ---- one query row per (caption, head): the attentions of an incremental decode step ------------------------------------------
+// One wavefront owns a (caption, head) pair, a workgroup holds four pairs; there is no K / V tile in LDS - a key row is read
+// once, by one lane, straight from global memory.  Lane l owns the keys l and l + 64: 64 dims against q, which the wave keeps
+// as 64 floats in LDS (a broadcast read), in the summation order of `dots` above.  Row maximum and sum are the two DPP wave
+// reductions, P goes to a per-wave LDS row, and for P V the lanes regroup as (key residue lane >> 4, dims 4 (lane & 15)): 16
+// lanes read one V row coalesced, each residue sums its keys in ascending order, and the four partial float4s are added in
+// the order 0, 1, 2, 3.  No atomics; every element of ctx is written.
+//   cross mode   keys [0, Lk) at rows n * Lk + j of k / v (leading dimension ldkv), the caption's additive key mask
+//   step mode    keys [0, t) at rows n * Tcap + j of the cache [N, Tcap, 2 * H * 64], key t from this step's Q|K|V row; the
+//                wave also copies that row's K|V columns of its head into cache row t (bits, not values) and never reads them
+//                back.  t comes from the host or from a device int32; a device t outside [0, Tcap) writes nothing to the
+//                cache and zeros to ctx.
+constexpr int DR_WAVES = 4, DR_Q = 64, DR_P = DA_MAX_LK, DR_RED = 4 * 64, DR_LDS = DR_Q + DR_P + DR_RED;   // floats per wave
+
+struct DecRow {
+  const void* q;           // [N, ldq], the head's 64 columns at h * 64
+  const void *k, *v;       // rows (n * rows_n + j) * ldkv, the head's columns at h * 64 (cache: k = cache, v = cache + H * 64)
+  const void *kt, *vt;     // step mode: this step's K and V row [N, ldq] (inside the packed Q|K|V buffer); NULL in cross mode
+  void* cache;             // step mode: [N, Tcap, 2 * H * 64], row t is written
+  const float* key_mask;   // cross mode: [N, Lk] additive or NULL
+  void* ctx;               // [N, H * 64]
+  const int* pos_dev;
+  int pos, N, rows_n, H, ldq, ldkv;   // rows_n = Lk (cross) | Tcap (step)
+  float scale;
+};
+
+// 64-dim dot product of a global row with the wave's q in LDS, d ascending in groups of 4 as in `dots`; 16-byte loads
+template <typename T> __device__ __forceinline__ float dot_row(const T* row, const float* qs);
+template <> __device__ __forceinline__ float dot_row<float>(const float* row, const float* qs) {
+  float acc = 0.f;
+#pragma unroll
+  for (int d = 0; d < 64; d += 4) acc = dot4(ldf4(qs + d), ldf4(row + d), acc);
+  return acc;
+}
+template <> __device__ __forceinline__ float dot_row<bf16_t>(const bf16_t* row, const float* qs) {
+  float acc = 0.f;
+#pragma unroll
+  for (int d = 0; d < 64; d += 8) {
+    const uint4 u = *reinterpret_cast<const uint4*>(row + d);
+    const float4 lo = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u),
+                                  __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
+    const float4 hi = make_float4(__uint_as_float(u.z << 16), __uint_as_float(u.z & 0xffff0000u),
+                                  __uint_as_float(u.w << 16), __uint_as_float(u.w & 0xffff0000u));
+    acc = dot4(ldf4(qs + d), lo, acc);
+    acc = dot4(ldf4(qs + d + 4), hi, acc);
+  }
+  return acc;
+}
+
+template <typename T, bool STEP>
+__global__ __launch_bounds__(256) void dec_attn_row_kernel(DecRow a) {
+  __shared__ __attribute__((aligned(16))) float lds[DR_WAVES * DR_LDS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int pair = blockIdx.x * DR_WAVES + wave;
+  const bool active = pair < a.N * a.H;                             // wave-uniform; idle waves only keep the barriers company
+  const int n = active ? pair / a.H : 0, h = active ? pair % a.H : 0;
+  float *qs = lds + wave * DR_LDS, *ps = qs + DR_Q, *red = ps + DR_P;
+  const int D = a.H * 64;
+  T* out = static_cast<T*>(a.ctx) + (size_t)n * D + h * 64;
+  int Lm = a.rows_n;                                                // keys read from memory
+  if (STEP) {
+    const int t = a.pos_dev ? *a.pos_dev : a.pos;
+    if (t < 0 || t >= a.rows_n) {                                   // uniform over the grid: no barrier is reached by anyone
+      if (active && lane < 16) V4<T>::st(out + 4 * lane, make_float4(0.f, 0.f, 0.f, 0.f));
+      return;
+    }
+    Lm = t;
+  }
+  const int Lall = Lm + (STEP ? 1 : 0);                             // <= 128
+  const size_t row0 = (size_t)n * a.rows_n;
+  const T* K = static_cast<const T*>(a.k) + row0 * a.ldkv + h * 64;
+  const T* V = static_cast<const T*>(a.v) + row0 * a.ldkv + h * 64;
+  const T* Kt = STEP ? static_cast<const T*>(a.kt) + (size_t)n * a.ldq + h * 64 : nullptr;
+  const T* Vt = STEP ? static_cast<const T*>(a.vt) + (size_t)n * a.ldq + h * 64 : nullptr;
+  if (active && lane < 16)
+    *reinterpret_cast<float4*>(qs + 4 * lane) = V4<T>::ld(static_cast<const T*>(a.q) + (size_t)n * a.ldq + h * 64 + 4 * lane);
+  if (STEP && active && lane < 32) {                                // cache row t <- this step's K | V columns of the head, bit for bit
+    const int c = 4 * (lane & 15);
+    const T* src = (lane < 16 ? Kt : Vt) + c;
+    T* dst = static_cast<T*>(a.cache) + (row0 + Lm) * a.ldkv + (lane < 16 ? 0 : D) + h * 64 + c;
+    if (sizeof(T) == 4) *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
+    else *reinterpret_cast<uint2*>(dst) = *reinterpret_cast<const uint2*>(src);
+  }
+  __syncthreads();
+  if (active) {
+    const float* km = (!STEP && a.key_mask) ? a.key_mask + (size_t)n * a.rows_n : nullptr;
+    float s[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int j = lane + 64 * b;
+      s[b] = -3.0e38f;
+      if (j < Lall) {
+        const T* row = (STEP && j == Lm) ? Kt : K + (size_t)j * a.ldkv;
+        s[b] = dot_row<T>(row, qs) * a.scale;
+        if (km) s[b] += km[j];
+      }
+    }
+    const float m = wave_max(fmaxf(s[0], s[1]));
+    const float e0 = lane < Lall ? expf(s[0] - m) : 0.f, e1 = lane + 64 < Lall ? expf(s[1] - m) : 0.f;
+    const float inv = 1.f / wave_sum(e0 + e1);
+    ps[lane] = e0 * inv;                                            // zero behind the last key
+    ps[lane + 64] = e1 * inv;
+  }
+  __syncthreads();
+  const int r = lane >> 4, d = 4 * (lane & 15);
+  if (active) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j = r; j < Lall; j += 4) {
+      const T* row = (STEP && j == Lm) ? Vt : V + (size_t)j * a.ldkv;
+      fma4(acc, ps[j], V4<T>::ld(row + d));
+    }
+    *reinterpret_cast<float4*>(red + r * 64 + d) = acc;
+  }
+  __syncthreads();
+  if (active && lane < 16) {
+    float4 o = ldf4(red + d);
+#pragma unroll
+    for (int g = 1; g < 4; ++g) {
+      const float4 x = ldf4(red + g * 64 + d);
+      o.x += x.x; o.y += x.y; o.z += x.z; o.w += x.w;
+    }
+    V4<T>::st(out + d, o);
+  }
+}
+
+bool aligned16(const void* p);
+
+int launch_row(const char* what, const DecRow& a, bool step, int dtype, hero_stream_t stream) {
+  HERO_REQUIRE(a.ldq % 8 == 0 && a.ldkv % 8 == 0 && a.ldq >= a.H * 64 && a.ldkv >= a.H * 64,
+               "%s: leading dimensions must be multiples of 8 and at least H * 64: ldq=%d ldkv=%d H=%d", what, a.ldq, a.ldkv, a.H);
+  HERO_REQUIRE((long long)a.N * a.H < (1ll << 31), "%s: N * H too large", what);
+  HERO_REQUIRE(a.q && a.k && a.v && a.ctx && (!step || (a.kt && a.vt && a.cache)), "%s: null pointer", what);
+  HERO_REQUIRE(aligned16(a.q) && aligned16(a.k) && aligned16(a.v) && aligned16(a.ctx), "%s: operands must be 16-byte aligned", what);
+  const dim3 grid((a.N * a.H + DR_WAVES - 1) / DR_WAVES), block(64 * DR_WAVES);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == HERO_F32) {
+    if (step) hipLaunchKernelGGL((dec_attn_row_kernel<float, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((dec_attn_row_kernel<float, false>), grid, block, 0, st, a);
+  } else {
+    if (step) hipLaunchKernelGGL((dec_attn_row_kernel<bf16_t, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((dec_attn_row_kernel<bf16_t, false>), grid, block, 0, st, a);
+  }
+  return check_launch(what);
+}
+
+bool row_in_envelope(int dtype, int Lk) { return (dtype == HERO_F32 || dtype == HERO_BF16) && Lk >= 1 && Lk <= DA_MAX_LK; }
+
 bool in_envelope(int dtype, int Lq, int Lk) {
   return (dtype == HERO_F32 || dtype == HERO_BF16) && Lq >= 1 && Lq <= DA_MAX_LQ && Lk >= 1 && Lk <= DA_MAX_LK;
 }
@@ -298,6 +448,32 @@ int check(const char* what, const DecAttn& a, int N, int dtype) {
 using namespace hero;
 
 extern "C" int hero_dec_attention_in_envelope(int dtype, int Lq, int Lk) { return in_envelope(dtype, Lq, Lk) ? 1 : 0; }
+
+extern "C" int hero_dec_attention_row_in_envelope(int dtype, int Lk) { return row_in_envelope(dtype, Lk) ? 1 : 0; }
+
+extern "C" int hero_dec_attention_row(const void* q, const void* k, const void* v, const float* key_mask_add, void* ctx, int N, int Lk,
+                                      int H, int ldq, int ldkv, float scale, int dtype, hero_stream_t stream) {
+  HERO_REQUIRE(row_in_envelope(dtype, Lk) && H >= 1 && N >= 1,
+               "hero_dec_attention_row: outside the envelope (fp32 / bf16, 1 <= Lk <= %d, H >= 1, N >= 1): dtype=%d N=%d Lk=%d H=%d",
+               DA_MAX_LK, dtype, N, Lk, H);
+  const DecRow a = {q, k, v, nullptr, nullptr, nullptr, key_mask_add, ctx, nullptr, 0, N, Lk, H, ldq, ldkv, scale};
+  return launch_row("hero_dec_attention_row", a, false, dtype, stream);
+}
+
+extern "C" int hero_dec_attention_step(const void* qkv, void* kv_cache, void* ctx, const int* pos_dev, int pos, int N, int Tcap, int H,
+                                       float scale, int dtype, hero_stream_t stream) {
+  HERO_REQUIRE(row_in_envelope(dtype, Tcap) && H >= 1 && N >= 1,
+               "hero_dec_attention_step: outside the envelope (fp32 / bf16, 1 <= Tcap <= %d, H >= 1, N >= 1): dtype=%d N=%d Tcap=%d H=%d",
+               DA_MAX_LK, dtype, N, Tcap, H);
+  HERO_REQUIRE(pos_dev || (pos >= 0 && pos < Tcap), "hero_dec_attention_step: position %d outside [0, Tcap = %d)", pos, Tcap);
+  HERO_REQUIRE(H <= (1 << 20), "hero_dec_attention_step: H too large");
+  const int D = H * 64;
+  const size_t es = dtype == HERO_F32 ? 4 : 2;
+  const char* row = static_cast<const char*>(qkv);
+  const DecRow a = {qkv, kv_cache, kv_cache ? static_cast<const char*>(kv_cache) + D * es : nullptr, qkv ? row + D * es : nullptr,
+                    qkv ? row + 2 * D * es : nullptr, kv_cache, nullptr, ctx, pos_dev, pos, N, Tcap, H, 3 * D, 2 * D, scale};
+  return launch_row("hero_dec_attention_step", a, true, dtype, stream);
+}
 
 extern "C" int hero_dec_attention_fwd(const void* q, const void* k, const void* v, const float* key_mask_add, void* ctx, float* stats,
                                       int N, int Lq, int Lk, int H, int ldq, int ldkv, int causal, float scale, int dtype,

@@ -101,6 +101,11 @@ def weight_cache_generation():
     return _WGEN[0]
 
 
+def weight_epoch():
+    """Grows with every notify_weights_updated(): with the parameters' version counters, the signature of "the weights changed"."""
+    return _WEPOCH[0]
+
+
 def notify_weights_updated():
     """Call after parameters were changed in a way autograd's version counters cannot see
     (raw-pointer optimisers such as hero_amd.optim.AdamW, or `p.data` updates)."""

@@ -45,6 +45,36 @@ def _add_norm_torch(mod, hidden, residual):
     return F.layer_norm(h + residual, ln.normalized_shape, ln.weight, ln.bias, ln.eps)
 
 
+def _attend_torch(att, q, k, v, mask_add):
+    """The attention of `_attention_torch` on PROJECTED operands (q [N, Lq, D], k / v [N, Lk, D]) and without dropout: what an
+    incremental decode step runs against the keys and values it has kept."""
+    H = att.num_attention_heads
+
+    def split(t):
+        return t.view(t.shape[0], t.shape[1], H, att.attention_head_size).permute(0, 2, 1, 3)
+    scores = torch.matmul(split(q), split(k).transpose(-1, -2)) / math.sqrt(att.attention_head_size)
+    if mask_add is not None:
+        scores = scores + mask_add
+    ctx = torch.matmul(torch.softmax(scores, dim=-1), split(v)).permute(0, 2, 1, 3).contiguous()
+    return ctx.view(ctx.shape[0], ctx.shape[1], att.all_head_size)
+
+
+class TvcDecodeState(object):
+    """What an incremental decode keeps between its steps (HeroForTvc.init_decode_state / decode_step), per decoder layer:
+        fused    cross_kv [N*Lv, 2D] the packed K|V projection of the encoder rows, computed ONCE; cache [N, max_step, 2D] the
+                 K|V of the decoded positions, extended by the step kernel; mask_add [N, Lv] fp32; pos (one device int32, the
+                 position of the next step - the kernels and the embedding read it on the device) with pid = pos per caption and
+                 wid, the int32 word ids of the step
+        PyTorch  cross_k / cross_v [N, Lv, D], self_k / self_v [N, t, D] grown by concatenation, mask_add [N, 1, 1, Lv], t
+    Every buffer keeps its address for the life of the state, so one captured step serves all steps and, after `refill`, all
+    batches of the same shape."""
+
+    def __init__(self, fused, N, Lv, max_step):
+        self.fused, self.N, self.Lv, self.max_step, self.t = fused, N, Lv, max_step, 0
+        self.cross_kv, self.cache, self.cross_k, self.cross_v, self.self_k, self.self_v = [], [], [], [], [], []
+        self.mask_add = self.pos = self.pid = self.wid = None
+
+
 class BertDecoderLayer(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -73,6 +103,39 @@ class BertDecoderLayer(nn.Module):
         a = _attention_torch(sa, dec_hidden_states, dec_hidden_states, tri_mask, sa.dropout.p, self.training)
         a = _add_norm_torch(self.add_norm_1, a, dec_hidden_states)
         c = _attention_torch(ca, a, enc_outputs, enc_mask, ca.dropout.p, self.training)
+        c = _add_norm_torch(self.add_norm_2, c, a)
+        h = F.gelu(self.intermidiate.dense(c))
+        return _add_norm_torch(self.add_norm_3, h, c)
+
+    def cross_kv(self, enc2):
+        """The packed K|V projection [N*Lv, 2D] of the encoder rows: the same GEMM DecAttentionFn runs, once per decode."""
+        ca = self.dec_enc_attention
+        return HF.k_linear(enc2, HF.packed((ca.key.weight, ca.value.weight), enc2.dtype),
+                           HF.packed((ca.key.bias, ca.value.bias), torch.float32))
+
+    def step(self, x, state, li):
+        """One decoded position per caption on the one-row kernels: x [N, D] in the compute dtype -> [N, D].  Inference only."""
+        sa, ca = self.self_attention, self.dec_enc_attention
+        wq, bq, wk, bk, wv, bv = sa.qkv_params()
+        qkv = HF.k_linear(x, HF.packed((wq, wk, wv), x.dtype), HF.packed((bq, bk, bv), torch.float32))
+        a = T.k_dec_attn_step(qkv, state.cache[li], state.pos, state.N, sa.num_attention_heads)
+        a = self.add_norm_1(a, x)
+        q = HF.k_linear(a, HF.packed((ca.query.weight,), a.dtype), HF.packed((ca.query.bias,), torch.float32))
+        c = T.k_dec_attn_row(q, state.cross_kv[li], state.mask_add, state.N, state.Lv, ca.num_attention_heads)
+        c = self.add_norm_2(c, a)
+        o = self.add_norm_3
+        return HF.FfnBlockFn.apply(c, o.LayerNorm.eps, _drop(o.dropout, x.device), self.intermidiate.dense.weight,
+                                   self.intermidiate.dense.bias, o.dense.weight, o.dense.bias, o.LayerNorm.weight, o.LayerNorm.bias)
+
+    def step_torch(self, x, state, li):
+        """The same step in PyTorch ops: x [N, 1, D]; the layer's keys / values grow by concatenation, so no tri_mask."""
+        sa, ca = self.self_attention, self.dec_enc_attention
+        k, v = sa.key(x), sa.value(x)
+        if state.t:
+            k, v = torch.cat([state.self_k[li], k], dim=1), torch.cat([state.self_v[li], v], dim=1)
+        state.self_k[li], state.self_v[li] = k, v
+        a = _add_norm_torch(self.add_norm_1, _attend_torch(sa, sa.query(x), k, v, None), x)
+        c = _attend_torch(ca, ca.query(a), state.cross_k[li], state.cross_v[li], state.mask_add)
         c = _add_norm_torch(self.add_norm_2, c, a)
         h = F.gelu(self.intermidiate.dense(c))
         return _add_norm_torch(self.add_norm_3, h, c)
@@ -236,6 +299,92 @@ class HeroForTvc(HeroModel):
             return rows[labels != -1]
         return HF.cross_entropy(logits, labels, ncols=V, ignore_index=-1)
 
+    # ---- incremental decoding ------------------------------------------------------------------------------------------
+    max_cache = T.MAX_LK    # Python-side limit on max_step of the cached route (never above the one-row kernels' envelope)
+
+    def _fused_step(self, encoder_outputs, max_step):
+        if self.v_encoder.f_encoder.vocab_pad:
+            raise ValueError("HeroForTvc: the vocabulary (%d) is not a multiple of 8" % self.config.f_config.vocab_size)
+        Lv = encoder_outputs.shape[1]
+        return (self.fused_decoder and encoder_outputs.is_cuda and max_step <= self.max_cache and Lv <= self.max_lk
+                and T.in_envelope_row(HF.compute_dtype(), max_step) and T.in_envelope_row(HF.compute_dtype(), Lv))
+
+    @torch.no_grad()
+    def init_decode_state(self, encoder_outputs, encoder_masks, max_step):
+        """The state of an incremental decode of up to `max_step` positions over encoder_outputs [N, Lv, D] and their 0/1 mask:
+        the cross-attention keys and values of every layer (they do not change during a decode), empty self-attention caches,
+        position 0.  On the kernels inside their envelope, in PyTorch ops otherwise (CPU tensors, fused_decoder = False,
+        max_step or Lv above 128 or above the Python-side limits)."""
+        N, Lv, D = encoder_outputs.shape
+        if max_step < 1 or max_step > self.position_embeddings.num_embeddings:
+            raise ValueError("HeroForTvc: max_step %d outside [1, %d]" % (max_step, self.position_embeddings.num_embeddings))
+        state = TvcDecodeState(self._fused_step(encoder_outputs, max_step), N, Lv, max_step)
+        dev = encoder_outputs.device
+        if state.fused:
+            cd = HF.compute_dtype()
+            for _ in self.decoder.layer:
+                state.cross_kv.append(torch.empty((N * Lv, 2 * D), dtype=cd, device=dev))
+                state.cache.append(torch.zeros((N, max_step, 2 * D), dtype=cd, device=dev))
+            state.mask_add = torch.empty((N, Lv), dtype=torch.float32, device=dev)
+            state.pos = torch.zeros((1,), dtype=torch.int32, device=dev)
+            state.pid = torch.zeros((N,), dtype=torch.int32, device=dev)
+            state.wid = torch.zeros((N,), dtype=torch.int32, device=dev)
+        else:
+            n = len(self.decoder.layer)
+            state.self_k, state.self_v = [None] * n, [None] * n
+        return self.refill_decode_state(state, encoder_outputs, encoder_masks)
+
+    @torch.no_grad()
+    def refill_decode_state(self, state, encoder_outputs, encoder_masks):
+        """Another batch of the same shape into the SAME buffers, position back to 0 (a captured step holds their addresses)."""
+        if tuple(encoder_outputs.shape[:2]) != (state.N, state.Lv):
+            raise ValueError("HeroForTvc: the decode state was made for [%d, %d] encoder rows, got %s"
+                             % (state.N, state.Lv, tuple(encoder_outputs.shape)))
+        state.t = 0
+        if state.fused:
+            enc2 = HF._as2d(HF.cast(encoder_outputs, HF.compute_dtype()))
+            for li, layer in enumerate(self.decoder.layer):
+                state.cross_kv[li].copy_(layer.cross_kv(enc2))
+            state.mask_add.copy_((1.0 - encoder_masks.reshape(state.N, state.Lv).to(torch.float32)) * -10000.0)
+            state.pos.zero_()
+            state.pid.zero_()
+            return state
+        enc = encoder_outputs.to(self.emb_LayerNorm.weight.dtype)
+        state.cross_k = [layer.dec_enc_attention.key(enc) for layer in self.decoder.layer]
+        state.cross_v = [layer.dec_enc_attention.value(enc) for layer in self.decoder.layer]
+        state.mask_add = (1.0 - encoder_masks.unsqueeze(1).unsqueeze(2).to(enc)) * -10000.0
+        return state
+
+    @torch.no_grad()
+    def decode_step(self, state, last_ids):
+        """last_ids [N]: the token of every caption at the state's position -> the prediction scores [N, vocab] of the next
+        one (in the compute dtype on the kernels); the position advances - on the device for the fused state, nothing here
+        reads it on the host, so the call can be captured and replayed."""
+        emb = self.v_encoder.f_encoder.embeddings
+        V = self.config.f_config.vocab_size
+        if state.fused:
+            state.wid.copy_(last_ids)
+            ln = self.emb_LayerNorm
+            x = HF.embed_ln(None, ln.weight, ln.bias, ln.eps, None, HF.compute_dtype(),
+                            tables=(emb.word_embeddings.weight, self.position_embeddings.weight), idxs=(state.wid, state.pid),
+                            skip_idx=(emb.padding_idx, -1))
+            for li, layer in enumerate(self.decoder.layer):
+                x = layer.step(x, state, li)
+            scores = self.v_encoder.f_encoder.lm_head(x, raw=True)
+            state.pos.add_(1)
+            state.pid.add_(1)
+            return scores[:, :V]
+        if state.t >= state.max_step:
+            raise ValueError("HeroForTvc: decode step %d of a state made for %d" % (state.t, state.max_step))
+        pos_ids = torch.full((state.N, 1), state.t, dtype=torch.long, device=last_ids.device)
+        x = emb.word_embeddings(last_ids.unsqueeze(1)) + self.position_embeddings(pos_ids)
+        ln = self.emb_LayerNorm
+        x = F.layer_norm(x, ln.normalized_shape, ln.weight, ln.bias, ln.eps)
+        for li, layer in enumerate(self.decoder.layer):
+            x = layer.step_torch(x, state, li)
+        state.t += 1
+        return self._scores_torch(x[:, 0])
+
     def forward(self, batch, mode="train", compute_loss=True, task=None):
         if task not in (None, "tvc"):
             raise ValueError(f"Unrecognized task: {task}")
@@ -262,10 +411,88 @@ class HeroForTvc(HeroModel):
 class TvcGenerator(object):
     """Greedy decoding (model/tvc.py:293-338) on a fixed [N, max_step] id buffer: the encoder runs once; every step runs the
     decoder over the whole buffer under the causal mask - positions past the current one cannot influence it - projects ONLY
-    the current position through the vocabulary GEMM and takes the arg-max on the device.  One host transfer, at the end."""
+    the current position through the vocabulary GEMM and takes the arg-max on the device.  One host transfer, at the end.
 
-    def __init__(self, model, max_step, bos, eos):
+    kv_cache = True decodes incrementally instead (HeroForTvc.init_decode_state / decode_step): every step runs the decoder on
+    ONE row per caption against the keys and values kept from the earlier steps, and the keys / values of the encoder rows are
+    projected once per decode.  use_graph = True (needs kv_cache, and the kernels' route) captures that step - embedding, both
+    layers, projection, arg-max, the id write at the device position, the position increment - once per (N, Lv, max_step) on one
+    stream and replays it max_step times; between batches of one shape only the state's buffers are refilled."""
+
+    MAX_GRAPHS = 8
+
+    def __init__(self, model, max_step, bos, eos, kv_cache=False, use_graph=False):
+        if use_graph and not kv_cache:
+            raise ValueError("TvcGenerator: use_graph replays the incremental decode step, it needs kv_cache=True")
         self.model, self.max_step, self.bos, self.eos = model, max_step, bos, eos
+        self.kv_cache, self.use_graph = kv_cache, use_graph
+        self._graphs = {}          # (N, Lv, max_step, dtype, device, weight-copy generation) -> captured step and its buffers
+        self.counts = {"captures": 0, "replayed": 0}
+
+    def _step(self, state, last, output_ids):
+        """One incremental step on device buffers only: `last` [N] in, the arg-max ids out - into `last` and into column
+        (position) of output_ids."""
+        model = self.model
+        scores = model.decode_step(state, last)
+        nxt = scores.float().argmax(dim=-1)
+        if state.fused:
+            col = (state.pos - 1).long().view(1, 1).expand(state.N, 1)                 # the position this step decoded
+            output_ids.scatter_(1, col, nxt.unsqueeze(1))
+        else:
+            output_ids[:, state.t - 1] = nxt
+        last.copy_(nxt)
+
+    def _weights_signature(self):
+        return tuple(p._version for p in self.model.parameters()) + (HF.weight_epoch(),)
+
+    def _decode_graph(self, encoder_outputs, enc_mask):
+        model = self.model
+        N, Lv = encoder_outputs.shape[:2]
+        dev = encoder_outputs.device
+        key = (N, Lv, self.max_step, HF.compute_dtype(), str(dev), HF.weight_cache_generation())
+        hit = self._graphs.get(key)
+        if hit is None:
+            state = model.init_decode_state(encoder_outputs, enc_mask, self.max_step)
+            if not state.fused:
+                raise ValueError("TvcGenerator: use_graph needs the kernels' route (CUDA tensors, fused_decoder, max_step and Lv "
+                                 "inside the envelope)")
+            last = torch.full((N,), self.bos, dtype=torch.long, device=dev)
+            output_ids = torch.zeros((N, self.max_step), dtype=torch.long, device=dev)
+            self._step(state, last, output_ids)                 # eager: every compute copy of a weight exists before the capture
+            key = key[:-1] + (HF.weight_cache_generation(),)
+            model.refill_decode_state(state, encoder_outputs, enc_mask)
+            last.fill_(self.bos)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):                       # one stream, no forks: the graph is a straight line
+                self._step(state, last, output_ids)
+            if len(self._graphs) >= self.MAX_GRAPHS:
+                self._graphs.clear()
+            hit = self._graphs[key] = dict(graph=graph, state=state, last=last, out=output_ids, wsig=self._weights_signature())
+            self.counts["captures"] += 1
+        state, last, output_ids = hit["state"], hit["last"], hit["out"]
+        wsig = self._weights_signature()
+        if wsig != hit["wsig"]:                                 # the replay calls no HF.packed: bring the compute copies up to date
+            HF.refresh_weight_cache()
+            hit["wsig"] = wsig
+        model.refill_decode_state(state, encoder_outputs, enc_mask)
+        last.fill_(self.bos)
+        for _ in range(self.max_step):
+            hit["graph"].replay()
+        self.counts["replayed"] += self.max_step
+        return output_ids
+
+    @torch.no_grad()
+    def _decode_cached(self, encoder_outputs, enc_mask):
+        if self.use_graph:
+            return self._decode_graph(encoder_outputs, enc_mask)
+        N, dev = encoder_outputs.shape[0], encoder_outputs.device
+        state = self.model.init_decode_state(encoder_outputs, enc_mask, self.max_step)
+        last = torch.full((N,), self.bos, dtype=torch.long, device=dev)
+        output_ids = torch.empty((N, self.max_step), dtype=torch.long, device=dev)
+        for _ in range(self.max_step):
+            self._step(state, last, output_ids)
+        return output_ids
 
     @torch.no_grad()
     def greedy_decode(self, batch, encoder_outputs=None):
@@ -274,6 +501,8 @@ class TvcGenerator(object):
         if encoder_outputs is None:
             encoder_outputs = model.encode(batch)
         enc_mask = batch["cap_attn_mask"]
+        if self.kv_cache:
+            return [self.cut_eos(ids) for ids in self._decode_cached(encoder_outputs, enc_mask).tolist()]
         N, dev = enc_mask.size(0), encoder_outputs.device
         # the buffer is padded with the pad id, whose embedding row and positions the causal mask hides from every earlier step
         input_ids = torch.full((N, self.max_step), model.v_encoder.f_encoder.embeddings.padding_idx, dtype=torch.long, device=dev)

@@ -5,6 +5,8 @@ hero_smooth_ce_fwd / _bwd (include/hero_hip.h "Decoder attention", "Label-smooth
                       [N*Lq, H*64] query and a [N*Lk, 2*H*64] K|V buffer (decoder-encoder attention, key mask per caption)
     DecAttentionFn    the same with its projections: BertSelfAttention under tri_mask / BertDecEncAttention of a decoder layer
     SmoothCeFn        LabelSmoothingLoss in closed form: per-row losses plus the device pair (sum, number of valid rows)
+    k_dec_attn_row / k_dec_attn_step   the one-query-row kernels of incremental decoding (no autograd: inference only) - attention
+                      over the encoder keys, and causal self-attention against a key/value cache that the kernel extends
 
 There is no PyTorch route in here: outside the kernels' envelope the nodes raise."""
 import ctypes as C
@@ -74,6 +76,70 @@ def k_dec_attn_bwd(qbuf, kvbuf, key_mask_add, stats, dctx, N, Lq, Lk, H, causal,
     L.check(L.lib().hero_dec_attention_bwd(q, k, v, L.ptr(key_mask_add), L.ptr(stats), L.ptr(dctx), dq, dk, dv, N, Lq, Lk, H, ldq, ldkv,
                                            1 if causal else 0, 1.0 / math.sqrt(HEAD), L.dt(qbuf), _drop_ref(drop), L.stream()))
     return dqbuf, dkvbuf
+
+
+def in_envelope_row(dtype, Lk):
+    """The library's own answer (hero_dec_attention_row_in_envelope): the one-row kernels take 1 <= Lk (or cache rows) <= 128."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return bool(L.lib().hero_dec_attention_row_in_envelope(L.F32 if dtype == torch.float32 else L.BF16, int(Lk)))
+
+
+def _row_operand(name, t, rows, cols, dtype=None):
+    if t.dim() != 2 or tuple(t.shape) != (rows, cols) or (dtype is not None and t.dtype != dtype):
+        raise ValueError("decoder attention: %s must be [%d, %d]%s, got %s %s"
+                         % (name, rows, cols, " of %s" % dtype if dtype is not None else "", tuple(t.shape), t.dtype))
+
+
+def k_dec_attn_row(q, kv, key_mask_add, N, Lk, H):
+    """Decoder-encoder attention of ONE decoder position per caption (inference: no dropout, no stats):
+    q [N, H*64], kv [N*Lk, 2*H*64] the packed K|V projection of the encoder rows, key_mask_add [N, Lk] fp32 | None
+    -> ctx [N, H*64] in the operands' dtype."""
+    if N < 1 or not in_envelope_row(q.dtype, Lk):
+        raise ValueError("decoder attention: %s, N=%d, Lk=%d is outside the one-row kernel's envelope (fp32 / bf16, N >= 1, "
+                         "1 <= Lk <= %d)" % (q.dtype, N, Lk, MAX_LK))
+    D, es = H * HEAD, q.element_size()
+    _row_operand("q", q, N, D)
+    _row_operand("kv", kv, N * Lk, 2 * D, q.dtype)
+    if key_mask_add is not None and (tuple(key_mask_add.shape) != (N, Lk) or key_mask_add.dtype != torch.float32):
+        raise ValueError("decoder attention: key mask must be fp32 [N, Lk], got %s %s" % (tuple(key_mask_add.shape), key_mask_add.dtype))
+    ctxt = torch.empty((N, D), dtype=q.dtype, device=q.device)
+    p = L.ptr(kv)
+    L.check(L.lib().hero_dec_attention_row(L.ptr(q), p, p + D * es, L.ptr(key_mask_add), L.ptr(ctxt), N, Lk, H, D, 2 * D,
+                                           1.0 / math.sqrt(HEAD), L.dt(q), L.stream()))
+    return ctxt
+
+
+def k_dec_attn_step(qkv, cache, pos, N, H):
+    """Causal self-attention of position `pos` against a key/value cache (inference):
+    qkv [N, 3*H*64] this step's packed Q|K|V rows, cache [N, Tcap, 2*H*64] with K|V of the positions < pos; the kernel also
+    writes this step's K|V into cache[:, pos].  pos: an int, or a 1-element int32 device tensor (read by the kernel, so that a
+    captured launch serves every step; a value outside [0, Tcap) leaves the cache alone and gives zeros).
+    -> ctx [N, H*64]."""
+    D = H * HEAD
+    if cache.dim() != 3:
+        raise ValueError("decoder attention: the cache must be [N, Tcap, 2 * H * 64], got %s" % (tuple(cache.shape),))
+    Tcap = cache.shape[1]
+    if N < 1 or not in_envelope_row(qkv.dtype, Tcap):
+        raise ValueError("decoder attention: %s, N=%d, Tcap=%d is outside the one-row kernel's envelope (fp32 / bf16, N >= 1, "
+                         "1 <= Tcap <= %d)" % (qkv.dtype, N, Tcap, MAX_LK))
+    _row_operand("qkv", qkv, N, 3 * D)
+    if tuple(cache.shape) != (N, Tcap, 2 * D) or cache.dtype != qkv.dtype:
+        raise ValueError("decoder attention: the cache must be [%d, Tcap, %d] of %s, got %s %s"
+                         % (N, 2 * D, qkv.dtype, tuple(cache.shape), cache.dtype))
+    if torch.is_tensor(pos):
+        if pos.numel() != 1 or pos.dtype != torch.int32 or pos.device != qkv.device:
+            raise ValueError("decoder attention: a device position must be one int32 on %s, got %s %s on %s"
+                             % (qkv.device, tuple(pos.shape), pos.dtype, pos.device))
+        pos_dev, pos_host = L.ptr(pos), 0
+    else:
+        pos_dev, pos_host = None, int(pos)
+        if not 0 <= pos_host < Tcap:
+            raise ValueError("decoder attention: position %d outside [0, Tcap = %d)" % (pos_host, Tcap))
+    ctxt = torch.empty((N, D), dtype=qkv.dtype, device=qkv.device)
+    L.check(L.lib().hero_dec_attention_step(L.ptr(qkv), L.ptr(cache), L.ptr(ctxt), pos_dev, pos_host, N, Tcap, H,
+                                            1.0 / math.sqrt(HEAD), L.dt(qkv), L.stream()))
+    return ctxt
 
 
 class DecAttnCoreFn(torch.autograd.Function):

@@ -48,6 +48,8 @@ const char* hero_last_error(void);
  * same way (a POINTER to the existing HeroDropout is an argument; the struct itself is unchanged).
  * Still 3: hero_gemm_route (host-only query of hero_gemm's kernel choice) was ADDED the same way (a pointer to the unchanged
  * HeroGemmEpilogue).
+ * Still 3: hero_dec_attention_row, hero_dec_attention_step and hero_dec_attention_row_in_envelope (one query row per caption
+ * against the encoder keys / a growing key-value cache: incremental captioning decode) were ADDED the same way.
  * INTEGRATION.md section 2 lists the breaks per version. */
 #define HERO_ABI_VERSION 3
 int hero_abi_version(void);
@@ -344,8 +346,31 @@ int hero_dec_attention_bwd(const void* q, const void* k, const void* v, const fl
                            const void* dctx, void* dq, void* dk, void* dv, int N, int Lq, int Lk, int H, int ldq, int ldkv,
                            int causal, float scale, int dtype, const HeroDropout* dropout, hero_stream_t stream);
 
+/* Incremental decoding (inference only: no dropout, no stats, no backward): ONE query row per  */
+/* caption, the same arithmetic - scores = <q, k_j> * scale + key_mask_add[n, j], softmax in fp32, */
+/* ctx = sum_j p_j v_j in a fixed order, no atomics - and ctx [N, H*64] written in full.          */
+/*   hero_dec_attention_row    decoder-encoder attention of one decoder position: q [N, ldq], k / v */
+/*       rows n*Lk + j with leading dimension ldkv (the packed K|V projection of the encoder rows, */
+/*       computed once per decode), key_mask_add [N, Lk] fp32 or NULL.                            */
+/*   hero_dec_attention_step   causal self-attention of position t against a cache: qkv [N, 3*H*64] */
+/*       is this step's packed Q|K|V projection; kv_cache [N, Tcap, 2*H*64] holds K|V of the        */
+/*       positions 0 .. t-1 on entry, and the kernel ALSO copies this step's K|V bits into its row t */
+/*       (it reads position t from qkv, never from the row it writes).  Rows behind t are neither  */
+/*       read nor written; no causal term is needed, the later keys are not there.                */
+/*       t = pos_dev ? *pos_dev : pos - a device int32, so that one captured launch serves every   */
+/*       step.  A device t outside [0, Tcap) cannot be refused on the host: the kernel then leaves */
+/*       the cache alone and writes zeros to ctx.                                                 */
+/* Envelope: fp32 / bf16, 1 <= Lk <= 128, 1 <= Tcap <= 128, H >= 1, N >= 1, a host pos in         */
+/* [0, Tcap); ldq, ldkv multiples of 8 and >= H*64; pointers 16-byte aligned.  Outside it           */
+/* HERO_ERR_ARG, no launch.  Plain arguments: a backward-compatible addition, HERO_ABI_VERSION stays. */
+int hero_dec_attention_row_in_envelope(int dtype, int Lk);
+int hero_dec_attention_row(const void* q, const void* k, const void* v, const float* key_mask_add, void* ctx,
+                           int N, int Lk, int H, int ldq, int ldkv, float scale, int dtype, hero_stream_t stream);
+int hero_dec_attention_step(const void* qkv, void* kv_cache, void* ctx, const int* pos_dev, int pos,
+                            int N, int Tcap, int H, float scale, int dtype, hero_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------ */
-/* Row gathers / scatters                                                                       */
+/* Row gathers / scatters                                                                      */
 /* ------------------------------------------------------------------------------------------ */
 /* out[r] = idx[r] >= 0 ? a[idx[r]] : (idx[r] == -1 ? 0 : b[-idx[r]-2]).                         */
 /* Replaces torch.gather(cat([img_emb, txt_emb]), gather_index) (model/encoder.py:271-279) and  */
