@@ -291,7 +291,14 @@ __global__ __launch_bounds__(256) void dec_attn_bwd_kernel(DecAttn a) {
 //                wave also copies that row's K|V columns of its head into cache row t (bits, not values) and never reads them
 //                back.  t comes from the host or from a device int32; a device t outside [0, Tcap) writes nothing to the
 //                cache and zeros to ctx.
-constexpr int DR_WAVES = 4, DR_Q = 64, DR_P = DA_MAX_LK, DR_RED = 4 * 64, DR_LDS = DR_Q + DR_P + DR_RED;   // floats per wave
+//   grouped      cross mode with group > 1: row n reads the keys, values and key mask of block n / group - the rows of one
+//                caption's beams share the caption's encoder K|V, which are not replicated.
+//   beam         step mode with a table anc [N, Tcap]: key / value j < t of row n come from cache row anc[n * Tcap + j] (clamped
+//                into [0, N)) at position j - a beam reads its ancestors' rows where they were written, nothing is copied.  Every
+//                wave still writes ITS row's K|V to position t, and no wave reads position t of the cache, so the rows of one
+//                launch do not race.  The lane that owns key j keeps the row index in a per-wave LDS table for the P V loop.
+constexpr int DR_WAVES = 4, DR_Q = 64, DR_P = DA_MAX_LK, DR_RED = 4 * 64, DR_ANC = DA_MAX_LK;
+constexpr int DR_LDS = DR_Q + DR_P + DR_RED + DR_ANC;                                                      // 4-byte words per wave
 
 struct DecRow {
   const void* q;           // [N, ldq], the head's 64 columns at h * 64
@@ -303,6 +310,8 @@ struct DecRow {
   const int* pos_dev;
   int pos, N, rows_n, H, ldq, ldkv;   // rows_n = Lk (cross) | Tcap (step)
   float scale;
+  const int* anc;          // step mode: [N, Tcap] cache row of every earlier position, or NULL = the row's own
+  int group;               // cross mode: rows per key / value block (1 = a block per row)
 };
 
 // 64-dim dot product of a global row with the wave's q in LDS, d ascending in groups of 4 as in `dots`; 16-byte loads
@@ -336,6 +345,7 @@ __global__ __launch_bounds__(256) void dec_attn_row_kernel(DecRow a) {
   const bool active = pair < a.N * a.H;                             // wave-uniform; idle waves only keep the barriers company
   const int n = active ? pair / a.H : 0, h = active ? pair % a.H : 0;
   float *qs = lds + wave * DR_LDS, *ps = qs + DR_Q, *red = ps + DR_P;
+  int* as = reinterpret_cast<int*>(red + DR_RED);                   // beam: the cache row of key j
   const int D = a.H * 64;
   T* out = static_cast<T*>(a.ctx) + (size_t)n * D + h * 64;
   int Lm = a.rows_n;                                                // keys read from memory
@@ -348,9 +358,12 @@ __global__ __launch_bounds__(256) void dec_attn_row_kernel(DecRow a) {
     Lm = t;
   }
   const int Lall = Lm + (STEP ? 1 : 0);                             // <= 128
-  const size_t row0 = (size_t)n * a.rows_n;
-  const T* K = static_cast<const T*>(a.k) + row0 * a.ldkv + h * 64;
-  const T* V = static_cast<const T*>(a.v) + row0 * a.ldkv + h * 64;
+  const size_t row0 = (size_t)n * a.rows_n;                         // the row's own block: the cache row that is written
+  const int* anc = STEP ? a.anc : nullptr;                          // uniform over the grid
+  const int nb = STEP ? n : n / a.group;                            // the block the keys come from (beam: per key, below)
+  const size_t rowk = anc ? 0 : (size_t)nb * a.rows_n;
+  const T* K = static_cast<const T*>(a.k) + rowk * a.ldkv + h * 64;
+  const T* V = static_cast<const T*>(a.v) + rowk * a.ldkv + h * 64;
   const T* Kt = STEP ? static_cast<const T*>(a.kt) + (size_t)n * a.ldq + h * 64 : nullptr;
   const T* Vt = STEP ? static_cast<const T*>(a.vt) + (size_t)n * a.ldq + h * 64 : nullptr;
   if (active && lane < 16)
@@ -364,14 +377,20 @@ __global__ __launch_bounds__(256) void dec_attn_row_kernel(DecRow a) {
   }
   __syncthreads();
   if (active) {
-    const float* km = (!STEP && a.key_mask) ? a.key_mask + (size_t)n * a.rows_n : nullptr;
+    const float* km = (!STEP && a.key_mask) ? a.key_mask + (size_t)nb * a.rows_n : nullptr;
     float s[2];
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       const int j = lane + 64 * b;
       s[b] = -3.0e38f;
       if (j < Lall) {
-        const T* row = (STEP && j == Lm) ? Kt : K + (size_t)j * a.ldkv;
+        size_t jr = j;
+        if (anc && j < Lm) {
+          const int src = min(max(anc[row0 + j], 0), a.N - 1);
+          as[j] = src;
+          jr = (size_t)src * a.rows_n + j;
+        }
+        const T* row = (STEP && j == Lm) ? Kt : K + jr * a.ldkv;
         s[b] = dot_row<T>(row, qs) * a.scale;
         if (km) s[b] += km[j];
       }
@@ -387,7 +406,8 @@ __global__ __launch_bounds__(256) void dec_attn_row_kernel(DecRow a) {
   if (active) {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int j = r; j < Lall; j += 4) {
-      const T* row = (STEP && j == Lm) ? Vt : V + (size_t)j * a.ldkv;
+      const size_t jr = (anc && j < Lm) ? (size_t)as[j] * a.rows_n + j : (size_t)j;
+      const T* row = (STEP && j == Lm) ? Vt : V + jr * a.ldkv;
       fma4(acc, ps[j], V4<T>::ld(row + d));
     }
     *reinterpret_cast<float4*>(red + r * 64 + d) = acc;
@@ -456,23 +476,43 @@ extern "C" int hero_dec_attention_row(const void* q, const void* k, const void* 
   HERO_REQUIRE(row_in_envelope(dtype, Lk) && H >= 1 && N >= 1,
                "hero_dec_attention_row: outside the envelope (fp32 / bf16, 1 <= Lk <= %d, H >= 1, N >= 1): dtype=%d N=%d Lk=%d H=%d",
                DA_MAX_LK, dtype, N, Lk, H);
-  const DecRow a = {q, k, v, nullptr, nullptr, nullptr, key_mask_add, ctx, nullptr, 0, N, Lk, H, ldq, ldkv, scale};
+  const DecRow a = {q, k, v, nullptr, nullptr, nullptr, key_mask_add, ctx, nullptr, 0, N, Lk, H, ldq, ldkv, scale, nullptr, 1};
   return launch_row("hero_dec_attention_row", a, false, dtype, stream);
 }
 
-extern "C" int hero_dec_attention_step(const void* qkv, void* kv_cache, void* ctx, const int* pos_dev, int pos, int N, int Tcap, int H,
-                                       float scale, int dtype, hero_stream_t stream) {
+extern "C" int hero_dec_attention_row_grouped(const void* q, const void* k, const void* v, const float* key_mask_add, void* ctx, int N,
+                                              int group, int Lk, int H, int ldq, int ldkv, float scale, int dtype, hero_stream_t stream) {
+  HERO_REQUIRE(row_in_envelope(dtype, Lk) && H >= 1 && N >= 1 && group >= 1,
+               "hero_dec_attention_row_grouped: outside the envelope (fp32 / bf16, 1 <= Lk <= %d, H >= 1, N >= 1, group >= 1): dtype=%d "
+               "N=%d group=%d Lk=%d H=%d", DA_MAX_LK, dtype, N, group, Lk, H);
+  const DecRow a = {q, k, v, nullptr, nullptr, nullptr, key_mask_add, ctx, nullptr, 0, N, Lk, H, ldq, ldkv, scale, nullptr, group};
+  return launch_row("hero_dec_attention_row_grouped", a, false, dtype, stream);
+}
+
+static int step(const char* what, const void* qkv, void* kv_cache, const int* anc, void* ctx, const int* pos_dev, int pos, int N, int Tcap,
+                int H, float scale, int dtype, hero_stream_t stream) {
   HERO_REQUIRE(row_in_envelope(dtype, Tcap) && H >= 1 && N >= 1,
-               "hero_dec_attention_step: outside the envelope (fp32 / bf16, 1 <= Tcap <= %d, H >= 1, N >= 1): dtype=%d N=%d Tcap=%d H=%d",
-               DA_MAX_LK, dtype, N, Tcap, H);
-  HERO_REQUIRE(pos_dev || (pos >= 0 && pos < Tcap), "hero_dec_attention_step: position %d outside [0, Tcap = %d)", pos, Tcap);
-  HERO_REQUIRE(H <= (1 << 20), "hero_dec_attention_step: H too large");
+               "%s: outside the envelope (fp32 / bf16, 1 <= Tcap <= %d, H >= 1, N >= 1): dtype=%d N=%d Tcap=%d H=%d", what, DA_MAX_LK,
+               dtype, N, Tcap, H);
+  HERO_REQUIRE(pos_dev || (pos >= 0 && pos < Tcap), "%s: position %d outside [0, Tcap = %d)", what, pos, Tcap);
+  HERO_REQUIRE(H <= (1 << 20), "%s: H too large", what);
   const int D = H * 64;
   const size_t es = dtype == HERO_F32 ? 4 : 2;
   const char* row = static_cast<const char*>(qkv);
   const DecRow a = {qkv, kv_cache, kv_cache ? static_cast<const char*>(kv_cache) + D * es : nullptr, qkv ? row + D * es : nullptr,
-                    qkv ? row + 2 * D * es : nullptr, kv_cache, nullptr, ctx, pos_dev, pos, N, Tcap, H, 3 * D, 2 * D, scale};
-  return launch_row("hero_dec_attention_step", a, true, dtype, stream);
+                    qkv ? row + 2 * D * es : nullptr, kv_cache, nullptr, ctx, pos_dev, pos, N, Tcap, H, 3 * D, 2 * D, scale, anc, 1};
+  return launch_row(what, a, true, dtype, stream);
+}
+
+extern "C" int hero_dec_attention_step(const void* qkv, void* kv_cache, void* ctx, const int* pos_dev, int pos, int N, int Tcap, int H,
+                                       float scale, int dtype, hero_stream_t stream) {
+  return step("hero_dec_attention_step", qkv, kv_cache, nullptr, ctx, pos_dev, pos, N, Tcap, H, scale, dtype, stream);
+}
+
+extern "C" int hero_dec_attention_step_beam(const void* qkv, void* kv_cache, const int* anc, void* ctx, const int* pos_dev, int pos, int N,
+                                            int Tcap, int H, float scale, int dtype, hero_stream_t stream) {
+  HERO_REQUIRE(anc, "hero_dec_attention_step_beam: null pointer");
+  return step("hero_dec_attention_step_beam", qkv, kv_cache, anc, ctx, pos_dev, pos, N, Tcap, H, scale, dtype, stream);
 }
 
 extern "C" int hero_dec_attention_fwd(const void* q, const void* k, const void* v, const float* key_mask_add, void* ctx, float* stats,

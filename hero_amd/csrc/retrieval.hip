@@ -30,13 +30,6 @@ struct SelShared {
   int bin, above, cnt, count;
 };
 
-// fp32 -> 32 bits that order as unsigned integers like the floats do (-0 is folded into +0 first: equal scores must tie)
-__device__ __forceinline__ uint32_t order_bits(float s) {
-  const uint32_t b = __float_as_uint(s + 0.f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float order_float(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
 // inclusive scan over the NT threads of the workgroup (thread order); total = the sum over all of them
 template <int NT>
 __device__ __forceinline__ int block_incl_scan(int v, int* wsum, int& total) {

@@ -67,12 +67,75 @@ class TvcDecodeState(object):
                  wid, the int32 word ids of the step
         PyTorch  cross_k / cross_v [N, Lv, D], self_k / self_v [N, t, D] grown by concatenation, mask_add [N, 1, 1, Lv], t
     Every buffer keeps its address for the life of the state, so one captured step serves all steps and, after `refill`, all
-    batches of the same shape."""
+    batches of the same shape.
 
-    def __init__(self, fused, N, Lv, max_step):
+    Beam search (beam > 1) decodes rows = N * beam rows, row n * beam + b = beam b of caption n.  The encoder side stays N
+    blocks on both routes (cross_kv / cross_k / cross_v, mask_add): the rows of a caption share them.  Fused: cache
+    [rows, max_step, 2D] is NEVER reordered - a row's K|V stay where the step kernel wrote them and the attention follows the
+    beam's ancestry through `anc`; PyTorch: self_k / self_v [rows, t, D] are re-gathered by parent after every selection
+    (HeroForTvc.reorder_decode_state).  `tables` (a BeamTables, when asked for) holds what hero_beam_select updates."""
+
+    def __init__(self, fused, N, Lv, max_step, beam=1):
         self.fused, self.N, self.Lv, self.max_step, self.t = fused, N, Lv, max_step, 0
+        self.beam, self.rows, self.tables = beam, N * beam, None
         self.cross_kv, self.cache, self.cross_k, self.cross_v, self.self_k, self.self_v = [], [], [], [], [], []
         self.mask_add = self.pos = self.pid = self.wid = None
+
+    @property
+    def anc(self):
+        """The ancestry table the step kernel reads; None with one beam per caption (every row reads its own cache row)."""
+        return self.tables.anc if self.beam > 1 else None
+
+
+class BeamTables(object):
+    """The tables of a beam search over rows = N * B decode rows (include/hero_hip.h "Beam-search selection"): cum [rows] fp32
+    the summed log-probabilities, fin / len [rows] finished flag and token count, ids / anc [rows, max_step] the tokens and
+    the cache row of every decoded position, ws the selection kernel's workspace.  int32 on the kernels' route (the kernel's
+    types), int64 indices in PyTorch ops."""
+    DEAD = -1.0e30          # the initial score of the beams 1 .. B-1: below every real candidate of beam 0
+
+    def __init__(self, N, B, max_step, device, fused):
+        R, it = N * B, torch.int32 if fused else torch.long
+        self.N, self.B = N, B
+        self.cum = torch.empty((R,), dtype=torch.float32, device=device)
+        self.fin, self.len = (torch.empty((R,), dtype=it, device=device) for _ in range(2))
+        self.ids, self.anc = (torch.empty((R, max_step), dtype=it, device=device) for _ in range(2))
+        self.ws = torch.empty((R * B,), dtype=torch.int64, device=device) if fused else None
+        self._cum0 = torch.full((N, B), self.DEAD, dtype=torch.float32, device=device)
+        self._cum0[:, 0] = 0.0
+        self._anc0 = torch.arange(R, dtype=it, device=device).unsqueeze(1).expand(R, max_step).contiguous()
+
+    def reset(self):
+        self.cum.copy_(self._cum0.view(-1))
+        self.fin.zero_()
+        self.len.zero_()
+        self.ids.zero_()
+        self.anc.copy_(self._anc0)
+
+
+def beam_select_torch(scores, tb, t, eos):
+    """hero_beam_select in PyTorch ops on a BeamTables of int64 indices: scores [rows, V] -> the parent ROW of every new beam
+    (the tables are replaced, not updated in place).  fp32 throughout; a stable descending sort gives the tie rule (among
+    equal scores the lower flat index b * V + v)."""
+    N, B, V = tb.N, tb.B, scores.shape[1]
+    x = scores.float()
+    cand = tb.cum.unsqueeze(1) + (x - torch.logsumexp(x, dim=1, keepdim=True))
+    done = tb.fin.bool().unsqueeze(1)
+    only_eos = torch.full_like(cand, float("-inf"))
+    only_eos[:, eos] = tb.cum
+    cand = torch.where(done, only_eos, cand).view(N, B * V)
+    val, idx = torch.sort(cand, dim=1, descending=True, stable=True)
+    val, idx = val[:, :B].reshape(-1), idx[:, :B]
+    rows = (torch.arange(N, device=x.device).unsqueeze(1) * B + idx // V).reshape(-1)
+    v = (idx % V).reshape(-1)
+    was_done = tb.fin[rows]
+    tb.cum = val
+    tb.fin = was_done | (v == eos).to(was_done.dtype)
+    tb.len = tb.len[rows] + (1 - was_done)
+    tb.ids, tb.anc = tb.ids[rows], tb.anc[rows]
+    tb.ids[:, t] = v
+    tb.anc[:, t] = rows
+    return rows, v
 
 
 class BertDecoderLayer(nn.Module):
@@ -118,10 +181,10 @@ class BertDecoderLayer(nn.Module):
         sa, ca = self.self_attention, self.dec_enc_attention
         wq, bq, wk, bk, wv, bv = sa.qkv_params()
         qkv = HF.k_linear(x, HF.packed((wq, wk, wv), x.dtype), HF.packed((bq, bk, bv), torch.float32))
-        a = T.k_dec_attn_step(qkv, state.cache[li], state.pos, state.N, sa.num_attention_heads)
+        a = T.k_dec_attn_step(qkv, state.cache[li], state.pos, state.rows, sa.num_attention_heads, anc=state.anc)
         a = self.add_norm_1(a, x)
         q = HF.k_linear(a, HF.packed((ca.query.weight,), a.dtype), HF.packed((ca.query.bias,), torch.float32))
-        c = T.k_dec_attn_row(q, state.cross_kv[li], state.mask_add, state.N, state.Lv, ca.num_attention_heads)
+        c = T.k_dec_attn_row(q, state.cross_kv[li], state.mask_add, state.rows, state.Lv, ca.num_attention_heads, group=state.beam)
         c = self.add_norm_2(c, a)
         o = self.add_norm_3
         return HF.FfnBlockFn.apply(c, o.LayerNorm.eps, _drop(o.dropout, x.device), self.intermidiate.dense.weight,
@@ -135,7 +198,9 @@ class BertDecoderLayer(nn.Module):
             k, v = torch.cat([state.self_k[li], k], dim=1), torch.cat([state.self_v[li], v], dim=1)
         state.self_k[li], state.self_v[li] = k, v
         a = _add_norm_torch(self.add_norm_1, _attend_torch(sa, sa.query(x), k, v, None), x)
-        c = _attend_torch(ca, ca.query(a), state.cross_k[li], state.cross_v[li], state.mask_add)
+        # the beams of a caption are the query rows of ONE attention over the caption's encoder keys: [N, beam, D]
+        q = ca.query(a).view(state.N, state.beam, -1)
+        c = _attend_torch(ca, q, state.cross_k[li], state.cross_v[li], state.mask_add).view(state.rows, 1, -1)
         c = _add_norm_torch(self.add_norm_2, c, a)
         h = F.gelu(self.intermidiate.dense(c))
         return _add_norm_torch(self.add_norm_3, h, c)
@@ -309,29 +374,42 @@ class HeroForTvc(HeroModel):
         return (self.fused_decoder and encoder_outputs.is_cuda and max_step <= self.max_cache and Lv <= self.max_lk
                 and T.in_envelope_row(HF.compute_dtype(), max_step) and T.in_envelope_row(HF.compute_dtype(), Lv))
 
+    max_beam = T.MAX_BEAM   # Python-side limit on the beam size of the kernels' route (never above hero_beam_select's envelope)
+
     @torch.no_grad()
-    def init_decode_state(self, encoder_outputs, encoder_masks, max_step):
+    def init_decode_state(self, encoder_outputs, encoder_masks, max_step, beam_size=1, beam_tables=False):
         """The state of an incremental decode of up to `max_step` positions over encoder_outputs [N, Lv, D] and their 0/1 mask:
         the cross-attention keys and values of every layer (they do not change during a decode), empty self-attention caches,
         position 0.  On the kernels inside their envelope, in PyTorch ops otherwise (CPU tensors, fused_decoder = False,
-        max_step or Lv above 128 or above the Python-side limits)."""
+        max_step or Lv above 128 or above the Python-side limits).
+        beam_size > 1: N * beam_size decode rows over the SAME N blocks of encoder keys, and the beam tables (also made for
+        beam_size = 1 when `beam_tables` asks); the kernels' route then also needs beam size, vocabulary and max_step inside the
+        selection kernel's envelope.  With beam_size = 1 state and kernels are those of the greedy decode."""
         N, Lv, D = encoder_outputs.shape
         if max_step < 1 or max_step > self.position_embeddings.num_embeddings:
             raise ValueError("HeroForTvc: max_step %d outside [1, %d]" % (max_step, self.position_embeddings.num_embeddings))
-        state = TvcDecodeState(self._fused_step(encoder_outputs, max_step), N, Lv, max_step)
-        dev = encoder_outputs.device
+        if beam_size < 1:
+            raise ValueError("HeroForTvc: beam size %d < 1" % beam_size)
+        want_tables = beam_tables or beam_size > 1
+        fused = self._fused_step(encoder_outputs, max_step)
+        if fused and want_tables:
+            fused = beam_size <= self.max_beam and T.in_envelope_beam(HF.compute_dtype(), self.config.f_config.vocab_size, beam_size, max_step)
+        state = TvcDecodeState(fused, N, Lv, max_step, beam_size)
+        dev, R = encoder_outputs.device, state.rows
         if state.fused:
             cd = HF.compute_dtype()
             for _ in self.decoder.layer:
                 state.cross_kv.append(torch.empty((N * Lv, 2 * D), dtype=cd, device=dev))
-                state.cache.append(torch.zeros((N, max_step, 2 * D), dtype=cd, device=dev))
+                state.cache.append(torch.zeros((R, max_step, 2 * D), dtype=cd, device=dev))
             state.mask_add = torch.empty((N, Lv), dtype=torch.float32, device=dev)
             state.pos = torch.zeros((1,), dtype=torch.int32, device=dev)
-            state.pid = torch.zeros((N,), dtype=torch.int32, device=dev)
-            state.wid = torch.zeros((N,), dtype=torch.int32, device=dev)
+            state.pid = torch.zeros((R,), dtype=torch.int32, device=dev)
+            state.wid = torch.zeros((R,), dtype=torch.int32, device=dev)
         else:
             n = len(self.decoder.layer)
             state.self_k, state.self_v = [None] * n, [None] * n
+        if want_tables:
+            state.tables = BeamTables(N, beam_size, max_step, dev, state.fused)
         return self.refill_decode_state(state, encoder_outputs, encoder_masks)
 
     @torch.no_grad()
@@ -341,6 +419,8 @@ class HeroForTvc(HeroModel):
             raise ValueError("HeroForTvc: the decode state was made for [%d, %d] encoder rows, got %s"
                              % (state.N, state.Lv, tuple(encoder_outputs.shape)))
         state.t = 0
+        if state.tables is not None:
+            state.tables.reset()
         if state.fused:
             enc2 = HF._as2d(HF.cast(encoder_outputs, HF.compute_dtype()))
             for li, layer in enumerate(self.decoder.layer):
@@ -356,14 +436,25 @@ class HeroForTvc(HeroModel):
         return state
 
     @torch.no_grad()
+    def reorder_decode_state(self, state, parent_rows):
+        """After a beam selection: row i continues row parent_rows[i].  The kernels' route keeps its caches where they are (the
+        step kernel follows the tables' `anc`); the PyTorch route gathers the keys and values it has kept."""
+        if state.fused:
+            return
+        state.self_k = [k.index_select(0, parent_rows) for k in state.self_k]
+        state.self_v = [v.index_select(0, parent_rows) for v in state.self_v]
+
+    @torch.no_grad()
     def decode_step(self, state, last_ids):
-        """last_ids [N]: the token of every caption at the state's position -> the prediction scores [N, vocab] of the next
-        one (in the compute dtype on the kernels); the position advances - on the device for the fused state, nothing here
-        reads it on the host, so the call can be captured and replayed."""
+        """last_ids [rows] (rows = N, or N * beam): the token of every row at the state's position -> the prediction scores
+        [rows, vocab] of the next one (in the compute dtype on the kernels); the position advances - on the device for the fused
+        state, nothing here reads it on the host, so the call can be captured and replayed.  A fused state takes its own
+        `wid` buffer as last_ids without a copy (hero_beam_select writes the next ids there)."""
         emb = self.v_encoder.f_encoder.embeddings
         V = self.config.f_config.vocab_size
         if state.fused:
-            state.wid.copy_(last_ids)
+            if last_ids is not state.wid:
+                state.wid.copy_(last_ids)
             ln = self.emb_LayerNorm
             x = HF.embed_ln(None, ln.weight, ln.bias, ln.eps, None, HF.compute_dtype(),
                             tables=(emb.word_embeddings.weight, self.position_embeddings.weight), idxs=(state.wid, state.pid),
@@ -376,7 +467,7 @@ class HeroForTvc(HeroModel):
             return scores[:, :V]
         if state.t >= state.max_step:
             raise ValueError("HeroForTvc: decode step %d of a state made for %d" % (state.t, state.max_step))
-        pos_ids = torch.full((state.N, 1), state.t, dtype=torch.long, device=last_ids.device)
+        pos_ids = torch.full((state.rows, 1), state.t, dtype=torch.long, device=last_ids.device)
         x = emb.word_embeddings(last_ids.unsqueeze(1)) + self.position_embeddings(pos_ids)
         ln = self.emb_LayerNorm
         x = F.layer_norm(x, ln.normalized_shape, ln.weight, ln.bias, ln.eps)
@@ -417,7 +508,12 @@ class TvcGenerator(object):
     ONE row per caption against the keys and values kept from the earlier steps, and the keys / values of the encoder rows are
     projected once per decode.  use_graph = True (needs kv_cache, and the kernels' route) captures that step - embedding, both
     layers, projection, arg-max, the id write at the device position, the position increment - once per (N, Lv, max_step) on one
-    stream and replays it max_step times; between batches of one shape only the state's buffers are refilled."""
+    stream and replays it max_step times; between batches of one shape only the state's buffers are refilled.
+
+    beam_decode(batch, beam_size) searches with beam_size beams per caption on the same incremental step (needs kv_cache; under
+    use_graph the beam step is captured once per (N, beam, Lv, max_step) and shares MAX_GRAPHS and `counts` with the greedy
+    graphs): the step runs N * beam rows, hero_beam_select takes the beam tables to the next step on the device, and neither
+    the key/value cache nor the encoder keys are copied or replicated."""
 
     MAX_GRAPHS = 8
 
@@ -445,42 +541,50 @@ class TvcGenerator(object):
     def _weights_signature(self):
         return tuple(p._version for p in self.model.parameters()) + (HF.weight_epoch(),)
 
-    def _decode_graph(self, encoder_outputs, enc_mask):
+    def _replay(self, kind, encoder_outputs, enc_mask, make):
+        """The captured step of `kind` for this shape, refilled with the batch and replayed max_step times -> its entry.  On first
+        use make() -> dict(state, last = the ids buffer the step embeds, step = one step on device buffers only, ...): the step runs
+        once eagerly, so that every compute copy of a weight exists, and is then captured on one stream - a straight line."""
         model = self.model
         N, Lv = encoder_outputs.shape[:2]
-        dev = encoder_outputs.device
-        key = (N, Lv, self.max_step, HF.compute_dtype(), str(dev), HF.weight_cache_generation())
+        key = kind + (N, Lv, self.max_step, HF.compute_dtype(), str(encoder_outputs.device), HF.weight_cache_generation())
         hit = self._graphs.get(key)
         if hit is None:
-            state = model.init_decode_state(encoder_outputs, enc_mask, self.max_step)
-            if not state.fused:
+            hit = make()
+            if not hit["state"].fused:
                 raise ValueError("TvcGenerator: use_graph needs the kernels' route (CUDA tensors, fused_decoder, max_step and Lv "
-                                 "inside the envelope)")
-            last = torch.full((N,), self.bos, dtype=torch.long, device=dev)
-            output_ids = torch.zeros((N, self.max_step), dtype=torch.long, device=dev)
-            self._step(state, last, output_ids)                 # eager: every compute copy of a weight exists before the capture
+                                 "inside the envelope; beam search: beam size and vocabulary, too)")
+            hit["step"]()
             key = key[:-1] + (HF.weight_cache_generation(),)
-            model.refill_decode_state(state, encoder_outputs, enc_mask)
-            last.fill_(self.bos)
+            model.refill_decode_state(hit["state"], encoder_outputs, enc_mask)
             torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):                       # one stream, no forks: the graph is a straight line
-                self._step(state, last, output_ids)
+            hit["graph"] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(hit["graph"]):
+                hit["step"]()
             if len(self._graphs) >= self.MAX_GRAPHS:
                 self._graphs.clear()
-            hit = self._graphs[key] = dict(graph=graph, state=state, last=last, out=output_ids, wsig=self._weights_signature())
+            hit["wsig"] = self._weights_signature()
+            self._graphs[key] = hit
             self.counts["captures"] += 1
-        state, last, output_ids = hit["state"], hit["last"], hit["out"]
         wsig = self._weights_signature()
         if wsig != hit["wsig"]:                                 # the replay calls no HF.packed: bring the compute copies up to date
             HF.refresh_weight_cache()
             hit["wsig"] = wsig
-        model.refill_decode_state(state, encoder_outputs, enc_mask)
-        last.fill_(self.bos)
+        model.refill_decode_state(hit["state"], encoder_outputs, enc_mask)
+        hit["last"].fill_(self.bos)
         for _ in range(self.max_step):
             hit["graph"].replay()
         self.counts["replayed"] += self.max_step
-        return output_ids
+        return hit
+
+    def _decode_graph(self, encoder_outputs, enc_mask):
+        def make():
+            N, dev = encoder_outputs.shape[0], encoder_outputs.device
+            state = self.model.init_decode_state(encoder_outputs, enc_mask, self.max_step)
+            last = torch.full((N,), self.bos, dtype=torch.long, device=dev)
+            out = torch.zeros((N, self.max_step), dtype=torch.long, device=dev)
+            return dict(state=state, last=last, out=out, step=lambda: self._step(state, last, out))
+        return self._replay((), encoder_outputs, enc_mask, make)["out"]
 
     @torch.no_grad()
     def _decode_cached(self, encoder_outputs, enc_mask):
@@ -522,6 +626,66 @@ class TvcGenerator(object):
             last_out = scores[:, :model.config.f_config.vocab_size].float().argmax(dim=-1)
             output_ids[:, step] = last_out
         return [self.cut_eos(ids) for ids in output_ids.tolist()]
+
+    # ---- beam search --------------------------------------------------------------------------------------------------------
+    def _beam_state(self, encoder_outputs, enc_mask, beam_size):
+        state = self.model.init_decode_state(encoder_outputs, enc_mask, self.max_step, beam_size, beam_tables=True)
+        if state.fused:
+            state.wid.fill_(self.bos)
+            return state, state.wid
+        return state, torch.full((state.rows,), self.bos, dtype=torch.long, device=encoder_outputs.device)
+
+    def _beam_step(self, state, last):
+        """One beam step on device buffers only: decode_step over all rows, then the selection.  Fused: hero_beam_select updates
+        the tables in place and leaves the next ids in the state's `wid`; the position it reads has already advanced, hence the
+        offset.  PyTorch route: the same algorithm in ops, and the kept keys / values follow their parents.  -> the next ids."""
+        model, tb = self.model, state.tables
+        scores = model.decode_step(state, last)
+        if state.fused:
+            T.k_beam_select(scores, tb.cum, tb.fin, tb.len, tb.ids, tb.anc, state.wid, tb.ws, state.pos, state.N, state.beam,
+                            scores.shape[1], self.eos, pos_offset=-1)
+            return state.wid
+        rows, nxt = beam_select_torch(scores, tb, state.t - 1, self.eos)
+        model.reorder_decode_state(state, rows)
+        return nxt
+
+    def _beam_graph(self, encoder_outputs, enc_mask, beam_size):
+        """The beam step captured once per (N, beam, Lv, max_step); it shares the graph table with the greedy steps."""
+        def make():
+            state, last = self._beam_state(encoder_outputs, enc_mask, beam_size)
+            return dict(state=state, last=last, step=lambda: self._beam_step(state, last))
+        return self._replay(("beam", beam_size), encoder_outputs, enc_mask, make)["state"]
+
+    @torch.no_grad()
+    def beam_decode(self, batch, beam_size, length_penalty=1.0, encoder_outputs=None, return_scores=False):
+        """Beam search over the incremental decode (needs kv_cache=True): max_step steps of decode_step + selection for
+        N * beam_size rows, no early exit - a finished beam carries `eos` at an unchanged score - then per caption the beam with
+        the largest  cum / max(len, 1) ** length_penalty  (the lower beam among equals), ONE host transfer, and the ids cut at
+        `eos`.  On the kernels' route the selection is hero_beam_select and neither the cache nor the encoder keys are copied or
+        replicated; use_graph replays the captured step.  -> list of id lists[, list of the picked beams' scores]."""
+        if not self.kv_cache:
+            raise ValueError("TvcGenerator: beam_decode runs on the incremental decode step, it needs kv_cache=True")
+        if beam_size < 1:
+            raise ValueError("TvcGenerator: beam size %d < 1" % beam_size)
+        model = self.model
+        if encoder_outputs is None:
+            encoder_outputs = model.encode(batch)
+        enc_mask = batch["cap_attn_mask"]
+        if self.use_graph:
+            state = self._beam_graph(encoder_outputs, enc_mask, beam_size)
+        else:
+            state, last = self._beam_state(encoder_outputs, enc_mask, beam_size)
+            for _ in range(self.max_step):
+                last = self._beam_step(state, last)
+        tb, N, B = state.tables, state.N, beam_size
+        norm = tb.cum.view(N, B) / tb.len.view(N, B).clamp(min=1).to(torch.float32) ** float(length_penalty)
+        best = torch.sort(norm, dim=1, descending=True, stable=True).indices[:, :1]            # stable: the lower beam wins a tie
+        rows = torch.arange(N, device=best.device) * B + best[:, 0]
+        packed = torch.cat([tb.ids[rows].to(torch.int32), norm.gather(1, best).contiguous().view(torch.int32)], dim=1).cpu()
+        ids = [self.cut_eos(r) for r in packed[:, :-1].tolist()]
+        if return_scores:
+            return ids, packed[:, -1:].contiguous().view(torch.float32).view(-1).tolist()
+        return ids
 
     def cut_eos(self, ids):
         out_ids = []

@@ -1,12 +1,15 @@
 """Autograd nodes of the captioning decoder (TVC) on the libhero_hip.so kernels hero_dec_attention_fwd / _bwd and
-hero_smooth_ce_fwd / _bwd (include/hero_hip.h "Decoder attention", "Label-smoothed loss"; reference: model/tvc.py:19-154).
+hero_smooth_ce_fwd / _bwd (include/hero_hip.h "Decoder attention", "Label-smoothed loss"; reference: model/tvc.py:19-154), and the
+inference-only kernels of its incremental and beam-search decode.
 
     DecAttnCoreFn     the attention kernel on projected operands: a fused [N*L, 3*H*64] Q|K|V buffer (causal self-attention) or a
                       [N*Lq, H*64] query and a [N*Lk, 2*H*64] K|V buffer (decoder-encoder attention, key mask per caption)
     DecAttentionFn    the same with its projections: BertSelfAttention under tri_mask / BertDecEncAttention of a decoder layer
     SmoothCeFn        LabelSmoothingLoss in closed form: per-row losses plus the device pair (sum, number of valid rows)
     k_dec_attn_row / k_dec_attn_step   the one-query-row kernels of incremental decoding (no autograd: inference only) - attention
-                      over the encoder keys, and causal self-attention against a key/value cache that the kernel extends
+                      over the encoder keys, and causal self-attention against a key/value cache that the kernel extends;
+                      `group=` / `anc=` are their beam-search forms (shared encoder keys, a cache read through an ancestry table)
+    k_beam_select     the selection step of beam search over [N * B, vocab] scores (hero_beam_select), in place on device tables
 
 There is no PyTorch route in here: outside the kernels' envelope the nodes raise."""
 import ctypes as C
@@ -91,30 +94,39 @@ def _row_operand(name, t, rows, cols, dtype=None):
                          % (name, rows, cols, " of %s" % dtype if dtype is not None else "", tuple(t.shape), t.dtype))
 
 
-def k_dec_attn_row(q, kv, key_mask_add, N, Lk, H):
+def k_dec_attn_row(q, kv, key_mask_add, N, Lk, H, group=1):
     """Decoder-encoder attention of ONE decoder position per caption (inference: no dropout, no stats):
     q [N, H*64], kv [N*Lk, 2*H*64] the packed K|V projection of the encoder rows, key_mask_add [N, Lk] fp32 | None
-    -> ctx [N, H*64] in the operands' dtype."""
+    -> ctx [N, H*64] in the operands' dtype.
+    group > 1 (the beams of a caption): row r reads block r // group of kv [N//group * Lk, 2*H*64] and of the mask
+    [N//group, Lk] - the encoder K|V are not replicated."""
     if N < 1 or not in_envelope_row(q.dtype, Lk):
         raise ValueError("decoder attention: %s, N=%d, Lk=%d is outside the one-row kernel's envelope (fp32 / bf16, N >= 1, "
                          "1 <= Lk <= %d)" % (q.dtype, N, Lk, MAX_LK))
-    D, es = H * HEAD, q.element_size()
+    if group < 1 or N % group:
+        raise ValueError("decoder attention: N=%d rows are no whole number of groups of %d" % (N, group))
+    D, es, nb = H * HEAD, q.element_size(), N // group
     _row_operand("q", q, N, D)
-    _row_operand("kv", kv, N * Lk, 2 * D, q.dtype)
-    if key_mask_add is not None and (tuple(key_mask_add.shape) != (N, Lk) or key_mask_add.dtype != torch.float32):
-        raise ValueError("decoder attention: key mask must be fp32 [N, Lk], got %s %s" % (tuple(key_mask_add.shape), key_mask_add.dtype))
+    _row_operand("kv", kv, nb * Lk, 2 * D, q.dtype)
+    if key_mask_add is not None and (tuple(key_mask_add.shape) != (nb, Lk) or key_mask_add.dtype != torch.float32):
+        raise ValueError("decoder attention: key mask must be fp32 [%d, Lk], got %s %s" % (nb, tuple(key_mask_add.shape), key_mask_add.dtype))
     ctxt = torch.empty((N, D), dtype=q.dtype, device=q.device)
     p = L.ptr(kv)
-    L.check(L.lib().hero_dec_attention_row(L.ptr(q), p, p + D * es, L.ptr(key_mask_add), L.ptr(ctxt), N, Lk, H, D, 2 * D,
-                                           1.0 / math.sqrt(HEAD), L.dt(q), L.stream()))
+    if group == 1:
+        L.check(L.lib().hero_dec_attention_row(L.ptr(q), p, p + D * es, L.ptr(key_mask_add), L.ptr(ctxt), N, Lk, H, D, 2 * D,
+                                               1.0 / math.sqrt(HEAD), L.dt(q), L.stream()))
+    else:
+        L.check(L.lib().hero_dec_attention_row_grouped(L.ptr(q), p, p + D * es, L.ptr(key_mask_add), L.ptr(ctxt), N, group, Lk, H, D,
+                                                       2 * D, 1.0 / math.sqrt(HEAD), L.dt(q), L.stream()))
     return ctxt
 
 
-def k_dec_attn_step(qkv, cache, pos, N, H):
+def k_dec_attn_step(qkv, cache, pos, N, H, anc=None):
     """Causal self-attention of position `pos` against a key/value cache (inference):
     qkv [N, 3*H*64] this step's packed Q|K|V rows, cache [N, Tcap, 2*H*64] with K|V of the positions < pos; the kernel also
     writes this step's K|V into cache[:, pos].  pos: an int, or a 1-element int32 device tensor (read by the kernel, so that a
     captured launch serves every step; a value outside [0, Tcap) leaves the cache alone and gives zeros).
+    anc [N, Tcap] int32 (beam search): key / value j < pos of row r come from cache row anc[r, j] - the cache is never reordered.
     -> ctx [N, H*64]."""
     D = H * HEAD
     if cache.dim() != 3:
@@ -137,9 +149,64 @@ def k_dec_attn_step(qkv, cache, pos, N, H):
         if not 0 <= pos_host < Tcap:
             raise ValueError("decoder attention: position %d outside [0, Tcap = %d)" % (pos_host, Tcap))
     ctxt = torch.empty((N, D), dtype=qkv.dtype, device=qkv.device)
-    L.check(L.lib().hero_dec_attention_step(L.ptr(qkv), L.ptr(cache), L.ptr(ctxt), pos_dev, pos_host, N, Tcap, H,
-                                            1.0 / math.sqrt(HEAD), L.dt(qkv), L.stream()))
+    if anc is None:
+        L.check(L.lib().hero_dec_attention_step(L.ptr(qkv), L.ptr(cache), L.ptr(ctxt), pos_dev, pos_host, N, Tcap, H,
+                                                1.0 / math.sqrt(HEAD), L.dt(qkv), L.stream()))
+        return ctxt
+    _beam_table("anc", anc, (N, Tcap), torch.int32, qkv.device)
+    L.check(L.lib().hero_dec_attention_step_beam(L.ptr(qkv), L.ptr(cache), L.ptr(anc), L.ptr(ctxt), pos_dev, pos_host, N, Tcap, H,
+                                                 1.0 / math.sqrt(HEAD), L.dt(qkv), L.stream()))
     return ctxt
+
+
+MAX_BEAM, MAX_BEAM_V = 8, 65536                        # hero_amd/csrc/beam.hip
+
+
+def in_envelope_beam(dtype, V, B, Tcap):
+    """The library's own answer (hero_beam_in_envelope): fp32 / bf16, 1 <= B <= 8, B <= V <= 65536, 1 <= Tcap <= 128."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return bool(L.lib().hero_beam_in_envelope(L.F32 if dtype == torch.float32 else L.BF16, int(V), int(B), int(Tcap)))
+
+
+def _beam_table(name, t, shape, dtype, device):
+    if tuple(t.shape) != shape or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise ValueError("beam search: %s must be a contiguous %s %s on %s, got %s %s on %s"
+                         % (name, dtype, shape, device, tuple(t.shape), t.dtype, t.device))
+
+
+def k_beam_select(logits, cum, fin, length, ids, anc, last, workspace, pos, N, B, V, eos, pos_offset=0):
+    """One selection step of beam search for N captions x B beams (row r = n*B + b), in place and on the device
+    (include/hero_hip.h "Beam-search selection"): logits [R, ld >= V] fp32 / bf16; cum [R] fp32; fin, length, last [R] and
+    ids, anc [R, Tcap] int32; workspace: at least R*B int64.  pos: the step's position as an int, or a 1-element int32 device
+    tensor to which `pos_offset` is added (-1 when the counter has already advanced)."""
+    R = N * B
+    if logits.dim() != 2 or logits.shape[0] != R or logits.stride(1) != 1:
+        raise ValueError("beam search: the scores must be [%d, >= V] with unit column stride, got %s" % (R, tuple(logits.shape)))
+    ld, Tcap, dev = logits.stride(0), ids.shape[1] if ids.dim() == 2 else 0, logits.device
+    if not in_envelope_beam(logits.dtype, V, B, Tcap) or N < 1 or ld < V or logits.shape[1] < V or not 0 <= eos < V:
+        raise ValueError("beam search: %s, N=%d, B=%d, V=%d, ld=%d, Tcap=%d, eos=%d is outside the selection kernel's envelope (fp32 / "
+                         "bf16, 1 <= B <= %d, B <= V <= %d, 1 <= Tcap <= %d, ld >= V, 0 <= eos < V)"
+                         % (logits.dtype, N, B, V, ld, Tcap, eos, MAX_BEAM, MAX_BEAM_V, MAX_LK))
+    _beam_table("cum", cum, (R,), torch.float32, dev)
+    for name, t in (("fin", fin), ("len", length), ("last", last)):
+        _beam_table(name, t, (R,), torch.int32, dev)
+    for name, t in (("ids", ids), ("anc", anc)):
+        _beam_table(name, t, (R, Tcap), torch.int32, dev)
+    if workspace.dtype != torch.int64 or workspace.numel() < R * B or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("beam search: the workspace must be at least %d contiguous int64 on %s" % (R * B, dev))
+    if torch.is_tensor(pos):
+        if pos.numel() != 1 or pos.dtype != torch.int32 or pos.device != dev:
+            raise ValueError("beam search: a device position must be one int32 on %s, got %s %s on %s"
+                             % (dev, tuple(pos.shape), pos.dtype, pos.device))
+        pos_dev, pos_host = L.ptr(pos), int(pos_offset)
+    else:
+        pos_dev, pos_host = None, int(pos) + int(pos_offset)
+        if not 0 <= pos_host < Tcap:
+            raise ValueError("beam search: position %d outside [0, Tcap = %d)" % (pos_host, Tcap))
+    # the scores may be the first V columns of a wider buffer (the padded vocabulary): rows ld apart, not contiguous
+    L.check(L.lib().hero_beam_select(logits.data_ptr(), L.ptr(cum), L.ptr(fin), L.ptr(length), L.ptr(ids), L.ptr(anc), L.ptr(last),
+                                     L.ptr(workspace), pos_dev, pos_host, N, B, V, ld, Tcap, eos, L.dt(logits), L.stream()))
 
 
 class DecAttnCoreFn(torch.autograd.Function):

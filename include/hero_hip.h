@@ -50,6 +50,9 @@ const char* hero_last_error(void);
  * HeroGemmEpilogue).
  * Still 3: hero_dec_attention_row, hero_dec_attention_step and hero_dec_attention_row_in_envelope (one query row per caption
  * against the encoder keys / a growing key-value cache: incremental captioning decode) were ADDED the same way.
+ * Still 3: hero_beam_select and hero_beam_in_envelope (the selection step of beam-search captioning), and
+ * hero_dec_attention_row_grouped and hero_dec_attention_step_beam (the one-row attentions of a beam: shared encoder keys, a
+ * cache read through an ancestry table) were ADDED the same way.
  * INTEGRATION.md section 2 lists the breaks per version. */
 #define HERO_ABI_VERSION 3
 int hero_abi_version(void);
@@ -368,6 +371,52 @@ int hero_dec_attention_row(const void* q, const void* k, const void* v, const fl
                            int N, int Lk, int H, int ldq, int ldkv, float scale, int dtype, hero_stream_t stream);
 int hero_dec_attention_step(const void* qkv, void* kv_cache, void* ctx, const int* pos_dev, int pos,
                             int N, int Tcap, int H, float scale, int dtype, hero_stream_t stream);
+
+/* The same two kernels for the rows of a beam search, R = N captions x B beams, without a copy of */
+/* any key or value:                                                                              */
+/*   hero_dec_attention_row_grouped   as hero_dec_attention_row over N rows, but row r reads the    */
+/*       keys, values and key mask of block r / group: k / v hold N / group blocks of Lk rows and    */
+/*       key_mask_add is [N / group, Lk].  group = 1 is hero_dec_attention_row, bit for bit.         */
+/*   hero_dec_attention_step_beam     as hero_dec_attention_step over N rows, with anc [N, Tcap]     */
+/*       int32: key and value j < t of row r are read from cache row anc[r*Tcap + j] at position j,  */
+/*       key t is this step's own row, and the row's K|V bits go to cache position t of row r as     */
+/*       before.  An entry outside [0, N) is clamped into it; entries at j >= t are not read.  With  */
+/*       anc[r, j] == r everywhere the result is hero_dec_attention_step's, bit for bit.             */
+/* Envelope as above, group >= 1, anc not NULL.  Plain arguments: HERO_ABI_VERSION stays.           */
+int hero_dec_attention_row_grouped(const void* q, const void* k, const void* v, const float* key_mask_add, void* ctx,
+                                   int N, int group, int Lk, int H, int ldq, int ldkv, float scale, int dtype,
+                                   hero_stream_t stream);
+int hero_dec_attention_step_beam(const void* qkv, void* kv_cache, const int32_t* anc, void* ctx, const int* pos_dev, int pos,
+                                 int N, int Tcap, int H, float scale, int dtype, hero_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Beam-search selection (captioning decode; inference only)                                   */
+/* ------------------------------------------------------------------------------------------ */
+/* One call per decode step takes the beam tables of N captions x B beams (row r = n*B + b) to  */
+/* the next step.  logits [R, ld] are the step's prediction scores (fp32 / bf16; arithmetic in   */
+/* fp32).  A live beam b offers the candidates (b, v) with score cum[b] + logit[b, v] - lse_b,     */
+/* lse_b = max + log(sum exp(x - max)) over its V scores; a finished beam (fin[b] != 0) offers     */
+/* only (b, eos) with score cum[b].  The B best candidates of a caption - score descending, among  */
+/* equal scores the lower flat index b*V + v - become its new beams in that order; with parent p   */
+/* and token v of new beam i, and t the position of this step:                                    */
+/*   cum[i] = score   fin[i] = fin[p] | (v == eos)   len[i] = len[p] + (fin[p] ? 0 : 1)             */
+/*   ids[i, :t] = ids[p, :t], ids[i, t] = v   anc[i, :t] = anc[p, :t], anc[i, t] = n*B + p          */
+/*   last[i] = v                                                                                  */
+/* cum [R] fp32; fin, len, last [R] and ids, anc [R, Tcap] int32, all updated IN PLACE: every read  */
+/* of a caption's old tables precedes every write.  Columns behind t are left alone.  anc is what   */
+/* hero_dec_attention_step_beam reads at the next step.  The caller starts a caption with          */
+/* cum = {0, -1e30, ...}, fin = len = 0, so that step 0 needs no special case.                      */
+/* t = pos_dev ? *pos_dev + pos : pos - with a device counter `pos` is an OFFSET to it (-1 when the */
+/* counter has already advanced past the step); a device t outside [0, Tcap) changes nothing.      */
+/* workspace: N*B*B*8 bytes, 8-byte aligned, owned by the caller; nothing is allocated, nothing is  */
+/* read on the host, no atomics: two runs give the same bits.                                      */
+/* Envelope: fp32 / bf16, 1 <= B <= 8, B <= V <= 65536, 1 <= Tcap <= 128, ld >= V, 0 <= eos < V,    */
+/* N >= 1, a host position in [0, Tcap).  Outside it HERO_ERR_ARG, no launch.                       */
+/* Plain arguments: a backward-compatible addition, HERO_ABI_VERSION stays.                        */
+int hero_beam_in_envelope(int dtype, int V, int B, int Tcap);
+int hero_beam_select(const void* logits, float* cum, int32_t* fin, int32_t* len, int32_t* ids, int32_t* anc, int32_t* last,
+                     void* workspace, const int* pos_dev, int pos, int N, int B, int V, int ld, int Tcap, int eos, int dtype,
+                     hero_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Row gathers / scatters                                                                      */
