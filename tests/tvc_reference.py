@@ -9,6 +9,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from tests.dropout_hash import _M64, _mix32, _splitmix64
+
 HEAD = 64
 MASKED = -10000.0
 
@@ -84,26 +86,7 @@ def smooth_loss(x, labels, eps, ignore_index=-1, dloss_rows=None, mean=False, up
     return {"loss": loss.detach(), "sum": loss.detach().sum(), "count": count, "dx": x.grad}
 
 
-# ---- the counter-based dropout draw (hero_amd/csrc/common.h: splitmix64, mix32, DropCtx::mask1) ------------------------------
-_M64 = (1 << 64) - 1
-
-
-def _splitmix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & _M64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
-    return x ^ (x >> 31)
-
-
-def _mix32(x):
-    x = x.astype(np.uint64)
-    x ^= x >> np.uint64(16)
-    x = (x * np.uint64(0x7FEB352D)) & np.uint64(0xFFFFFFFF)
-    x ^= x >> np.uint64(15)
-    x = (x * np.uint64(0x846CA68B)) & np.uint64(0xFFFFFFFF)
-    return x ^ (x >> np.uint64(16))
-
-
+# ---- the counter-based dropout draw (hero_amd/csrc/common.h: DropCtx::mask1; its two hashes are in tests/dropout_hash.py) ------
 def dropout_multipliers(seed, site, threshold16, scale, N, H, Lq, Lk):
     """[N, H, Lq, Lk] multipliers of the dropout on P: element index ((n*H + h)*Lq + i) * round_up(Lk, 4) + j (< 2^34)."""
     base = _splitmix64((seed ^ ((site * 0xD6E8FEB86659FD93) & _M64)) & _M64)
