@@ -6,6 +6,7 @@ frames, feed-forward; the reference's module names, `intermidiate` included) pre
 word-embedding table it shares with the encoder.  Both attentions run on one HIP kernel family
 (hero_amd.tvc.DecAttentionFn) and the label-smoothed loss over the vocabulary is one kernel each way
 (hero_amd.tvc.SmoothCeFn): no [rows, vocab] target matrix, no [N, H, Lq, Lk] probability tensor."""
+import gc
 import math
 
 import torch
@@ -112,6 +113,19 @@ class BeamTables(object):
         self.ids.zero_()
         self.anc.copy_(self._anc0)
 
+    def reset_sampling(self):
+        """The start of a SAMPLED decode (include/hero_hip.h "Sampled decoding"): the rows of a caption are independent samples,
+        so every row starts alive at cum = 0 and the ancestry stays the identity for the whole decode.  `kept` [rows] (the size of
+        every row's kept set at the last step) is made on first use and keeps its address."""
+        self.cum.zero_()
+        self.fin.zero_()
+        self.len.zero_()
+        self.ids.zero_()
+        self.anc.copy_(self._anc0)
+        if getattr(self, "kept", None) is None:
+            self.kept = torch.zeros_like(self.fin)
+        return self
+
 
 def beam_select_torch(scores, tb, t, eos):
     """hero_beam_select in PyTorch ops on a BeamTables of int64 indices: scores [rows, V] -> the parent ROW of every new beam
@@ -136,6 +150,67 @@ def beam_select_torch(scores, tb, t, eos):
     tb.ids[:, t] = v
     tb.anc[:, t] = rows
     return rows, v
+
+
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def _mul32(x, c):
+    """(x * c) mod 2^32 for an int64 tensor of 32-bit values, without leaving 63 bits."""
+    return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & 0xFFFFFFFF
+
+
+def gumbel_noise(seed, t, R, V, device):
+    """g [R, V] fp32 of hero_sample_select at position t: the hashes of hero_amd/csrc/common.h in int64 arithmetic,
+    u = (2h + 1) * 2^-24 exactly, g = -log(-log1p(-u)) in fp32."""
+    keys = [_splitmix64((int(seed) & _M64) ^ (((t * R + r) * 0xD6E8FEB86659FD93) & _M64)) & 0xFFFFFFFF for r in range(R)]
+    x = torch.arange(V, dtype=torch.long, device=device).unsqueeze(0) ^ torch.tensor(keys, dtype=torch.long, device=device).unsqueeze(1)
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    x = x ^ (x >> 16)
+    u = (2 * (x >> 9) + 1).to(torch.float32) * (2.0 ** -24)
+    return -torch.log(-torch.log1p(-u))
+
+
+def sample_select_torch(scores, tb, t, eos, seed, temperature, top_k, top_p):
+    """hero_sample_select in PyTorch ops on a BeamTables of int64 indices, updated in place: scores [rows, V] -> (the token of
+    every row [rows], the size of every row's kept set [rows]).  Ordering, noise and the perturbed scores are fp32 as in the
+    kernel - a stable descending sort gives the tie rule - and the nucleus masses are summed in float64; top_p counts as the
+    fp32 value the kernel receives."""
+    x = scores.float()
+    R, V = x.shape
+    dev = x.device
+    z = x * T.inv_temperature(temperature)
+    zs, order = torch.sort(z, dim=1, descending=True, stable=True)
+    K = min(int(top_k), V) if top_k > 0 else V
+    J = torch.full((R,), K, dtype=torch.long, device=dev)
+    p32 = float(torch.tensor(float(top_p), dtype=torch.float32))
+    if p32 < 1.0:
+        csum = torch.cumsum(torch.exp(zs[:, :K].double() - zs[:, :1].double()), dim=1)
+        J = ((csum < p32 * csum[:, -1:]).sum(dim=1) + 1).clamp(max=K)
+    col = torch.arange(V, device=dev).unsqueeze(0)
+    pert = zs + gumbel_noise(seed, t, R, V, dev).gather(1, order)
+    pert = torch.where(col < J.unsqueeze(1), pert, torch.full_like(pert, float("-inf")))
+    best = pert.max(dim=1, keepdim=True).values
+    v = torch.where(pert == best, order, torch.full_like(order, V)).min(dim=1).values          # among equals the lower token
+    live = tb.fin == 0
+    logp = x.gather(1, v.unsqueeze(1)).squeeze(1) - torch.logsumexp(x, dim=1)
+    tokens = torch.where(live, v, torch.full_like(v, eos))
+    tb.cum = torch.where(live, tb.cum + logp, tb.cum)
+    tb.len = tb.len + live.to(tb.len.dtype)
+    tb.fin = torch.where(live, (v == eos).to(tb.fin.dtype), tb.fin)
+    tb.ids[:, t] = tokens.to(tb.ids.dtype)
+    tb.kept = torch.where(live, J, torch.zeros_like(J))
+    return tokens, tb.kept
 
 
 class BertDecoderLayer(nn.Module):
@@ -513,17 +588,24 @@ class TvcGenerator(object):
     beam_decode(batch, beam_size) searches with beam_size beams per caption on the same incremental step (needs kv_cache; under
     use_graph the beam step is captured once per (N, beam, Lv, max_step) and shares MAX_GRAPHS and `counts` with the greedy
     graphs): the step runs N * beam rows, hero_beam_select takes the beam tables to the next step on the device, and neither
-    the key/value cache nor the encoder keys are copied or replicated."""
+    the key/value cache nor the encoder keys are copied or replicated.
+
+    sample_decode(batch, n_samples, temperature, top_k, top_p, seed) draws n_samples captions per clip on the same state (one
+    hero_sample_select per step; the ancestry table stays at the identity) and keeps the best by model likelihood.
+    stop_at_eos (beam_decode, sample_decode) ends a decode once every row has finished: after every `check_every` steps ONE
+    word is read from the device, outside the captured step.  counts["steps"] counts the decode steps actually run."""
 
     MAX_GRAPHS = 8
 
-    def __init__(self, model, max_step, bos, eos, kv_cache=False, use_graph=False):
+    def __init__(self, model, max_step, bos, eos, kv_cache=False, use_graph=False, check_every=4):
         if use_graph and not kv_cache:
             raise ValueError("TvcGenerator: use_graph replays the incremental decode step, it needs kv_cache=True")
+        if check_every < 1:
+            raise ValueError("TvcGenerator: check_every %d < 1" % check_every)
         self.model, self.max_step, self.bos, self.eos = model, max_step, bos, eos
-        self.kv_cache, self.use_graph = kv_cache, use_graph
+        self.kv_cache, self.use_graph, self.check_every = kv_cache, use_graph, int(check_every)
         self._graphs = {}          # (N, Lv, max_step, dtype, device, weight-copy generation) -> captured step and its buffers
-        self.counts = {"captures": 0, "replayed": 0}
+        self.counts = {"captures": 0, "replayed": 0, "steps": 0}     # steps: decode steps actually run, on every cached route
 
     def _step(self, state, last, output_ids):
         """One incremental step on device buffers only: `last` [N] in, the arg-max ids out - into `last` and into column
@@ -541,7 +623,23 @@ class TvcGenerator(object):
     def _weights_signature(self):
         return tuple(p._version for p in self.model.parameters()) + (HF.weight_epoch(),)
 
-    def _replay(self, kind, encoder_outputs, enc_mask, make):
+    def _all_finished(self, state):
+        """ONE word from the device: every row of the state's tables has emitted `eos`.  Outside any captured step."""
+        return int(state.tables.fin.min()) != 0
+
+    def _run_steps(self, state, step, stop_at_eos):
+        """step() up to max_step times; with stop_at_eos the finished flags are read after every `check_every` steps and the loop
+        ends once every row has finished - a finished row only re-emits `eos` at an unchanged score, so nothing is lost."""
+        done = 0
+        while done < self.max_step:
+            step()
+            done += 1
+            if stop_at_eos and done % self.check_every == 0 and done < self.max_step and self._all_finished(state):
+                break
+        self.counts["steps"] += done
+        return done
+
+    def _replay(self, kind, encoder_outputs, enc_mask, make, prepare=None, stop_at_eos=False):
         """The captured step of `kind` for this shape, refilled with the batch and replayed max_step times -> its entry.  On first
         use make() -> dict(state, last = the ids buffer the step embeds, step = one step on device buffers only, ...): the step runs
         once eagerly, so that every compute copy of a weight exists, and is then captured on one stream - a straight line."""
@@ -557,10 +655,22 @@ class TvcGenerator(object):
             hit["step"]()
             key = key[:-1] + (HF.weight_cache_generation(),)
             model.refill_decode_state(hit["state"], encoder_outputs, enc_mask)
+            if prepare is not None:
+                prepare(hit)
             torch.cuda.synchronize()
+            # An entry and its generator refer to each other (the step closes over `self`), so a generator that was dropped
+            # goes - with its graphs - only when the cycle collector runs.  Inside a capture that is an error (a graph and its
+            # memory pool cannot be released while a stream captures): collect now, and let no collection start in there.
+            gc.collect()
             hit["graph"] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(hit["graph"]):
-                hit["step"]()
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(hit["graph"]):
+                    hit["step"]()
+            finally:
+                if gc_was_on:
+                    gc.enable()
             if len(self._graphs) >= self.MAX_GRAPHS:
                 self._graphs.clear()
             hit["wsig"] = self._weights_signature()
@@ -571,10 +681,10 @@ class TvcGenerator(object):
             HF.refresh_weight_cache()
             hit["wsig"] = wsig
         model.refill_decode_state(hit["state"], encoder_outputs, enc_mask)
+        if prepare is not None:                                 # what the kind adds to a refilled state (sampling: its tables and seed)
+            prepare(hit)
         hit["last"].fill_(self.bos)
-        for _ in range(self.max_step):
-            hit["graph"].replay()
-        self.counts["replayed"] += self.max_step
+        self.counts["replayed"] += self._run_steps(hit["state"], hit["graph"].replay, stop_at_eos)
         return hit
 
     def _decode_graph(self, encoder_outputs, enc_mask):
@@ -596,6 +706,7 @@ class TvcGenerator(object):
         output_ids = torch.empty((N, self.max_step), dtype=torch.long, device=dev)
         for _ in range(self.max_step):
             self._step(state, last, output_ids)
+        self.counts["steps"] += self.max_step
         return output_ids
 
     @torch.no_grad()
@@ -649,20 +760,22 @@ class TvcGenerator(object):
         model.reorder_decode_state(state, rows)
         return nxt
 
-    def _beam_graph(self, encoder_outputs, enc_mask, beam_size):
+    def _beam_graph(self, encoder_outputs, enc_mask, beam_size, stop_at_eos=False):
         """The beam step captured once per (N, beam, Lv, max_step); it shares the graph table with the greedy steps."""
         def make():
             state, last = self._beam_state(encoder_outputs, enc_mask, beam_size)
             return dict(state=state, last=last, step=lambda: self._beam_step(state, last))
-        return self._replay(("beam", beam_size), encoder_outputs, enc_mask, make)["state"]
+        return self._replay(("beam", beam_size), encoder_outputs, enc_mask, make, stop_at_eos=stop_at_eos)["state"]
 
     @torch.no_grad()
-    def beam_decode(self, batch, beam_size, length_penalty=1.0, encoder_outputs=None, return_scores=False):
+    def beam_decode(self, batch, beam_size, length_penalty=1.0, encoder_outputs=None, return_scores=False, stop_at_eos=False):
         """Beam search over the incremental decode (needs kv_cache=True): max_step steps of decode_step + selection for
         N * beam_size rows, no early exit - a finished beam carries `eos` at an unchanged score - then per caption the beam with
         the largest  cum / max(len, 1) ** length_penalty  (the lower beam among equals), ONE host transfer, and the ids cut at
         `eos`.  On the kernels' route the selection is hero_beam_select and neither the cache nor the encoder keys are copied or
-        replicated; use_graph replays the captured step.  -> list of id lists[, list of the picked beams' scores]."""
+        replicated; use_graph replays the captured step.  stop_at_eos: leave the loop once every beam of every caption has finished
+        (one word read from the device after every `check_every` steps, outside the captured step); the result is that of the
+        full-length run.  -> list of id lists[, list of the picked beams' scores]."""
         if not self.kv_cache:
             raise ValueError("TvcGenerator: beam_decode runs on the incremental decode step, it needs kv_cache=True")
         if beam_size < 1:
@@ -672,16 +785,99 @@ class TvcGenerator(object):
             encoder_outputs = model.encode(batch)
         enc_mask = batch["cap_attn_mask"]
         if self.use_graph:
-            state = self._beam_graph(encoder_outputs, enc_mask, beam_size)
+            state = self._beam_graph(encoder_outputs, enc_mask, beam_size, stop_at_eos)
         else:
             state, last = self._beam_state(encoder_outputs, enc_mask, beam_size)
-            for _ in range(self.max_step):
-                last = self._beam_step(state, last)
+            cur = [last]
+            self._run_steps(state, lambda: cur.__setitem__(0, self._beam_step(state, cur[0])), stop_at_eos)
         tb, N, B = state.tables, state.N, beam_size
         norm = tb.cum.view(N, B) / tb.len.view(N, B).clamp(min=1).to(torch.float32) ** float(length_penalty)
         best = torch.sort(norm, dim=1, descending=True, stable=True).indices[:, :1]            # stable: the lower beam wins a tie
         rows = torch.arange(N, device=best.device) * B + best[:, 0]
         packed = torch.cat([tb.ids[rows].to(torch.int32), norm.gather(1, best).contiguous().view(torch.int32)], dim=1).cpu()
+        ids = [self.cut_eos(r) for r in packed[:, :-1].tolist()]
+        if return_scores:
+            return ids, packed[:, -1:].contiguous().view(torch.float32).view(-1).tolist()
+        return ids
+
+    # ---- sampling -----------------------------------------------------------------------------------------------------------
+    def _sample_step(self, state, last, seed, params):
+        """One sampling step on device buffers only: decode_step over all rows, then the draw.  Fused: hero_sample_select updates
+        the tables in place and leaves the next ids in the state's `wid` (`seed` is a device word); PyTorch route: the same
+        algorithm in ops (`seed` is an int).  -> the next ids."""
+        tb = state.tables
+        temperature, top_k, top_p = params
+        scores = self.model.decode_step(state, last)
+        if state.fused:
+            T.k_sample_select(scores, tb.cum, tb.fin, tb.len, tb.ids, state.wid, tb.kept, seed, state.pos, state.N, state.beam,
+                              scores.shape[1], self.eos, temperature, top_k, top_p, pos_offset=-1)
+            return state.wid
+        return sample_select_torch(scores, tb, state.t - 1, self.eos, seed, temperature, top_k, top_p)[0]
+
+    @staticmethod
+    def _seed_word(seed):
+        s = int(seed) & _M64
+        return s - (1 << 64) if s >= (1 << 63) else s              # the same 64 bits in an int64
+
+    def _sample_graph(self, encoder_outputs, enc_mask, n_samples, seed, params, stop_at_eos):
+        """The sampling step captured once per (N, samples, Lv, max_step, temperature, top_k, top_p) - the three are launch scalars
+        of the captured kernel; the seed is a device word filled before the replays."""
+        def make():
+            state, last = self._beam_state(encoder_outputs, enc_mask, n_samples)
+            state.tables.reset_sampling()
+            word = torch.zeros((1,), dtype=torch.long, device=encoder_outputs.device)
+            return dict(state=state, last=last, seed=word, step=lambda: self._sample_step(state, last, word, params))
+
+        def prepare(hit):
+            hit["state"].tables.reset_sampling()
+            hit["seed"].fill_(self._seed_word(seed))
+        return self._replay(("sample", n_samples) + params, encoder_outputs, enc_mask, make, prepare, stop_at_eos)["state"]
+
+    @torch.no_grad()
+    def sample_decode(self, batch, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=1.0,
+                      return_all=False, return_scores=False, stop_at_eos=False, encoder_outputs=None):
+        """Sampled decoding over the incremental decode (needs kv_cache=True): n_samples independent captions per clip, drawn token
+        by token from the step's scores under temperature, then top-k (0 = off), then top-p (>= 1 = off); the draw is a
+        counter-based Gumbel-max, a function of (seed, position, row, token) alone.  The state is the beam state: N * n_samples
+        rows over the caption's own N blocks of encoder keys, the ancestry table left at the identity, no cache copied.  cum is
+        the model's own log-likelihood of the drawn tokens (temperature 1, no filter).  -> per caption the sample with the
+        largest  cum / max(len, 1) ** length_penalty  (the lower sample among equals), or with return_all all N * n_samples
+        captions in row order (caption-major); ONE host transfer, ids cut at `eos`[, the scores of the returned captions].
+        On the kernels' route (n_samples within the beam envelope) the draw is hero_sample_select; use_graph replays the captured
+        step and a new seed does not recapture.  stop_at_eos as in beam_decode.  top_k = 1 is greedy decoding."""
+        if not self.kv_cache:
+            raise ValueError("TvcGenerator: sample_decode runs on the incremental decode step, it needs kv_cache=True")
+        if n_samples < 1:
+            raise ValueError("TvcGenerator: n_samples %d < 1" % n_samples)
+        if not temperature > 0 or not math.isfinite(temperature):
+            raise ValueError("TvcGenerator: temperature %r must be finite and > 0" % (temperature,))
+        if top_k < 0:
+            raise ValueError("TvcGenerator: top_k %r < 0" % (top_k,))
+        if not top_p > 0:
+            raise ValueError("TvcGenerator: top_p %r must be > 0" % (top_p,))
+        params = (float(temperature), int(top_k), float(top_p))
+        model = self.model
+        if encoder_outputs is None:
+            encoder_outputs = model.encode(batch)
+        enc_mask = batch["cap_attn_mask"]
+        if self.use_graph:
+            state = self._sample_graph(encoder_outputs, enc_mask, n_samples, seed, params, stop_at_eos)
+        else:
+            state, last = self._beam_state(encoder_outputs, enc_mask, n_samples)
+            state.tables.reset_sampling()
+            word = seed
+            if state.fused:
+                word = torch.full((1,), self._seed_word(seed), dtype=torch.long, device=encoder_outputs.device)
+            cur = [last]
+            self._run_steps(state, lambda: cur.__setitem__(0, self._sample_step(state, cur[0], word, params)), stop_at_eos)
+        tb, N, S = state.tables, state.N, n_samples
+        norm = tb.cum.view(N, S) / tb.len.view(N, S).clamp(min=1).to(torch.float32) ** float(length_penalty)
+        if return_all:
+            rows, picked = torch.arange(N * S, device=norm.device), norm.reshape(-1, 1)
+        else:
+            best = torch.sort(norm, dim=1, descending=True, stable=True).indices[:, :1]        # stable: the lower sample wins a tie
+            rows, picked = torch.arange(N, device=best.device) * S + best[:, 0], norm.gather(1, best)
+        packed = torch.cat([tb.ids[rows].to(torch.int32), picked.contiguous().view(torch.int32)], dim=1).cpu()
         ids = [self.cut_eos(r) for r in packed[:, :-1].tolist()]
         if return_scores:
             return ids, packed[:, -1:].contiguous().view(torch.float32).view(-1).tolist()

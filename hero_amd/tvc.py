@@ -10,6 +10,8 @@ inference-only kernels of its incremental and beam-search decode.
                       over the encoder keys, and causal self-attention against a key/value cache that the kernel extends;
                       `group=` / `anc=` are their beam-search forms (shared encoder keys, a cache read through an ancestry table)
     k_beam_select     the selection step of beam search over [N * B, vocab] scores (hero_beam_select), in place on device tables
+    k_sample_select   the sampling step (temperature, top-k, top-p, Gumbel-max draw) over [N * S, vocab] scores
+                      (hero_sample_select), in place on the same tables
 
 There is no PyTorch route in here: outside the kernels' envelope the nodes raise."""
 import ctypes as C
@@ -207,6 +209,56 @@ def k_beam_select(logits, cum, fin, length, ids, anc, last, workspace, pos, N, B
     # the scores may be the first V columns of a wider buffer (the padded vocabulary): rows ld apart, not contiguous
     L.check(L.lib().hero_beam_select(logits.data_ptr(), L.ptr(cum), L.ptr(fin), L.ptr(length), L.ptr(ids), L.ptr(anc), L.ptr(last),
                                      L.ptr(workspace), pos_dev, pos_host, N, B, V, ld, Tcap, eos, L.dt(logits), L.stream()))
+
+
+def in_envelope_sample(dtype, V, Tcap):
+    """The library's own answer (hero_sample_in_envelope): fp32 / bf16, 1 <= V <= 65536, 1 <= Tcap <= 128."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return bool(L.lib().hero_sample_in_envelope(L.F32 if dtype == torch.float32 else L.BF16, int(V), int(Tcap)))
+
+
+def inv_temperature(temperature):
+    """The fp32 multiplier 1 / temperature that both routes of the sampling step apply to the logits."""
+    return float(torch.tensor(1.0 / float(temperature), dtype=torch.float32))
+
+
+def k_sample_select(logits, cum, fin, length, ids, last, kept, seed, pos, N, S, V, eos, temperature, top_k, top_p, pos_offset=0):
+    """One sampling step for N captions x S samples (row r = n*S + s), in place and on the device (include/hero_hip.h "Sampled
+    decoding"): logits [R, ld >= V] fp32 / bf16; cum [R] fp32; fin, length, last [R] and ids [R, Tcap] int32; kept [R] int32 or
+    None (the size of every row's kept set); seed: a 1-element int64 device tensor whose 64 bits are the seed word.  pos: the
+    step's position as an int, or a 1-element int32 device tensor to which `pos_offset` is added.  temperature > 0, top_k >= 0
+    (0 = off), top_p > 0 (>= 1 = off)."""
+    R = N * S
+    if logits.dim() != 2 or logits.shape[0] != R or logits.stride(1) != 1:
+        raise ValueError("sampling: the scores must be [%d, >= V] with unit column stride, got %s" % (R, tuple(logits.shape)))
+    ld, Tcap, dev = logits.stride(0), ids.shape[1] if ids.dim() == 2 else 0, logits.device
+    if not temperature > 0 or not math.isfinite(temperature) or top_k < 0 or not top_p > 0:
+        raise ValueError("sampling: temperature %r, top_k %r, top_p %r: temperature must be finite and > 0, top_k >= 0, top_p > 0"
+                         % (temperature, top_k, top_p))
+    if not in_envelope_sample(logits.dtype, V, Tcap) or N < 1 or S < 1 or ld < V or logits.shape[1] < V or not 0 <= eos < V:
+        raise ValueError("sampling: %s, N=%d, S=%d, V=%d, ld=%d, Tcap=%d, eos=%d is outside the sampling kernel's envelope (fp32 / "
+                         "bf16, N, S >= 1, 1 <= V <= %d, 1 <= Tcap <= %d, ld >= V, 0 <= eos < V)"
+                         % (logits.dtype, N, S, V, ld, Tcap, eos, MAX_BEAM_V, MAX_LK))
+    _beam_table("cum", cum, (R,), torch.float32, dev)
+    for name, t in (("fin", fin), ("len", length), ("last", last)) + ((("kept", kept),) if kept is not None else ()):
+        _beam_table(name, t, (R,), torch.int32, dev)
+    _beam_table("ids", ids, (R, Tcap), torch.int32, dev)
+    if not torch.is_tensor(seed) or seed.numel() != 1 or seed.dtype != torch.int64 or seed.device != dev:
+        raise ValueError("sampling: the seed must be one int64 on %s" % (dev,))
+    if torch.is_tensor(pos):
+        if pos.numel() != 1 or pos.dtype != torch.int32 or pos.device != dev:
+            raise ValueError("sampling: a device position must be one int32 on %s, got %s %s on %s"
+                             % (dev, tuple(pos.shape), pos.dtype, pos.device))
+        pos_dev, pos_host = L.ptr(pos), int(pos_offset)
+    else:
+        pos_dev, pos_host = None, int(pos) + int(pos_offset)
+        if not 0 <= pos_host < Tcap:
+            raise ValueError("sampling: position %d outside [0, Tcap = %d)" % (pos_host, Tcap))
+    # the scores may be the first V columns of a wider buffer (the padded vocabulary): rows ld apart, not contiguous
+    L.check(L.lib().hero_sample_select(logits.data_ptr(), L.ptr(cum), L.ptr(fin), L.ptr(length), L.ptr(ids), L.ptr(last), L.ptr(kept),
+                                       L.ptr(seed), pos_dev, pos_host, N, S, V, ld, Tcap, eos, inv_temperature(temperature),
+                                       int(top_k), float(top_p), L.dt(logits), L.stream()))
 
 
 class DecAttnCoreFn(torch.autograd.Function):

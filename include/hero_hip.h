@@ -53,6 +53,8 @@ const char* hero_last_error(void);
  * Still 3: hero_beam_select and hero_beam_in_envelope (the selection step of beam-search captioning), and
  * hero_dec_attention_row_grouped and hero_dec_attention_step_beam (the one-row attentions of a beam: shared encoder keys, a
  * cache read through an ancestry table) were ADDED the same way.
+ * Still 3: hero_sample_select and hero_sample_in_envelope (the sampling step of the captioning decode: temperature, top-k,
+ * top-p, a Gumbel-max draw) were ADDED the same way.
  * INTEGRATION.md section 2 lists the breaks per version. */
 #define HERO_ABI_VERSION 3
 int hero_abi_version(void);
@@ -417,6 +419,44 @@ int hero_beam_in_envelope(int dtype, int V, int B, int Tcap);
 int hero_beam_select(const void* logits, float* cum, int32_t* fin, int32_t* len, int32_t* ids, int32_t* anc, int32_t* last,
                      void* workspace, const int* pos_dev, int pos, int N, int B, int V, int ld, int Tcap, int eos, int dtype,
                      hero_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Sampled decoding (captioning decode; inference only)                                         */
+/* ------------------------------------------------------------------------------------------ */
+/* One call per decode step draws the next token of R = N captions x S samples (row r = n*S + s) */
+/* and updates the rows' tables - the buffers of the beam search, without anc: a row never changes */
+/* its parent.  logits [R, ld] fp32 / bf16; all arithmetic in fp32.  With t the step's position:   */
+/*   finished row (fin[r] != 0)  token = eos; cum, len unchanged; ids[r, t] = last[r] = eos;        */
+/*       kept[r] = 0.                                                                              */
+/*   live row                                                                                      */
+/*     order   z_v = float(logit_v) * inv_temperature, one rounding.  Candidates are ordered by    */
+/*             (order_bits(z_v) << 32) | ~v: larger z first, among equal z the lower token.          */
+/*     top-k   keep the first min(top_k, V) candidates in that order; 0 = off.                      */
+/*     top-p   masses exp(z_v - max z) over the survivors of top-k; keep the shortest prefix, in     */
+/*             the same order, whose mass is >= top_p times the mass of all survivors, at least one   */
+/*             candidate; top_p >= 1 = off.                                                          */
+/*     draw    Gumbel-max: the kept v that maximises z_v + g_v, ties by the same composite on the     */
+/*             perturbed score, where                                                                */
+/*               base = splitmix64(seed ^ (site * 0xD6E8FEB86659FD93)), site = (uint64)t * R + r      */
+/*               h = mix32((uint32)v ^ (uint32)base) >> 9,  u = (2h + 1) * 2^-24,                      */
+/*               g = -logf(-log1pf(-u))                                                              */
+/*     update  cum[r] += logit_v - lse_r, lse_r the log-sum-exp of the RAW row (temperature 1, no     */
+/*             filter: the model's likelihood of the token); len[r] += 1; fin[r] = (v == eos);        */
+/*             ids[r, t] = last[r] = v; kept[r] = the size of the kept set.                           */
+/* cum [R] fp32; fin, len, last [R] and ids [R, Tcap] int32, updated IN PLACE; kept [R] int32 may be  */
+/* NULL; columns other than t of ids are left alone.  seed_dev is ONE device uint64, read by the      */
+/* kernel (a captured launch serves every seed).  t = pos_dev ? *pos_dev + pos : pos, as in           */
+/* hero_beam_select; a device t outside [0, Tcap) changes nothing.                                   */
+/* The masses of top-p are added as 64-bit integers in units of 2^-40 (LDS integer atomics): a sum    */
+/* does not depend on the order of its terms, there are no floating-point atomics, two runs give the  */
+/* same bits.  One launch; nothing is allocated or read on the host.                                 */
+/* Envelope: fp32 / bf16, N, S >= 1, 1 <= V <= 65536, top_k >= 0, top_p > 0, inv_temperature finite   */
+/* and > 0, 1 <= Tcap <= 128, ld >= V, 0 <= eos < V, a host position in [0, Tcap).  Outside it        */
+/* HERO_ERR_ARG, no launch.  Plain arguments: a backward-compatible addition, HERO_ABI_VERSION stays. */
+int hero_sample_in_envelope(int dtype, int V, int Tcap);
+int hero_sample_select(const void* logits, float* cum, int32_t* fin, int32_t* len, int32_t* ids, int32_t* last, int32_t* kept,
+                       const unsigned long long* seed_dev, const int* pos_dev, int pos, int N, int S, int V, int ld, int Tcap,
+                       int eos, float inv_temperature, int top_k, float top_p, int dtype, hero_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Row gathers / scatters                                                                      */

@@ -28,7 +28,17 @@ tool measures untimed under teacher forcing on random ids.  Prints one JSON line
                             index_select indices that were never written.  Graph replay is "not available" for this side.
 (eos = 2 here: the selection needs a real id; with random weights it is rarely chosen).  What is timed is again one whole
 decode on given encoder outputs.  The sides' ids are compared; with random weights equal ids are not expected between the
-fused and the PyTorch side (near ties, see above), between the fused side and its own graph replay they are."""
+fused and the PyTorch side (near ties, see above), between the fused side and its own graph replay they are.
+
+`--sample S [--top-k K --top-p P --temperature T]` measures sampled decoding instead, four sides alternating -
+    greedy_cached           the cached greedy decode above, for scale
+    sample_fused[_graph]    TvcGenerator.sample_decode on the kernels' route: N * S rows on the beam state, one hero_sample_select
+                            per step, the seed a device word
+    sample_torch            the same draw in PyTorch ops (hero_amd.model.tvc.sample_select_torch: sort of the whole vocabulary,
+                            cumulative sum, hash and arg-max as tensor ops, the per-row hash keys made on the host) around the
+                            SAME cached step and the same shared encoder keys.  Eager only: its keys are host values.
+Every run draws with a new seed, the same on all sampling sides.  The fused sides must agree with each other on every run; the
+fused and the PyTorch side draw the same tokens wherever fp32 decides them, which the line reports as a share of captions."""
 import argparse
 import json
 import os
@@ -110,6 +120,82 @@ class TorchBeam(object):
         return self.ids[rows].tolist()
 
 
+class TorchSample(object):
+    """Sampled decoding written around the cached decode step with hero_amd.model.tvc.sample_select_torch in place of
+    hero_sample_select: the same N * S-row state over N blocks of encoder keys, int64 tables, the pick of
+    TvcGenerator.sample_decode."""
+
+    def __init__(self, model, max_step, S, bos, eos, params):
+        self.model, self.max_step, self.S, self.bos, self.eos, self.params = model, max_step, S, bos, eos, params
+        self.state = None
+
+    @torch.no_grad()
+    def decode(self, batch, enc, seed, length_penalty=1.0):
+        from hero_amd.model.tvc import BeamTables, sample_select_torch
+        mask, S = batch["cap_attn_mask"], self.S
+        N = enc.shape[0]
+        if self.state is None:
+            self.state = self.model.init_decode_state(enc, mask, self.max_step, S, beam_tables=True)
+            self.tb = BeamTables(N, S, self.max_step, enc.device, False)
+        self.model.refill_decode_state(self.state, enc, mask)
+        tb = self.tb.reset_sampling()
+        last = torch.full((N * S,), self.bos, dtype=torch.long, device=enc.device)
+        for t in range(self.max_step):
+            last, _ = sample_select_torch(self.model.decode_step(self.state, last), tb, t, self.eos, seed, *self.params)
+        norm = tb.cum.view(N, S) / tb.len.view(N, S).clamp(min=1).float() ** length_penalty
+        best = torch.sort(norm, dim=1, descending=True, stable=True).indices[:, 0]
+        return tb.ids[torch.arange(N, device=enc.device) * S + best].tolist()
+
+
+def main_sample(a, model, batch, enc, N, Lv, max_step):
+    from hero_amd.model import TvcGenerator
+    S, bos, eos = a.sample, 0, 2
+    params = (a.temperature, a.top_k, a.top_p)
+    greedy = TvcGenerator(model, max_step, bos, eos, kv_cache=True)
+    fused = {"sample_fused": TvcGenerator(model, max_step, bos, eos, kv_cache=True),
+             "sample_fused_graph": TvcGenerator(model, max_step, bos, eos, kv_cache=True, use_graph=True)}
+    plain = TorchSample(model, max_step, S, bos, eos, params)
+    run = {"greedy_cached": lambda seed: greedy.greedy_decode(batch, encoder_outputs=enc)}
+    run.update({k: (lambda seed, g=g: g.sample_decode(batch, S, *params, seed=seed, encoder_outputs=enc)) for k, g in fused.items()})
+    run["sample_torch"] = lambda seed: [greedy.cut_eos(r) for r in plain.decode(batch, enc, seed)]
+
+    def timed(fn, seed):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ids = fn(seed)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3, ids
+
+    for i in range(3):
+        for fn in run.values():
+            timed(fn, 1000 + i)
+    times = {k: [] for k in run}
+    same = {"sample_fused_graph_vs_sample_fused": 0, "sample_fused_vs_sample_torch": 0}
+    cap_same = []
+    for i in range(a.runs):
+        got = {}
+        for k, fn in run.items():
+            us, got[k] = timed(fn, i)
+            times[k].append(us)
+        same["sample_fused_graph_vs_sample_fused"] += int(got["sample_fused_graph"] == got["sample_fused"])
+        same["sample_fused_vs_sample_torch"] += int(got["sample_fused"] == got["sample_torch"])
+        cap_same.append(sum(x == y for x, y in zip(got["sample_fused"], got["sample_torch"])) / float(N))
+    out = {"bench": "tvc_sample_ab", "shape_N_Lv_maxstep": [N, Lv, max_step], "samples": S, "temperature": a.temperature,
+           "top_k": a.top_k, "top_p": a.top_p, "model": "HERO-base decoder, 2 layers, vocab 50272", "dtype": "bf16",
+           "mode": "eval, no early exit, length_penalty 1, a new seed every run",
+           "what": "one whole decode on given encoder outputs: state set-up + max_step steps + pick + id transfer",
+           "timer": "HIP events, one pair per decode, sides alternating", "runs": a.runs,
+           "sample_torch_graph": "not available: the hash keys of sample_select_torch are host values"}
+    for k, v in times.items():
+        out[k + "_us_median"], out[k + "_us_min"] = round(statistics.median(v), 1), round(min(v), 1)
+    out.update({"sample_torch_over_sample_fused": round(statistics.median(times["sample_torch"]) / statistics.median(times["sample_fused"]), 2),
+                "runs_with_equal_ids": same, "captions_equal_fused_vs_torch": round(statistics.median(cap_same), 4),
+                "graphs_captured": {k: g.counts["captures"] for k, g in fused.items()},
+                "device": torch.cuda.get_device_name(0)})
+    return json.dumps(out)
+
+
 def main_beam(a, model, batch, enc, N, Lv, max_step):
     from hero_amd.model import TvcGenerator
     B, bos, eos = a.beam, 0, 2
@@ -164,6 +250,10 @@ def main():
     ap.add_argument("--shape", default="40,20,30", help="captions, Lv, max_step")
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--beam", type=int, default=0, help="beam size: measure beam search (fused, PyTorch formulation) beside the cached greedy decode")
+    ap.add_argument("--sample", type=int, default=0, help="samples per caption: measure sampled decoding (fused, PyTorch formulation) beside the cached greedy decode")
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--out")
     a = ap.parse_args()
     import hero_amd
@@ -183,8 +273,8 @@ def main():
     lens_v = torch.randint(1, Lv + 1, (N,), generator=g)
     lens_v[0] = Lv
     batch = {"cap_attn_mask": (torch.arange(Lv).unsqueeze(0) < lens_v.unsqueeze(1)).long().cuda()}
-    if a.beam:
-        line = main_beam(a, model, batch, enc, N, Lv, max_step)
+    if a.beam or a.sample:
+        line = (main_sample if a.sample else main_beam)(a, model, batch, enc, N, Lv, max_step)
         print(line)
         if a.out:
             with open(a.out, "w") as f:
