@@ -32,7 +32,7 @@ def _stale(target, deps):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_args.h"), os.path.join(CSRC, "gemm_route.h"), os.path.join(CSRC, "gemm_ws_common.h"), os.path.join(CSRC, "attn_mfma.h"),
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_args.h"), os.path.join(CSRC, "gemm_route.h"), os.path.join(CSRC, "gemm_ws_common.h"), os.path.join(CSRC, "attn_mfma.h"), os.path.join(CSRC, "select_rows.h"),
                os.path.join(os.path.dirname(HERE), "include", "hero_hip.h")]
     jobs = []
     objs = []

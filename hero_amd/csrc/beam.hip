@@ -22,7 +22,7 @@
 //                      update is safe for any parent assignment, cycles included.
 // No floating-point atomics, no atomics at all: two runs give the same bits.  The launches allocate nothing and read nothing
 // on the host; the step position comes from a device int32 (a captured launch serves every step) or from the host.
-#include "common.h"
+#include "select_rows.h"
 
 namespace hero {
 namespace {
@@ -38,35 +38,6 @@ struct BeamSel {
   int pos, N, B, V, ld, Tcap, eos, vec;
 };
 
-__device__ __forceinline__ unsigned long long compose(float score, int flat) {
-  return ((unsigned long long)order_bits(score) << 32) | (uint32_t)~(uint32_t)flat;
-}
-
-// f(v, x) for the elements of the row that belong to this thread: 4 consecutive ones per load where the row allows it
-template <typename T, class F>
-__device__ __forceinline__ void for_row(const T* row, int V, bool vec, F f) {
-  if (vec) {
-    const int V4n = V >> 2;
-    for (int g = threadIdx.x; g < V4n; g += BM_NT) {
-      const float4 x = V4<T>::ld(row + 4 * g);
-      f(4 * g, x.x); f(4 * g + 1, x.y); f(4 * g + 2, x.z); f(4 * g + 3, x.w);
-    }
-    const int v = (V4n << 2) + threadIdx.x;
-    if (v < V) f(v, ld1<T>(row + v));
-  } else {
-    for (int v = threadIdx.x; v < V; v += BM_NT) f(v, ld1<T>(row + v));
-  }
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long c) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long x = __shfl_xor(c, o, 64);
-    c = x > c ? x : c;
-  }
-  return c;
-}
-
 template <typename T>
 __global__ __launch_bounds__(BM_NT) void beam_rows_kernel(BeamSel a) {
   __shared__ float red_m[BM_WAVES], red_s[BM_WAVES];
@@ -75,38 +46,19 @@ __global__ __launch_bounds__(BM_NT) void beam_rows_kernel(BeamSel a) {
   unsigned long long* out = a.cand + (size_t)r * a.B;
   const float cum = a.cum[r];
   if (a.fin[r] != 0) {                                              // uniform over the workgroup
-    if (tid < a.B) out[tid] = tid == 0 ? compose(cum, b * a.V + a.eos) : 0ull;
+    if (tid < a.B) out[tid] = tid == 0 ? compose(order_bits(cum), (uint32_t)(b * a.V + a.eos)) : 0ull;
     return;
   }
   const T* row = static_cast<const T*>(a.logits) + (size_t)r * a.ld;
   const bool vec = a.vec != 0;
-  float m = -3.0e38f, s = 0.f;
-  for_row<T>(row, a.V, vec, [&](int, float x) {
-    if (x > m) {
-      s = s * expf(m - x) + 1.f;
-      m = x;
-    } else {
-      s += expf(x - m);
-    }
-  });
-  const float wm = wave_max(m);
-  const float ws = wave_sum(s * expf(m - wm));
-  if (lane == 0) { red_m[wave] = wm; red_s[wave] = ws; }
-  __syncthreads();
-  float bm = red_m[0];
-#pragma unroll
-  for (int w = 1; w < BM_WAVES; ++w) bm = fmaxf(bm, red_m[w]);
-  float bs = 0.f;
-#pragma unroll
-  for (int w = 0; w < BM_WAVES; ++w) bs += red_s[w] * expf(red_m[w] - bm);
-  const float lse = bm + logf(bs);
+  const float lse = row_lse<T, BM_NT>(row, a.V, vec, red_m, red_s).lse;
 
   unsigned long long top[BM_MAX_B];
 #pragma unroll
   for (int k = 0; k < BM_MAX_B; ++k) top[k] = 0ull;
   const int flat0 = b * a.V;
-  for_row<T>(row, a.V, vec, [&](int v, float x) {
-    const unsigned long long c = compose(cum + (x - lse), flat0 + v);
+  for_row<T, BM_NT>(row, a.V, vec, [&](int v, float x) {
+    const unsigned long long c = compose(order_bits(cum + (x - lse)), (uint32_t)(flat0 + v));
     if (c > top[BM_MAX_B - 1]) {
       top[BM_MAX_B - 1] = c;
 #pragma unroll
@@ -138,7 +90,7 @@ __global__ __launch_bounds__(BM_NT) void beam_merge_kernel(BeamSel a) {
   __shared__ int par[BM_MAX_B], tok[BM_MAX_B], o_fin[BM_MAX_B], o_len[BM_MAX_B];
   __shared__ float sc[BM_MAX_B];
   __shared__ int o_ids[BM_MAX_B * BM_MAX_T], o_anc[BM_MAX_B * BM_MAX_T];
-  const int t = a.pos_dev ? *a.pos_dev + a.pos : a.pos;
+  const int t = step_position(a.pos_dev, a.pos);
   if (t < 0 || t >= a.Tcap) return;                                 // uniform over the grid: a device position cannot be refused on the host
   const int tid = threadIdx.x, B = a.B, Tcap = a.Tcap, row0 = blockIdx.x * B, nc = B * B;
   if (tid < nc) cs[tid] = a.cand[(size_t)row0 * B + tid];
@@ -206,10 +158,8 @@ extern "C" int hero_beam_select(const void* logits, float* cum, int* fin, int* l
   HERO_REQUIRE(logits && cum && fin && len && ids && anc && last && workspace, "hero_beam_select: null pointer");
   HERO_REQUIRE(pos_dev || (pos >= 0 && pos < Tcap), "hero_beam_select: position %d outside [0, Tcap = %d)", pos, Tcap);
   HERO_REQUIRE((((uintptr_t)workspace) & 7) == 0, "hero_beam_select: the workspace must be 8-byte aligned");
-  const size_t es = dtype == HERO_F32 ? 4 : 2;
-  const int vec = (ld % 4 == 0 && (((uintptr_t)logits) & (4 * es - 1)) == 0) ? 1 : 0;   // every row starts on a 4-element boundary
   const BeamSel a = {logits, pos_dev, cum, fin, len, ids, anc, last, static_cast<unsigned long long*>(workspace),
-                     pos, N, B, V, ld, Tcap, eos, vec};
+                     pos, N, B, V, ld, Tcap, eos, rows_vec4(logits, ld, dtype)};
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dtype == HERO_F32) hipLaunchKernelGGL((beam_rows_kernel<float>), dim3(N * B), dim3(BM_NT), 0, st, a);
   else hipLaunchKernelGGL((beam_rows_kernel<bf16_t>), dim3(N * B), dim3(BM_NT), 0, st, a);

@@ -139,13 +139,14 @@ template <int LPK> __device__ __forceinline__ float group_sum(float v) {
 }
 
 // fp32 -> 32 bits that order as unsigned integers like the floats do (-0 is folded into +0 first: equal scores must tie), and
-// back.  (order_bits(score) << 32) | ~index is the selection composite of retrieval.hip and beam.hip: unique per candidate,
-// larger = better score and, among equal scores, the lower index.
+// back.  compose(order_bits(score), index) is the selection composite of retrieval.hip, beam.hip and sample.hip: unique per
+// candidate, larger = better score and, among equal scores, the lower index.
 __device__ __forceinline__ uint32_t order_bits(float s) {
   const uint32_t b = __float_as_uint(s + 0.f);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ __forceinline__ float order_float(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+__device__ __forceinline__ unsigned long long compose(uint32_t key, uint32_t index) { return ((unsigned long long)key << 32) | (uint32_t)~index; }
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float gelu_erf_grad(float x) {

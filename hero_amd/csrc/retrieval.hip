@@ -71,7 +71,7 @@ __device__ void select_top(const Src& src, int top, SelShared& sh, float alpha, 
     for (int i = tid; i < SEL_BINS; i += NT) sh.hist[i] = 0u;
     __syncthreads();
     src.for_each([&](uint32_t key, uint32_t id) {
-      const unsigned long long comp = ((unsigned long long)key << 32) | (uint32_t)~id;
+      const unsigned long long comp = compose(key, id);
       if ((comp & pmask) == prefix) atomicAdd(&sh.hist[(int)((comp >> shift) & dmask)], 1u);
     });
     __syncthreads();
@@ -103,7 +103,7 @@ __device__ void select_top(const Src& src, int top, SelShared& sh, float alpha, 
   if (tid == 0) sh.count = 0;
   __syncthreads();
   src.for_each([&](uint32_t key, uint32_t id) {
-    const unsigned long long comp = ((unsigned long long)key << 32) | (uint32_t)~id;
+    const unsigned long long comp = compose(key, id);
     if ((comp & pmask) >= prefix) {
       const int pos = atomicAdd(&sh.count, 1);
       if (pos < SEL_CAP) sh.buf[pos] = comp;

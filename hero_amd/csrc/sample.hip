@@ -30,7 +30,7 @@
 // LDS integer atomics only, no floating-point atomics: two runs give the same bits.  The launch allocates nothing and reads
 // nothing on the host; the seed is a device word and the step position a device int32 (a captured launch serves every seed and
 // every step) or a host value.
-#include "common.h"
+#include "select_rows.h"
 
 namespace hero {
 namespace {
@@ -68,22 +68,6 @@ struct Found {
   uint32_t key, cnt_above, cnt_eq;
   u64 mass_above, mass_eq, target;
 };
-
-// f(v, x) for the elements of the row that belong to this thread: 4 consecutive ones per load where the row allows it
-template <typename T, class F>
-__device__ __forceinline__ void for_row(const T* row, int V, bool vec, F f) {
-  if (vec) {
-    const int V4n = V >> 2;
-    for (int g = threadIdx.x; g < V4n; g += SM_NT) {
-      const float4 x = V4<T>::ld(row + 4 * g);
-      f(4 * g, x.x); f(4 * g + 1, x.y); f(4 * g + 2, x.z); f(4 * g + 3, x.w);
-    }
-    const int v = (V4n << 2) + threadIdx.x;
-    if (v < V) f(v, ld1<T>(row + v));
-  } else {
-    for (int v = threadIdx.x; v < V; v += SM_NT) f(v, ld1<T>(row + v));
-  }
-}
 
 __device__ __forceinline__ int bin0(float z, float zmax) {
   const float d = fminf(fmaxf((zmax - z) * SM_BIN_SCALE, 0.f), (float)(SM_BINS - 1));   // NaN -> 0
@@ -130,7 +114,7 @@ __device__ Found descend(const SampleSel& a, const T* row, float zmax, SampleLds
       atomicAdd(&sh.cnt[digit], c);
       if (MODE != SEL_INDEX && with_mass) atomicAdd(&sh.mass[digit], m_known ? m_given : mass_of(z, zmax));
     };
-    for_row<T>(row, a.V, vec, [&](int v, float x) {
+    for_row<T, SM_NT>(row, a.V, vec, [&](int v, float x) {
       const float z = x * a.inv_t;
       const uint32_t key = order_bits(z);
       if (MODE == SEL_COUNT) {
@@ -191,7 +175,7 @@ __device__ Found descend(const SampleSel& a, const T* row, float zmax, SampleLds
 template <typename T>
 __global__ __launch_bounds__(SM_NT) void sample_rows_kernel(SampleSel a) {
   __shared__ SampleLds sh;
-  const int t = a.pos_dev ? *a.pos_dev + a.pos : a.pos;
+  const int t = step_position(a.pos_dev, a.pos);
   if (t < 0 || t >= a.Tcap) return;                                 // uniform over the grid: a device position cannot be refused on the host
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = a.V;
   if (a.fin[r] != 0) {                                              // uniform over the workgroup
@@ -204,27 +188,9 @@ __global__ __launch_bounds__(SM_NT) void sample_rows_kernel(SampleSel a) {
   }
   const T* row = static_cast<const T*>(a.logits) + (size_t)r * a.ld;
   const bool vec = a.vec != 0;
-  float m = -3.0e38f, s = 0.f;
-  for_row<T>(row, V, vec, [&](int, float x) {
-    if (x > m) {
-      s = s * expf(m - x) + 1.f;
-      m = x;
-    } else {
-      s += expf(x - m);
-    }
-  });
-  const float wm = wave_max(m);
-  const float ws = wave_sum(s * expf(m - wm));
-  if (lane == 0) { sh.red_m[wave] = wm; sh.red_s[wave] = ws; }
-  __syncthreads();
-  float bm = sh.red_m[0];
-#pragma unroll
-  for (int w = 1; w < SM_WAVES; ++w) bm = fmaxf(bm, sh.red_m[w]);
-  float bs = 0.f;
-#pragma unroll
-  for (int w = 0; w < SM_WAVES; ++w) bs += sh.red_s[w] * expf(sh.red_m[w] - bm);
-  const float lse = bm + logf(bs);
-  const float zmax = bm * a.inv_t;                                  // rounding is monotone: the maximum of z
+  const RowLse rl = row_lse<T, SM_NT>(row, V, vec, sh.red_m, sh.red_s);
+  const float lse = rl.lse;
+  const float zmax = rl.max * a.inv_t;                              // rounding is monotone: the maximum of z
 
   const uint32_t K = a.top_k > 0 ? (uint32_t)min(a.top_k, V) : (uint32_t)V;
   const bool have_k = K < (uint32_t)V, have_p = a.top_p < 1.f, all = !have_k && !have_p;
@@ -258,22 +224,18 @@ __global__ __launch_bounds__(SM_NT) void sample_rows_kernel(SampleSel a) {
   const u64 site = (u64)t * (u64)(a.N * a.S) + (u64)r;
   const uint32_t k32 = (uint32_t)splitmix64(*a.seed_dev ^ (site * 0xD6E8FEB86659FD93ull));
   u64 best = 0ull;
-  for_row<T>(row, V, vec, [&](int v, float x) {
+  for_row<T, SM_NT>(row, V, vec, [&](int v, float x) {
     const float z = x * a.inv_t;
     const uint32_t key = order_bits(z);
     if (all || key > thr || (key == thr && v <= v_cut)) {
       const uint32_t h = mix32((uint32_t)v ^ k32) >> 9;
       const float u = (float)(2u * h + 1u) * 5.9604644775390625e-8f;          // (2h + 1) * 2^-24: exact, in (0, 1)
       const float g = -logf(-log1pf(-u));
-      const u64 c = ((u64)order_bits(z + g) << 32) | (uint32_t)~(uint32_t)v;
+      const u64 c = compose(order_bits(z + g), (uint32_t)v);
       best = c > best ? c : best;
     }
   });
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const u64 x = __shfl_xor(best, o, 64);
-    best = x > best ? x : best;
-  }
+  best = wave_max_u64(best);
   if (lane == 0) sh.red_c[wave] = best;
   __syncthreads();
   if (tid == 0) {
@@ -311,10 +273,8 @@ extern "C" int hero_sample_select(const void* logits, float* cum, int* fin, int*
   HERO_REQUIRE(logits && cum && fin && len && ids && last && seed_dev, "hero_sample_select: null pointer");
   HERO_REQUIRE(pos_dev || (pos >= 0 && pos < Tcap), "hero_sample_select: position %d outside [0, Tcap = %d)", pos, Tcap);
   HERO_REQUIRE((((uintptr_t)seed_dev) & 7) == 0, "hero_sample_select: the seed word must be 8-byte aligned");
-  const size_t es = dtype == HERO_F32 ? 4 : 2;
-  const int vec = (ld % 4 == 0 && (((uintptr_t)logits) & (4 * es - 1)) == 0) ? 1 : 0;   // every row starts on a 4-element boundary
-  const SampleSel a = {logits, seed_dev, pos_dev, cum, fin, len, ids, last, kept, pos, N, S, V, ld, Tcap, eos, top_k, vec,
-                       inv_temperature, top_p};
+  const SampleSel a = {logits, seed_dev, pos_dev, cum, fin, len, ids, last, kept, pos, N, S, V, ld, Tcap, eos, top_k,
+                       rows_vec4(logits, ld, dtype), inv_temperature, top_p};
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dtype == HERO_F32) hipLaunchKernelGGL((sample_rows_kernel<float>), dim3(N * S), dim3(SM_NT), 0, st, a);
   else hipLaunchKernelGGL((sample_rows_kernel<bf16_t>), dim3(N * S), dim3(SM_NT), 0, st, a);

@@ -91,8 +91,8 @@ class TvcDecodeState(object):
 class BeamTables(object):
     """The tables of a beam search over rows = N * B decode rows (include/hero_hip.h "Beam-search selection"): cum [rows] fp32
     the summed log-probabilities, fin / len [rows] finished flag and token count, ids / anc [rows, max_step] the tokens and
-    the cache row of every decoded position, ws the selection kernel's workspace.  int32 on the kernels' route (the kernel's
-    types), int64 indices in PyTorch ops."""
+    the cache row of every decoded position, ws the selection kernel's workspace, kept [rows] what a sampled decode reports.
+    int32 on the kernels' route (the kernel's types), int64 indices in PyTorch ops."""
     DEAD = -1.0e30          # the initial score of the beams 1 .. B-1: below every real candidate of beam 0
 
     def __init__(self, N, B, max_step, device, fused):
@@ -100,31 +100,28 @@ class BeamTables(object):
         self.N, self.B = N, B
         self.cum = torch.empty((R,), dtype=torch.float32, device=device)
         self.fin, self.len = (torch.empty((R,), dtype=it, device=device) for _ in range(2))
+        self.kept = torch.zeros((R,), dtype=it, device=device)      # sampling: the size of every row's kept set at the last step
         self.ids, self.anc = (torch.empty((R, max_step), dtype=it, device=device) for _ in range(2))
         self.ws = torch.empty((R * B,), dtype=torch.int64, device=device) if fused else None
         self._cum0 = torch.full((N, B), self.DEAD, dtype=torch.float32, device=device)
         self._cum0[:, 0] = 0.0
         self._anc0 = torch.arange(R, dtype=it, device=device).unsqueeze(1).expand(R, max_step).contiguous()
 
-    def reset(self):
-        self.cum.copy_(self._cum0.view(-1))
+    def reset(self, sampling=False):
+        """The start of a beam search, or of a SAMPLED decode (include/hero_hip.h "Sampled decoding"): there the rows of a caption
+        are independent samples, so every row starts alive at cum = 0 and the ancestry stays the identity for the whole decode."""
+        if sampling:
+            self.cum.zero_()
+        else:
+            self.cum.copy_(self._cum0.view(-1))
         self.fin.zero_()
         self.len.zero_()
         self.ids.zero_()
         self.anc.copy_(self._anc0)
+        return self
 
     def reset_sampling(self):
-        """The start of a SAMPLED decode (include/hero_hip.h "Sampled decoding"): the rows of a caption are independent samples,
-        so every row starts alive at cum = 0 and the ancestry stays the identity for the whole decode.  `kept` [rows] (the size of
-        every row's kept set at the last step) is made on first use and keeps its address."""
-        self.cum.zero_()
-        self.fin.zero_()
-        self.len.zero_()
-        self.ids.zero_()
-        self.anc.copy_(self._anc0)
-        if getattr(self, "kept", None) is None:
-            self.kept = torch.zeros_like(self.fin)
-        return self
+        return self.reset(sampling=True)
 
 
 def beam_select_torch(scores, tb, t, eos):
@@ -639,11 +636,19 @@ class TvcGenerator(object):
         self.counts["steps"] += done
         return done
 
-    def _replay(self, kind, encoder_outputs, enc_mask, make, prepare=None, stop_at_eos=False):
-        """The captured step of `kind` for this shape, refilled with the batch and replayed max_step times -> its entry.  On first
-        use make() -> dict(state, last = the ids buffer the step embeds, step = one step on device buffers only, ...): the step runs
-        once eagerly, so that every compute copy of a weight exists, and is then captured on one stream - a straight line."""
+    def _decode(self, kind, encoder_outputs, enc_mask, make, prepare=None, stop_at_eos=False):
+        """One decode of `kind` (the kind's part of a graph key) over the batch -> its entry.  make() -> dict(state, last = the ids
+        buffer the step embeds, filled with `bos`, step = one step on device buffers only that leaves the next ids in `last`, ...);
+        prepare(entry) is what the kind adds to a filled state (sampling: its tables and seed).  Eager: a new entry per call.
+        use_graph: the entry is made once per shape - the step runs once eagerly, so that every compute copy of a weight exists,
+        and is then captured on one stream, a straight line - and from then on refilled with the batch and replayed."""
         model = self.model
+        if not self.use_graph:
+            hit = make()
+            if prepare is not None:
+                prepare(hit)
+            self._run_steps(hit["state"], hit["step"], stop_at_eos)
+            return hit
         N, Lv = encoder_outputs.shape[:2]
         key = kind + (N, Lv, self.max_step, HF.compute_dtype(), str(encoder_outputs.device), HF.weight_cache_generation())
         hit = self._graphs.get(key)
@@ -681,33 +686,21 @@ class TvcGenerator(object):
             HF.refresh_weight_cache()
             hit["wsig"] = wsig
         model.refill_decode_state(hit["state"], encoder_outputs, enc_mask)
-        if prepare is not None:                                 # what the kind adds to a refilled state (sampling: its tables and seed)
+        if prepare is not None:
             prepare(hit)
         hit["last"].fill_(self.bos)
         self.counts["replayed"] += self._run_steps(hit["state"], hit["graph"].replay, stop_at_eos)
         return hit
 
-    def _decode_graph(self, encoder_outputs, enc_mask):
+    @torch.no_grad()
+    def _decode_cached(self, encoder_outputs, enc_mask):
         def make():
             N, dev = encoder_outputs.shape[0], encoder_outputs.device
             state = self.model.init_decode_state(encoder_outputs, enc_mask, self.max_step)
             last = torch.full((N,), self.bos, dtype=torch.long, device=dev)
             out = torch.zeros((N, self.max_step), dtype=torch.long, device=dev)
             return dict(state=state, last=last, out=out, step=lambda: self._step(state, last, out))
-        return self._replay((), encoder_outputs, enc_mask, make)["out"]
-
-    @torch.no_grad()
-    def _decode_cached(self, encoder_outputs, enc_mask):
-        if self.use_graph:
-            return self._decode_graph(encoder_outputs, enc_mask)
-        N, dev = encoder_outputs.shape[0], encoder_outputs.device
-        state = self.model.init_decode_state(encoder_outputs, enc_mask, self.max_step)
-        last = torch.full((N,), self.bos, dtype=torch.long, device=dev)
-        output_ids = torch.empty((N, self.max_step), dtype=torch.long, device=dev)
-        for _ in range(self.max_step):
-            self._step(state, last, output_ids)
-        self.counts["steps"] += self.max_step
-        return output_ids
+        return self._decode((), encoder_outputs, enc_mask, make)["out"]
 
     @torch.no_grad()
     def greedy_decode(self, batch, encoder_outputs=None):
@@ -747,25 +740,35 @@ class TvcGenerator(object):
         return state, torch.full((state.rows,), self.bos, dtype=torch.long, device=encoder_outputs.device)
 
     def _beam_step(self, state, last):
-        """One beam step on device buffers only: decode_step over all rows, then the selection.  Fused: hero_beam_select updates
-        the tables in place and leaves the next ids in the state's `wid`; the position it reads has already advanced, hence the
-        offset.  PyTorch route: the same algorithm in ops, and the kept keys / values follow their parents.  -> the next ids."""
+        """One beam step on device buffers only: decode_step over all rows, then the selection; the next ids go to `last`.  Fused:
+        hero_beam_select updates the tables in place and leaves the ids in the state's `wid`, which is `last`; the position it
+        reads has already advanced, hence the offset.  PyTorch route: the same algorithm in ops, and the kept keys / values
+        follow their parents."""
         model, tb = self.model, state.tables
         scores = model.decode_step(state, last)
         if state.fused:
             T.k_beam_select(scores, tb.cum, tb.fin, tb.len, tb.ids, tb.anc, state.wid, tb.ws, state.pos, state.N, state.beam,
                             scores.shape[1], self.eos, pos_offset=-1)
-            return state.wid
+            return
         rows, nxt = beam_select_torch(scores, tb, state.t - 1, self.eos)
         model.reorder_decode_state(state, rows)
-        return nxt
+        last.copy_(nxt)
 
-    def _beam_graph(self, encoder_outputs, enc_mask, beam_size, stop_at_eos=False):
-        """The beam step captured once per (N, beam, Lv, max_step); it shares the graph table with the greedy steps."""
-        def make():
-            state, last = self._beam_state(encoder_outputs, enc_mask, beam_size)
-            return dict(state=state, last=last, step=lambda: self._beam_step(state, last))
-        return self._replay(("beam", beam_size), encoder_outputs, enc_mask, make, stop_at_eos=stop_at_eos)["state"]
+    def _pick(self, tb, N, per, length_penalty, return_all, return_scores):
+        """Of the `per` rows of each of the N captions the one with the largest  cum / max(len, 1) ** length_penalty  - a stable
+        sort: the lower row wins a tie - or, with return_all, every row in row order; ids and the fp32 scores' bits come to the
+        host in ONE int32 transfer.  -> list of id lists cut at `eos`[, list of their scores]."""
+        norm = tb.cum.view(N, per) / tb.len.view(N, per).clamp(min=1).to(torch.float32) ** float(length_penalty)
+        if return_all:
+            rows, picked = torch.arange(N * per, device=norm.device), norm.reshape(-1, 1)
+        else:
+            best = torch.sort(norm, dim=1, descending=True, stable=True).indices[:, :1]
+            rows, picked = torch.arange(N, device=best.device) * per + best[:, 0], norm.gather(1, best)
+        packed = torch.cat([tb.ids[rows].to(torch.int32), picked.contiguous().view(torch.int32)], dim=1).cpu()
+        ids = [self.cut_eos(r) for r in packed[:, :-1].tolist()]
+        if return_scores:
+            return ids, packed[:, -1:].contiguous().view(torch.float32).view(-1).tolist()
+        return ids
 
     @torch.no_grad()
     def beam_decode(self, batch, beam_size, length_penalty=1.0, encoder_outputs=None, return_scores=False, stop_at_eos=False):
@@ -773,65 +776,42 @@ class TvcGenerator(object):
         N * beam_size rows, no early exit - a finished beam carries `eos` at an unchanged score - then per caption the beam with
         the largest  cum / max(len, 1) ** length_penalty  (the lower beam among equals), ONE host transfer, and the ids cut at
         `eos`.  On the kernels' route the selection is hero_beam_select and neither the cache nor the encoder keys are copied or
-        replicated; use_graph replays the captured step.  stop_at_eos: leave the loop once every beam of every caption has finished
+        replicated; use_graph replays the step, captured once per (N, beam, Lv, max_step) into the graph table it shares with the
+        greedy steps.  stop_at_eos: leave the loop once every beam of every caption has finished
         (one word read from the device after every `check_every` steps, outside the captured step); the result is that of the
         full-length run.  -> list of id lists[, list of the picked beams' scores]."""
         if not self.kv_cache:
             raise ValueError("TvcGenerator: beam_decode runs on the incremental decode step, it needs kv_cache=True")
         if beam_size < 1:
             raise ValueError("TvcGenerator: beam size %d < 1" % beam_size)
-        model = self.model
         if encoder_outputs is None:
-            encoder_outputs = model.encode(batch)
+            encoder_outputs = self.model.encode(batch)
         enc_mask = batch["cap_attn_mask"]
-        if self.use_graph:
-            state = self._beam_graph(encoder_outputs, enc_mask, beam_size, stop_at_eos)
-        else:
+
+        def make():
             state, last = self._beam_state(encoder_outputs, enc_mask, beam_size)
-            cur = [last]
-            self._run_steps(state, lambda: cur.__setitem__(0, self._beam_step(state, cur[0])), stop_at_eos)
-        tb, N, B = state.tables, state.N, beam_size
-        norm = tb.cum.view(N, B) / tb.len.view(N, B).clamp(min=1).to(torch.float32) ** float(length_penalty)
-        best = torch.sort(norm, dim=1, descending=True, stable=True).indices[:, :1]            # stable: the lower beam wins a tie
-        rows = torch.arange(N, device=best.device) * B + best[:, 0]
-        packed = torch.cat([tb.ids[rows].to(torch.int32), norm.gather(1, best).contiguous().view(torch.int32)], dim=1).cpu()
-        ids = [self.cut_eos(r) for r in packed[:, :-1].tolist()]
-        if return_scores:
-            return ids, packed[:, -1:].contiguous().view(torch.float32).view(-1).tolist()
-        return ids
+            return dict(state=state, last=last, step=lambda: self._beam_step(state, last))
+        state = self._decode(("beam", beam_size), encoder_outputs, enc_mask, make, stop_at_eos=stop_at_eos)["state"]
+        return self._pick(state.tables, state.N, beam_size, length_penalty, False, return_scores)
 
     # ---- sampling -----------------------------------------------------------------------------------------------------------
     def _sample_step(self, state, last, seed, params):
-        """One sampling step on device buffers only: decode_step over all rows, then the draw.  Fused: hero_sample_select updates
-        the tables in place and leaves the next ids in the state's `wid` (`seed` is a device word); PyTorch route: the same
-        algorithm in ops (`seed` is an int).  -> the next ids."""
+        """One sampling step on device buffers only: decode_step over all rows, then the draw; the next ids go to `last`.  Fused:
+        hero_sample_select updates the tables in place and leaves the ids in the state's `wid`, which is `last` (`seed` is a
+        device word); PyTorch route: the same algorithm in ops (`seed` is an int)."""
         tb = state.tables
         temperature, top_k, top_p = params
         scores = self.model.decode_step(state, last)
         if state.fused:
             T.k_sample_select(scores, tb.cum, tb.fin, tb.len, tb.ids, state.wid, tb.kept, seed, state.pos, state.N, state.beam,
                               scores.shape[1], self.eos, temperature, top_k, top_p, pos_offset=-1)
-            return state.wid
-        return sample_select_torch(scores, tb, state.t - 1, self.eos, seed, temperature, top_k, top_p)[0]
+            return
+        last.copy_(sample_select_torch(scores, tb, state.t - 1, self.eos, seed, temperature, top_k, top_p)[0])
 
     @staticmethod
     def _seed_word(seed):
         s = int(seed) & _M64
         return s - (1 << 64) if s >= (1 << 63) else s              # the same 64 bits in an int64
-
-    def _sample_graph(self, encoder_outputs, enc_mask, n_samples, seed, params, stop_at_eos):
-        """The sampling step captured once per (N, samples, Lv, max_step, temperature, top_k, top_p) - the three are launch scalars
-        of the captured kernel; the seed is a device word filled before the replays."""
-        def make():
-            state, last = self._beam_state(encoder_outputs, enc_mask, n_samples)
-            state.tables.reset_sampling()
-            word = torch.zeros((1,), dtype=torch.long, device=encoder_outputs.device)
-            return dict(state=state, last=last, seed=word, step=lambda: self._sample_step(state, last, word, params))
-
-        def prepare(hit):
-            hit["state"].tables.reset_sampling()
-            hit["seed"].fill_(self._seed_word(seed))
-        return self._replay(("sample", n_samples) + params, encoder_outputs, enc_mask, make, prepare, stop_at_eos)["state"]
 
     @torch.no_grad()
     def sample_decode(self, batch, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=1.0,
@@ -843,8 +823,10 @@ class TvcGenerator(object):
         the model's own log-likelihood of the drawn tokens (temperature 1, no filter).  -> per caption the sample with the
         largest  cum / max(len, 1) ** length_penalty  (the lower sample among equals), or with return_all all N * n_samples
         captions in row order (caption-major); ONE host transfer, ids cut at `eos`[, the scores of the returned captions].
-        On the kernels' route (n_samples within the beam envelope) the draw is hero_sample_select; use_graph replays the captured
-        step and a new seed does not recapture.  stop_at_eos as in beam_decode.  top_k = 1 is greedy decoding."""
+        On the kernels' route (n_samples within the beam envelope) the draw is hero_sample_select; use_graph replays the step,
+        captured once per (N, samples, Lv, max_step, temperature, top_k, top_p) - the three are launch scalars of the captured
+        kernel, the seed is a device word filled before the replays: a new seed does not recapture.  stop_at_eos as in
+        beam_decode.  top_k = 1 is greedy decoding."""
         if not self.kv_cache:
             raise ValueError("TvcGenerator: sample_decode runs on the incremental decode step, it needs kv_cache=True")
         if n_samples < 1:
@@ -856,32 +838,24 @@ class TvcGenerator(object):
         if not top_p > 0:
             raise ValueError("TvcGenerator: top_p %r must be > 0" % (top_p,))
         params = (float(temperature), int(top_k), float(top_p))
-        model = self.model
         if encoder_outputs is None:
-            encoder_outputs = model.encode(batch)
+            encoder_outputs = self.model.encode(batch)
         enc_mask = batch["cap_attn_mask"]
-        if self.use_graph:
-            state = self._sample_graph(encoder_outputs, enc_mask, n_samples, seed, params, stop_at_eos)
-        else:
+
+        def make():
             state, last = self._beam_state(encoder_outputs, enc_mask, n_samples)
-            state.tables.reset_sampling()
-            word = seed
-            if state.fused:
-                word = torch.full((1,), self._seed_word(seed), dtype=torch.long, device=encoder_outputs.device)
-            cur = [last]
-            self._run_steps(state, lambda: cur.__setitem__(0, self._sample_step(state, cur[0], word, params)), stop_at_eos)
-        tb, N, S = state.tables, state.N, n_samples
-        norm = tb.cum.view(N, S) / tb.len.view(N, S).clamp(min=1).to(torch.float32) ** float(length_penalty)
-        if return_all:
-            rows, picked = torch.arange(N * S, device=norm.device), norm.reshape(-1, 1)
-        else:
-            best = torch.sort(norm, dim=1, descending=True, stable=True).indices[:, :1]        # stable: the lower sample wins a tie
-            rows, picked = torch.arange(N, device=best.device) * S + best[:, 0], norm.gather(1, best)
-        packed = torch.cat([tb.ids[rows].to(torch.int32), picked.contiguous().view(torch.int32)], dim=1).cpu()
-        ids = [self.cut_eos(r) for r in packed[:, :-1].tolist()]
-        if return_scores:
-            return ids, packed[:, -1:].contiguous().view(torch.float32).view(-1).tolist()
-        return ids
+            hit = dict(state=state, last=last, seed=torch.zeros((1,), dtype=torch.long, device=last.device) if state.fused else 0)
+            hit["step"] = lambda: self._sample_step(state, last, hit["seed"], params)
+            return hit
+
+        def prepare(hit):                                           # the seed: a device word on the kernels' route, the int in PyTorch ops
+            hit["state"].tables.reset(sampling=True)
+            if hit["state"].fused:
+                hit["seed"].fill_(self._seed_word(seed))
+            else:
+                hit["seed"] = seed
+        state = self._decode(("sample", n_samples) + params, encoder_outputs, enc_mask, make, prepare, stop_at_eos)["state"]
+        return self._pick(state.tables, state.N, n_samples, length_penalty, return_all, return_scores)
 
     def cut_eos(self, ids):
         out_ids = []

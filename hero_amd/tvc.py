@@ -123,6 +123,20 @@ def k_dec_attn_row(q, kv, key_mask_add, N, Lk, H, group=1):
     return ctxt
 
 
+def _pos_args(what, pos, pos_offset, Tcap, device):
+    """The position of a step as the kernels take it, (pos_dev, pos_host): a 1-element int32 device tensor is read by the kernel
+    and `pos_offset` added to it there; an int is checked here and passed with the offset already added."""
+    if torch.is_tensor(pos):
+        if pos.numel() != 1 or pos.dtype != torch.int32 or pos.device != device:
+            raise ValueError("%s: a device position must be one int32 on %s, got %s %s on %s"
+                             % (what, device, tuple(pos.shape), pos.dtype, pos.device))
+        return L.ptr(pos), int(pos_offset)
+    pos_host = int(pos) + int(pos_offset)
+    if not 0 <= pos_host < Tcap:
+        raise ValueError("%s: position %d outside [0, Tcap = %d)" % (what, pos_host, Tcap))
+    return None, pos_host
+
+
 def k_dec_attn_step(qkv, cache, pos, N, H, anc=None):
     """Causal self-attention of position `pos` against a key/value cache (inference):
     qkv [N, 3*H*64] this step's packed Q|K|V rows, cache [N, Tcap, 2*H*64] with K|V of the positions < pos; the kernel also
@@ -141,15 +155,7 @@ def k_dec_attn_step(qkv, cache, pos, N, H, anc=None):
     if tuple(cache.shape) != (N, Tcap, 2 * D) or cache.dtype != qkv.dtype:
         raise ValueError("decoder attention: the cache must be [%d, Tcap, %d] of %s, got %s %s"
                          % (N, 2 * D, qkv.dtype, tuple(cache.shape), cache.dtype))
-    if torch.is_tensor(pos):
-        if pos.numel() != 1 or pos.dtype != torch.int32 or pos.device != qkv.device:
-            raise ValueError("decoder attention: a device position must be one int32 on %s, got %s %s on %s"
-                             % (qkv.device, tuple(pos.shape), pos.dtype, pos.device))
-        pos_dev, pos_host = L.ptr(pos), 0
-    else:
-        pos_dev, pos_host = None, int(pos)
-        if not 0 <= pos_host < Tcap:
-            raise ValueError("decoder attention: position %d outside [0, Tcap = %d)" % (pos_host, Tcap))
+    pos_dev, pos_host = _pos_args("decoder attention", pos, 0, Tcap, qkv.device)
     ctxt = torch.empty((N, D), dtype=qkv.dtype, device=qkv.device)
     if anc is None:
         L.check(L.lib().hero_dec_attention_step(L.ptr(qkv), L.ptr(cache), L.ptr(ctxt), pos_dev, pos_host, N, Tcap, H,
@@ -177,36 +183,43 @@ def _beam_table(name, t, shape, dtype, device):
                          % (name, dtype, shape, device, tuple(t.shape), t.dtype, t.device))
 
 
+def _score_rows(what, logits, R, ids):
+    """The scores of a selection step, [R, >= V] with rows `ld` apart (they may be the first V columns of a wider buffer: the
+    padded vocabulary) -> (ld, Tcap of the id table)."""
+    if logits.dim() != 2 or logits.shape[0] != R or logits.stride(1) != 1:
+        raise ValueError("%s: the scores must be [%d, >= V] with unit column stride, got %s" % (what, R, tuple(logits.shape)))
+    return logits.stride(0), ids.shape[1] if ids.dim() == 2 else 0
+
+
+def _cols_in_range(logits, ld, V, eos):
+    """The vocabulary fits the score rows and holds `eos` (part of each kernel's envelope, refused in its words)."""
+    return ld >= V and logits.shape[1] >= V and 0 <= eos < V
+
+
+def _select_tables(R, Tcap, dev, cum, rows, mats):
+    """The tables a selection step updates: cum [R] fp32, `rows` [R] and `mats` [R, Tcap] int32, as (name, tensor) pairs."""
+    _beam_table("cum", cum, (R,), torch.float32, dev)
+    for name, t in rows:
+        _beam_table(name, t, (R,), torch.int32, dev)
+    for name, t in mats:
+        _beam_table(name, t, (R, Tcap), torch.int32, dev)
+
+
 def k_beam_select(logits, cum, fin, length, ids, anc, last, workspace, pos, N, B, V, eos, pos_offset=0):
     """One selection step of beam search for N captions x B beams (row r = n*B + b), in place and on the device
     (include/hero_hip.h "Beam-search selection"): logits [R, ld >= V] fp32 / bf16; cum [R] fp32; fin, length, last [R] and
     ids, anc [R, Tcap] int32; workspace: at least R*B int64.  pos: the step's position as an int, or a 1-element int32 device
     tensor to which `pos_offset` is added (-1 when the counter has already advanced)."""
     R = N * B
-    if logits.dim() != 2 or logits.shape[0] != R or logits.stride(1) != 1:
-        raise ValueError("beam search: the scores must be [%d, >= V] with unit column stride, got %s" % (R, tuple(logits.shape)))
-    ld, Tcap, dev = logits.stride(0), ids.shape[1] if ids.dim() == 2 else 0, logits.device
-    if not in_envelope_beam(logits.dtype, V, B, Tcap) or N < 1 or ld < V or logits.shape[1] < V or not 0 <= eos < V:
+    (ld, Tcap), dev = _score_rows("beam search", logits, R, ids), logits.device
+    if not in_envelope_beam(logits.dtype, V, B, Tcap) or N < 1 or not _cols_in_range(logits, ld, V, eos):
         raise ValueError("beam search: %s, N=%d, B=%d, V=%d, ld=%d, Tcap=%d, eos=%d is outside the selection kernel's envelope (fp32 / "
                          "bf16, 1 <= B <= %d, B <= V <= %d, 1 <= Tcap <= %d, ld >= V, 0 <= eos < V)"
                          % (logits.dtype, N, B, V, ld, Tcap, eos, MAX_BEAM, MAX_BEAM_V, MAX_LK))
-    _beam_table("cum", cum, (R,), torch.float32, dev)
-    for name, t in (("fin", fin), ("len", length), ("last", last)):
-        _beam_table(name, t, (R,), torch.int32, dev)
-    for name, t in (("ids", ids), ("anc", anc)):
-        _beam_table(name, t, (R, Tcap), torch.int32, dev)
+    _select_tables(R, Tcap, dev, cum, (("fin", fin), ("len", length), ("last", last)), (("ids", ids), ("anc", anc)))
     if workspace.dtype != torch.int64 or workspace.numel() < R * B or workspace.device != dev or not workspace.is_contiguous():
         raise ValueError("beam search: the workspace must be at least %d contiguous int64 on %s" % (R * B, dev))
-    if torch.is_tensor(pos):
-        if pos.numel() != 1 or pos.dtype != torch.int32 or pos.device != dev:
-            raise ValueError("beam search: a device position must be one int32 on %s, got %s %s on %s"
-                             % (dev, tuple(pos.shape), pos.dtype, pos.device))
-        pos_dev, pos_host = L.ptr(pos), int(pos_offset)
-    else:
-        pos_dev, pos_host = None, int(pos) + int(pos_offset)
-        if not 0 <= pos_host < Tcap:
-            raise ValueError("beam search: position %d outside [0, Tcap = %d)" % (pos_host, Tcap))
-    # the scores may be the first V columns of a wider buffer (the padded vocabulary): rows ld apart, not contiguous
+    pos_dev, pos_host = _pos_args("beam search", pos, pos_offset, Tcap, dev)
     L.check(L.lib().hero_beam_select(logits.data_ptr(), L.ptr(cum), L.ptr(fin), L.ptr(length), L.ptr(ids), L.ptr(anc), L.ptr(last),
                                      L.ptr(workspace), pos_dev, pos_host, N, B, V, ld, Tcap, eos, L.dt(logits), L.stream()))
 
@@ -230,32 +243,19 @@ def k_sample_select(logits, cum, fin, length, ids, last, kept, seed, pos, N, S, 
     step's position as an int, or a 1-element int32 device tensor to which `pos_offset` is added.  temperature > 0, top_k >= 0
     (0 = off), top_p > 0 (>= 1 = off)."""
     R = N * S
-    if logits.dim() != 2 or logits.shape[0] != R or logits.stride(1) != 1:
-        raise ValueError("sampling: the scores must be [%d, >= V] with unit column stride, got %s" % (R, tuple(logits.shape)))
-    ld, Tcap, dev = logits.stride(0), ids.shape[1] if ids.dim() == 2 else 0, logits.device
+    (ld, Tcap), dev = _score_rows("sampling", logits, R, ids), logits.device
     if not temperature > 0 or not math.isfinite(temperature) or top_k < 0 or not top_p > 0:
         raise ValueError("sampling: temperature %r, top_k %r, top_p %r: temperature must be finite and > 0, top_k >= 0, top_p > 0"
                          % (temperature, top_k, top_p))
-    if not in_envelope_sample(logits.dtype, V, Tcap) or N < 1 or S < 1 or ld < V or logits.shape[1] < V or not 0 <= eos < V:
+    if not in_envelope_sample(logits.dtype, V, Tcap) or N < 1 or S < 1 or not _cols_in_range(logits, ld, V, eos):
         raise ValueError("sampling: %s, N=%d, S=%d, V=%d, ld=%d, Tcap=%d, eos=%d is outside the sampling kernel's envelope (fp32 / "
                          "bf16, N, S >= 1, 1 <= V <= %d, 1 <= Tcap <= %d, ld >= V, 0 <= eos < V)"
                          % (logits.dtype, N, S, V, ld, Tcap, eos, MAX_BEAM_V, MAX_LK))
-    _beam_table("cum", cum, (R,), torch.float32, dev)
-    for name, t in (("fin", fin), ("len", length), ("last", last)) + ((("kept", kept),) if kept is not None else ()):
-        _beam_table(name, t, (R,), torch.int32, dev)
-    _beam_table("ids", ids, (R, Tcap), torch.int32, dev)
+    _select_tables(R, Tcap, dev, cum, (("fin", fin), ("len", length), ("last", last)) + ((("kept", kept),) if kept is not None else ()),
+                   (("ids", ids),))
     if not torch.is_tensor(seed) or seed.numel() != 1 or seed.dtype != torch.int64 or seed.device != dev:
         raise ValueError("sampling: the seed must be one int64 on %s" % (dev,))
-    if torch.is_tensor(pos):
-        if pos.numel() != 1 or pos.dtype != torch.int32 or pos.device != dev:
-            raise ValueError("sampling: a device position must be one int32 on %s, got %s %s on %s"
-                             % (dev, tuple(pos.shape), pos.dtype, pos.device))
-        pos_dev, pos_host = L.ptr(pos), int(pos_offset)
-    else:
-        pos_dev, pos_host = None, int(pos) + int(pos_offset)
-        if not 0 <= pos_host < Tcap:
-            raise ValueError("sampling: position %d outside [0, Tcap = %d)" % (pos_host, Tcap))
-    # the scores may be the first V columns of a wider buffer (the padded vocabulary): rows ld apart, not contiguous
+    pos_dev, pos_host = _pos_args("sampling", pos, pos_offset, Tcap, dev)
     L.check(L.lib().hero_sample_select(logits.data_ptr(), L.ptr(cum), L.ptr(fin), L.ptr(length), L.ptr(ids), L.ptr(last), L.ptr(kept),
                                        L.ptr(seed), pos_dev, pos_host, N, S, V, ld, Tcap, eos, inv_temperature(temperature),
                                        int(top_k), float(top_p), L.dt(logits), L.stream()))
