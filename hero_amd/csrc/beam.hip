@@ -161,9 +161,10 @@ extern "C" int hero_beam_select(const void* logits, float* cum, int* fin, int* l
   const BeamSel a = {logits, pos_dev, cum, fin, len, ids, anc, last, static_cast<unsigned long long*>(workspace),
                      pos, N, B, V, ld, Tcap, eos, rows_vec4(logits, ld, dtype)};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HERO_F32) hipLaunchKernelGGL((beam_rows_kernel<float>), dim3(N * B), dim3(BM_NT), 0, st, a);
-  else hipLaunchKernelGGL((beam_rows_kernel<bf16_t>), dim3(N * B), dim3(BM_NT), 0, st, a);
-  if (const int rc = check_launch("hero_beam_select")) return rc;
+  const int rc = by_dtype(dtype, "hero_beam_select", [&](auto tag) {
+    hipLaunchKernelGGL((beam_rows_kernel<typename decltype(tag)::type>), dim3(N * B), dim3(BM_NT), 0, st, a);
+  });
+  if (rc) return rc;
   hipLaunchKernelGGL(beam_merge_kernel, dim3(N), dim3(BM_NT), 0, st, a);
   return check_launch("hero_beam_select");
 }

@@ -39,6 +39,13 @@ template <> struct V4<bf16_t> {
     *reinterpret_cast<uint2*>(p) = u;
   }
 };
+// fp32 quads: 16-byte access, the pairwise dot product, acc += s * v
+__device__ __forceinline__ float4 ldf4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void stf4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ float dot4(float4 a, float4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
+__device__ __forceinline__ void fma4(float4& acc, float s, float4 v) {
+  acc.x = fmaf(s, v.x, acc.x); acc.y = fmaf(s, v.y, acc.y); acc.z = fmaf(s, v.z, acc.z); acc.w = fmaf(s, v.w, acc.w);
+}
 template <typename T> __device__ __forceinline__ float ld1(const T* p);
 template <> __device__ __forceinline__ float ld1<float>(const float* p) { return *p; }
 template <> __device__ __forceinline__ float ld1<bf16_t>(const bf16_t* p) { return bf2f(*p); }
@@ -204,6 +211,17 @@ template <> __device__ __forceinline__ void gelu_both<bf16_t>(float x, float& y,
 // error plumbing (api.cpp)
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+
+// Host: f(DType<T>()) with the element type that a dtype code names, for launches whose branches differ only in T:
+//   return by_dtype(dtype, "hero_x", [&](auto tag) { using T = typename decltype(tag)::type; hipLaunchKernelGGL(x_kernel<T>, ...); });
+// An unknown code sets "<what>: bad dtype <code>" and launches nothing; after f the result is check_launch(what).
+template <typename T> struct DType { using type = T; };
+template <class F> int by_dtype(int dtype, const char* what, F f) {
+  if (dtype == HERO_F32) f(DType<float>());
+  else if (dtype == HERO_BF16) f(DType<bf16_t>());
+  else { set_error("%s: bad dtype %d", what, dtype); return HERO_ERR_ARG; }
+  return check_launch(what);
+}
 
 // "This kernel may use `bytes` of dynamic LDS": hipFuncSetAttribute is a PER-DEVICE setting and can be refused, so it is
 // applied once per (kernel, device) - a bit per device ordinal in the call site's own atomic mask, thread-safe - and its

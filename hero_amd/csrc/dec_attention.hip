@@ -58,10 +58,7 @@ __host__ __device__ inline Tiles tiles(int Lq, int Lk, bool bwd) {
   return t;
 }
 
-__device__ __forceinline__ float4 ldf4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void fma4(float4& acc, float s, float4 v) {
-  acc.x = fmaf(s, v.x, acc.x); acc.y = fmaf(s, v.y, acc.y); acc.z = fmaf(s, v.z, acc.z); acc.w = fmaf(s, v.w, acc.w);
-}
+// accumulating, one fma chain (common.h's two-argument dot4 is the pairwise sum of products)
 __device__ __forceinline__ float dot4(float4 a, float4 b, float acc) {
   return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, fmaf(a.x, b.x, acc))));
 }
@@ -434,14 +431,11 @@ int launch_row(const char* what, const DecRow& a, bool step, int dtype, hero_str
   HERO_REQUIRE(aligned16(a.q) && aligned16(a.k) && aligned16(a.v) && aligned16(a.ctx), "%s: operands must be 16-byte aligned", what);
   const dim3 grid((a.N * a.H + DR_WAVES - 1) / DR_WAVES), block(64 * DR_WAVES);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HERO_F32) {
-    if (step) hipLaunchKernelGGL((dec_attn_row_kernel<float, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((dec_attn_row_kernel<float, false>), grid, block, 0, st, a);
-  } else {
-    if (step) hipLaunchKernelGGL((dec_attn_row_kernel<bf16_t, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((dec_attn_row_kernel<bf16_t, false>), grid, block, 0, st, a);
-  }
-  return check_launch(what);
+  return by_dtype(dtype, what, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (step) hipLaunchKernelGGL((dec_attn_row_kernel<T, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((dec_attn_row_kernel<T, false>), grid, block, 0, st, a);
+  });
 }
 
 bool row_in_envelope(int dtype, int Lk) { return (dtype == HERO_F32 || dtype == HERO_BF16) && Lk >= 1 && Lk <= DA_MAX_LK; }

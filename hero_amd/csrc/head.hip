@@ -1,5 +1,6 @@
-// VSM / VCMR task-head kernels (gfx950): query pooling, row normalisation, masked max of the
-// query x frame scores, in-batch ranking loss, start/end localisation loss - forward and backward.
+// VSM / VCMR task-head kernels (gfx950): row normalisation, masked max of the query x frame scores,
+// in-batch ranking loss, start/end localisation loss - forward and backward.  (A, the query pooling,
+// is one of the attention pools of pool.hip.)
 //
 // These are the "small ops" of model/pretrain.py:62-292 and model/encoder.py:460-471: a few MB of
 // fp32 data per step, but ~250 PyTorch launches of 2-10 us each when written as tensor ops.  Each
@@ -18,91 +19,6 @@ __device__ __forceinline__ float block_sum(float v, float* red) {   // 256 threa
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float dot4(float4 a, float4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
-
-// ------------------------------------------------------------------------------------------------
-// A. query pooling
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void query_pool_fwd_kernel(HeroQueryPool a) {
-  extern __shared__ float sc[];                      // [L]
-  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const T* q = static_cast<const T*>(a.q) + (size_t)b * a.L * a.D;
-  for (int l = wave; l < a.L; l += 4) {
-    float s = 0.f;
-    for (int d = lane * 4; d < a.D; d += 256) s += dot4(V4<T>::ld(q + (size_t)l * a.D + d), *reinterpret_cast<const float4*>(a.w + d));
-    s = wave_sum(s);
-    if (lane == 0) {
-      const float m = a.mask[(size_t)b * a.L + l];
-      sc[l] = s * m + (1.f - m) * -10000.f;          // mask_logits, model/modeling_utils.py:42-43
-    }
-  }
-  __syncthreads();
-  if (wave == 0) {
-    float mx = -3.0e38f;
-    for (int l = lane; l < a.L; l += 64) mx = fmaxf(mx, sc[l]);
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int l = lane; l < a.L; l += 64) sum += __expf(sc[l] - mx);
-    sum = wave_sum(sum);
-    const float inv = 1.f / sum;
-    for (int l = lane; l < a.L; l += 64) {
-      const float p = __expf(sc[l] - mx) * inv;
-      sc[l] = p;
-      a.att[(size_t)b * a.L + l] = p;
-    }
-  }
-  __syncthreads();
-  for (int d = threadIdx.x * 4; d < a.D; d += 1024) {
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int l = 0; l < a.L; ++l) {
-      const float p = sc[l];
-      const float4 v = V4<T>::ld(q + (size_t)l * a.D + d);
-      acc.x = fmaf(p, v.x, acc.x); acc.y = fmaf(p, v.y, acc.y); acc.z = fmaf(p, v.z, acc.z); acc.w = fmaf(p, v.w, acc.w);
-    }
-    *reinterpret_cast<float4*>(a.pooled + (size_t)b * a.D + d) = acc;
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void query_pool_bwd_kernel(HeroQueryPool a) {
-  extern __shared__ float sm[];                      // da[L], ds[L]
-  float* da = sm;
-  float* ds = sm + a.L;
-  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const T* q = static_cast<const T*>(a.q) + (size_t)b * a.L * a.D;
-  const float* dp = a.dpooled + (size_t)b * a.D;
-  const float* att = a.att + (size_t)b * a.L;
-  for (int l = wave; l < a.L; l += 4) {              // d att[l] = <dpooled, q[l]>
-    float s = 0.f;
-    for (int d = lane * 4; d < a.D; d += 256) s += dot4(V4<T>::ld(q + (size_t)l * a.D + d), *reinterpret_cast<const float4*>(dp + d));
-    s = wave_sum(s);
-    if (lane == 0) da[l] = s;
-  }
-  __syncthreads();
-  if (wave == 0) {
-    float dot = 0.f;
-    for (int l = lane; l < a.L; l += 64) dot += att[l] * da[l];
-    dot = wave_sum(dot);
-    for (int l = lane; l < a.L; l += 64) ds[l] = att[l] * (da[l] - dot) * a.mask[(size_t)b * a.L + l];
-  }
-  __syncthreads();
-  T* dq = static_cast<T*>(a.dq) + (size_t)b * a.L * a.D;
-  for (int d = threadIdx.x * 4; d < a.D; d += 1024) {
-    const float4 g = *reinterpret_cast<const float4*>(dp + d);
-    const float4 w = *reinterpret_cast<const float4*>(a.w + d);
-    float4 dw = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int l = 0; l < a.L; ++l) {
-      const float p = att[l], s = ds[l];
-      const float4 v = V4<T>::ld(q + (size_t)l * a.D + d);
-      V4<T>::st(dq + (size_t)l * a.D + d, make_float4(fmaf(p, g.x, s * w.x), fmaf(p, g.y, s * w.y), fmaf(p, g.z, s * w.z), fmaf(p, g.w, s * w.w)));
-      dw.x = fmaf(s, v.x, dw.x); dw.y = fmaf(s, v.y, dw.y); dw.z = fmaf(s, v.z, dw.z); dw.w = fmaf(s, v.w, dw.w);
-    }
-    // dw: [B, D] partial sums, one row per query (round 4; the caller folds them in a fixed order - round 3 added the B
-    // shares to one [D] vector with fp32 atomics)
-    if (a.dw) *reinterpret_cast<float4*>(a.dw + (size_t)b * a.D + d) = dw;
-  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -525,38 +441,21 @@ __global__ __launch_bounds__(64) void sums_scaled_kernel(SumsArgs a) {
 
 using namespace hero;
 
-#define HERO_BY_DTYPE(dt, KERNEL, grid, lds, s, arg, what)                                         \
-  do {                                                                                             \
-    if ((dt) == HERO_F32) hipLaunchKernelGGL((KERNEL<float>), dim3(grid), dim3(256), lds, s, arg);  \
-    else if ((dt) == HERO_BF16) hipLaunchKernelGGL((KERNEL<bf16_t>), dim3(grid), dim3(256), lds, s, arg); \
-    else { set_error(what ": bad dtype %d", (dt)); return HERO_ERR_ARG; }                           \
-    return check_launch(what);                                                                     \
-  } while (0)
-
-extern "C" int hero_query_pool_fwd(const HeroQueryPool* a, hero_stream_t stream) {
-  HERO_REQUIRE(a && a->q && a->mask && a->w && a->pooled && a->att, "hero_query_pool_fwd: null pointer");
-  HERO_REQUIRE(a->L > 0 && a->L <= 4096 && a->D > 0 && a->D % 4 == 0, "hero_query_pool_fwd: bad dims L=%d D=%d", a->L, a->D);
-  if (a->B <= 0) return HERO_OK;
-  HERO_BY_DTYPE(a->dtype, query_pool_fwd_kernel, a->B, a->L * sizeof(float), static_cast<hipStream_t>(stream), *a, "hero_query_pool_fwd");
-}
-extern "C" int hero_query_pool_bwd(const HeroQueryPool* a, hero_stream_t stream) {
-  HERO_REQUIRE(a && a->q && a->mask && a->w && a->att && a->dpooled && a->dq, "hero_query_pool_bwd: null pointer");
-  HERO_REQUIRE(a->L > 0 && a->L <= 4096 && a->D > 0 && a->D % 4 == 0, "hero_query_pool_bwd: bad dims L=%d D=%d", a->L, a->D);
-  if (a->B <= 0) return HERO_OK;
-  HERO_BY_DTYPE(a->dtype, query_pool_bwd_kernel, a->B, 2 * a->L * sizeof(float), static_cast<hipStream_t>(stream), *a, "hero_query_pool_bwd");
-}
-
 extern "C" int hero_rownorm_fwd(const HeroRowNorm* a, hero_stream_t stream) {
   HERO_REQUIRE(a && a->x && a->y && a->rnorm, "hero_rownorm_fwd: null pointer");
   HERO_REQUIRE(a->cols > 0 && a->cols % 4 == 0, "hero_rownorm_fwd: cols (%d) must be a positive multiple of 4", a->cols);
   if (a->rows <= 0) return HERO_OK;
-  HERO_BY_DTYPE(a->x_dtype, rownorm_fwd_kernel, (a->rows + 3) / 4, 0, static_cast<hipStream_t>(stream), *a, "hero_rownorm_fwd");
+  return by_dtype(a->x_dtype, "hero_rownorm_fwd", [&](auto tag) {
+    hipLaunchKernelGGL((rownorm_fwd_kernel<typename decltype(tag)::type>), dim3((a->rows + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), *a);
+  });
 }
 extern "C" int hero_rownorm_bwd(const HeroRowNorm* a, hero_stream_t stream) {
   HERO_REQUIRE(a && a->x && a->rnorm && a->dy && a->dx, "hero_rownorm_bwd: null pointer");
   HERO_REQUIRE(a->cols > 0 && a->cols % 4 == 0, "hero_rownorm_bwd: cols (%d) must be a positive multiple of 4", a->cols);
   if (a->rows <= 0) return HERO_OK;
-  HERO_BY_DTYPE(a->x_dtype, rownorm_bwd_kernel, (a->rows + 3) / 4, 0, static_cast<hipStream_t>(stream), *a, "hero_rownorm_bwd");
+  return by_dtype(a->x_dtype, "hero_rownorm_bwd", [&](auto tag) {
+    hipLaunchKernelGGL((rownorm_bwd_kernel<typename decltype(tag)::type>), dim3((a->rows + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), *a);
+  });
 }
 
 extern "C" int hero_score_max_fwd(const HeroScoreMax* a, hero_stream_t stream) {
@@ -601,7 +500,9 @@ extern "C" int hero_st_ed_fwd(const HeroStEd* a, hero_stream_t stream) {
   HERO_REQUIRE(a->L > 0 && a->L <= 2048 && a->D % 4 == 0 && a->K >= 1 && a->K <= MAXK && (a->K & 1), "hero_st_ed_fwd: bad dims L=%d D=%d K=%d",
                a->L, a->D, a->K);
   if (a->B <= 0) return HERO_OK;
-  HERO_BY_DTYPE(a->dtype, st_ed_fwd_kernel, a->B, 3 * a->L * sizeof(float), static_cast<hipStream_t>(stream), *a, "hero_st_ed_fwd");
+  return by_dtype(a->dtype, "hero_st_ed_fwd", [&](auto tag) {
+    hipLaunchKernelGGL((st_ed_fwd_kernel<typename decltype(tag)::type>), dim3(a->B), dim3(256), 3 * a->L * sizeof(float), static_cast<hipStream_t>(stream), *a);
+  });
 }
 extern "C" size_t hero_st_ed_bwd_workspace_bytes(int B) { return ((size_t)(B > 0 ? B : 0) * 2 * (MAXK + 1) + 4) * sizeof(float); }
 
@@ -612,7 +513,9 @@ extern "C" int hero_st_ed_bwd(const HeroStEd* a, hero_stream_t stream) {
                a->L, a->D, a->K);
   HERO_REQUIRE(a->ws || !(a->dw_st || a->dw_ed), "hero_st_ed_bwd: dw_st / dw_ed need the workspace (hero_st_ed_bwd_workspace_bytes)");
   if (a->B <= 0) return HERO_OK;
-  HERO_BY_DTYPE(a->dtype, st_ed_bwd_kernel, a->B, 4 * a->L * sizeof(float), static_cast<hipStream_t>(stream), *a, "hero_st_ed_bwd");
+  return by_dtype(a->dtype, "hero_st_ed_bwd", [&](auto tag) {
+    hipLaunchKernelGGL((st_ed_bwd_kernel<typename decltype(tag)::type>), dim3(a->B), dim3(256), 4 * a->L * sizeof(float), static_cast<hipStream_t>(stream), *a);
+  });
 }
 
 extern "C" int hero_sums_scaled(const float* src, int n_segs, int seg_len, const float* scales, float* out, hero_stream_t stream) {

@@ -243,20 +243,18 @@ extern "C" int hero_cross_entropy_fwd(const HeroCrossEntropy* a, hero_stream_t s
   int rc = check_ce(a, false);
   if (rc) return rc;
   if (a->rows == 0) return HERO_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (a->dtype == HERO_BF16) hipLaunchKernelGGL(ce_fwd_kernel<bf16_t>, dim3(a->rows), dim3(256), 0, s, *a);
-  else hipLaunchKernelGGL(ce_fwd_kernel<float>, dim3(a->rows), dim3(256), 0, s, *a);
-  return check_launch("hero_cross_entropy_fwd");
+  return by_dtype(a->dtype, "hero_cross_entropy_fwd", [&](auto tag) {
+    hipLaunchKernelGGL(ce_fwd_kernel<typename decltype(tag)::type>, dim3(a->rows), dim3(256), 0, static_cast<hipStream_t>(stream), *a);
+  });
 }
 
 extern "C" int hero_cross_entropy_bwd(const HeroCrossEntropy* a, hero_stream_t stream) {
   int rc = check_ce(a, true);
   if (rc) return rc;
   if (a->rows == 0) return HERO_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (a->dtype == HERO_BF16) hipLaunchKernelGGL(ce_bwd_kernel<bf16_t>, dim3(a->rows), dim3(256), 0, s, *a);
-  else hipLaunchKernelGGL(ce_bwd_kernel<float>, dim3(a->rows), dim3(256), 0, s, *a);
-  return check_launch("hero_cross_entropy_bwd");
+  return by_dtype(a->dtype, "hero_cross_entropy_bwd", [&](auto tag) {
+    hipLaunchKernelGGL(ce_bwd_kernel<typename decltype(tag)::type>, dim3(a->rows), dim3(256), 0, static_cast<hipStream_t>(stream), *a);
+  });
 }
 
 static int check_smooth(const char* what, const void* logits, const long long* labels, const float* lse, int rows, int cols, int ld, int dtype,
@@ -300,8 +298,7 @@ extern "C" int hero_smooth_ce_bwd(const void* logits, const long long* labels, c
   SmoothCe a = {logits, labels, nullptr, const_cast<float*>(lse), nullptr, dloss, dloss_rows, mean_cnt, dlogits, rows, cols, ld, ignore_index,
                 0.0, 0.0, 0.0};
   smooth_consts(a, eps);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == HERO_BF16) hipLaunchKernelGGL(smooth_ce_bwd_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(smooth_ce_bwd_kernel<float>, dim3(rows), dim3(256), 0, s, a);
-  return check_launch("hero_smooth_ce_bwd");
+  return by_dtype(dtype, "hero_smooth_ce_bwd", [&](auto tag) {
+    hipLaunchKernelGGL(smooth_ce_bwd_kernel<typename decltype(tag)::type>, dim3(rows), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  });
 }

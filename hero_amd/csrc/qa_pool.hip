@@ -8,16 +8,17 @@
 // pooled vector per frame).  Written as tensor ops that is 2 matvecs, 2 mask_logits, 2 softmaxes and 2 einsums over
 // a [Nv, A, L, D] slice copy - and their backward.
 //
-// One workgroup (4 waves) owns one video: the A * L rows of a video are all that either softmax couples.
-//   pass 1  one wave per row: both dot products from ONE read of the row (forward: w_qa, w_se; backward: dqa[a],
-//           dse[l]), DPP butterfly sums, results into two LDS tables of A * L floats (<= 8 KB each)
-//   pass 2  the two softmaxes (or their backward) in the LDS: over l one wave per copy, over a one thread per frame
-//   pass 3  one thread per 4 columns walks the rows again (L2-resident: <= 8 * 256 rows of <= 4 KB): both weighted
-//           sums / the row gradient and both parameter-gradient shares, 16-byte accesses, A independent loads in
-//           flight per frame.  The A accumulators are a fully unrolled register array (A <= 8): no scratch.
+// One workgroup (4 waves) owns one video: the A * L rows of a video are all that either softmax couples.  The passes
+// are those of pool_rows.h, with what two tables change:
+//   pass 1  both dot products from ONE read of the row (forward: w_qa, w_se; backward: dqa[a], dse[l]) into two LDS
+//           tables of A * L floats (<= 8 KB each)
+//   pass 2  over l one wave per copy (pool_rows.h), over a one thread per frame (here)
+//   pass 3  <= 8 * 256 rows of <= 4 KB: both weighted sums / the row gradient and both parameter-gradient shares, A
+//           independent loads in flight per frame.  The A accumulators are a fully unrolled register array (A <= 8):
+//           no scratch.
 // Parameter gradients leave as one [D] share per video; the caller folds them in a fixed order (hero_colsum), so
-// there is no floating-point atomic and two runs give the same bits.
-#include "common.h"
+// there is no floating-point atomic and two runs give the same bits.  The arithmetic is pool_rows.h's VSM = false.
+#include "pool_rows.h"
 
 namespace hero {
 namespace {
@@ -41,13 +42,6 @@ struct QaPoolArgs {
   int A, L, Lt, D;
 };
 
-__device__ __forceinline__ float dot4(float4 a, float4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
-__device__ __forceinline__ void fma4(float4& acc, float s, float4 v) {
-  acc.x = fmaf(s, v.x, acc.x); acc.y = fmaf(s, v.y, acc.y); acc.z = fmaf(s, v.z, acc.z); acc.w = fmaf(s, v.w, acc.w);
-}
-__device__ __forceinline__ float4 ldf4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void stf4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
 template <typename T>
 __global__ __launch_bounds__(256) void qa_pool_fwd_kernel(QaPoolArgs a) {
   __shared__ float t_qa[QA_MAX_A * QA_MAX_L];        // scores, then attention, [a * L + l]
@@ -60,40 +54,25 @@ __global__ __launch_bounds__(256) void qa_pool_fwd_kernel(QaPoolArgs a) {
 
   for (int r = wave; r < rows; r += 4) {             // pass 1: r = ai * L + l
     const int ai = r / L, l = r - ai * L;
-    const T* row = x + ai * seq + (size_t)l * D;
-    float sq = 0.f, ss = 0.f;
-    for (int d = lane * 4; d < D; d += 256) {
-      const float4 xv = V4<T>::ld(row + d);
-      sq += dot4(xv, ldf4(a.w_qa + d));
-      ss += dot4(xv, ldf4(a.w_se + d));
-    }
-    sq = wave_sum(sq);
-    ss = wave_sum(ss);
+    const float* const w[2] = {a.w_qa, a.w_se};
+    float s[2];
+    row_dots<T, 2>(x + ai * seq + (size_t)l * D, w, D, s);
     if (lane == 0) {
-      const float m = mask[r];
-      t_qa[r] = sq * m + (1.f - m) * -10000.f;       // mask_logits, model/modeling_utils.py:42-43
-      t_se[r] = ss * m + (1.f - m) * -10000.f;
+      t_qa[r] = s[0];
+      t_se[r] = s[1];
     }
   }
   __syncthreads();
 
-  for (int ai = wave; ai < A; ai += 4) {             // pass 2a: softmax over the frames of one copy
-    float* s = t_qa + ai * L;
+  for (int ai = wave; ai < A; ai += 4)               // pass 2a: mask_logits and softmax over the frames of one copy
+    softmax_row<false>(t_qa + ai * L, mask + ai * L, a.att_qa + (size_t)v * rows + ai * L, L);
+  for (int l = threadIdx.x; l < L; l += 256) {       // pass 2b: the same over the copies of one frame, one thread each
     float mx = -3.0e38f;
-    for (int l = lane; l < L; l += 64) mx = fmaxf(mx, s[l]);
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int l = lane; l < L; l += 64) sum += expf(s[l] - mx);
-    sum = wave_sum(sum);
-    for (int l = lane; l < L; l += 64) {
-      const float p = expf(s[l] - mx) / sum;
-      s[l] = p;
-      a.att_qa[(size_t)v * rows + ai * L + l] = p;
+    for (int ai = 0; ai < A; ++ai) {
+      const float sc = mask_logits(t_se[ai * L + l], mask[ai * L + l]);
+      t_se[ai * L + l] = sc;
+      mx = fmaxf(mx, sc);
     }
-  }
-  for (int l = threadIdx.x; l < L; l += 256) {       // pass 2b: softmax over the copies of one frame
-    float mx = -3.0e38f;
-    for (int ai = 0; ai < A; ++ai) mx = fmaxf(mx, t_se[ai * L + l]);
     float sum = 0.f;
     for (int ai = 0; ai < A; ++ai) sum += expf(t_se[ai * L + l] - mx);
     for (int ai = 0; ai < A; ++ai) {                 // a masked frame: A equal scores -> exactly 1 / A each
@@ -143,32 +122,22 @@ __global__ __launch_bounds__(256) void qa_pool_bwd_kernel(QaPoolArgs a) {
 
   for (int r = wave; r < rows; r += 4) {             // pass 1: d att_qa[a,l] = <dqa[a], x>, d att_se[a,l] = <dse[l], x>
     const int ai = r / L, l = r - ai * L;
-    const T* row = x + ai * seq + (size_t)l * D;
-    float sq = 0.f, ss = 0.f;
-    for (int d = lane * 4; d < D; d += 256) {
-      const float4 xv = V4<T>::ld(row + d);
-      sq += dot4(xv, ldf4(dqa + (size_t)ai * D + d));
-      ss += dot4(xv, ldf4(dse + (size_t)l * D + d));
-    }
-    sq = wave_sum(sq);
-    ss = wave_sum(ss);
+    const float* const g[2] = {dqa + (size_t)ai * D, dse + (size_t)l * D};
+    float s[2];
+    row_dots<T, 2>(x + ai * seq + (size_t)l * D, g, D, s);
     if (lane == 0) {
-      t_qa[r] = sq;
-      t_se[r] = ss;
+      t_qa[r] = s[0];
+      t_se[r] = s[1];
     }
   }
   __syncthreads();
 
-  for (int ai = wave; ai < A; ai += 4) {             // pass 2a: softmax backward over l, times d mask_logits / ds = mask
-    float dot = 0.f;
-    for (int l = lane; l < L; l += 64) dot += att_qa[ai * L + l] * t_qa[ai * L + l];
-    dot = wave_sum(dot);
-    for (int l = lane; l < L; l += 64) t_qa[ai * L + l] = att_qa[ai * L + l] * (t_qa[ai * L + l] - dot) * mask[ai * L + l];
-  }
-  for (int l = threadIdx.x; l < L; l += 256) {       // pass 2b: softmax backward over a
+  for (int ai = wave; ai < A; ai += 4)               // pass 2a: softmax backward over l
+    softmax_bwd_row(t_qa + ai * L, att_qa + ai * L, mask + ai * L, L);
+  for (int l = threadIdx.x; l < L; l += 256) {       // pass 2b: softmax backward over a, one thread each
     float dot = 0.f;
     for (int ai = 0; ai < A; ++ai) dot += att_se[ai * L + l] * t_se[ai * L + l];
-    for (int ai = 0; ai < A; ++ai) t_se[ai * L + l] = att_se[ai * L + l] * (t_se[ai * L + l] - dot) * mask[ai * L + l];
+    for (int ai = 0; ai < A; ++ai) t_se[ai * L + l] = softmax_bwd(att_se[ai * L + l], t_se[ai * L + l], dot, mask[ai * L + l]);
   }
   __syncthreads();
 
@@ -202,12 +171,7 @@ __global__ __launch_bounds__(256) void qa_pool_bwd_kernel(QaPoolArgs a) {
     stf4(a.dw_se + (size_t)v * D + d, dws);
   }
   // the QA-token rows behind the frames take no gradient from this head: written as zeros, the caller does no memset
-  const int tail = (Lt - L) * D;                     // contiguous per copy, a multiple of 4 elements
-  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int ai = 0; ai < A; ++ai) {
-    T* p = dx + ai * seq + (size_t)L * D;
-    for (int i = threadIdx.x * 4; i < tail; i += 1024) V4<T>::st(p + i, z);
-  }
+  for (int ai = 0; ai < A; ++ai) zero_rows(dx + ai * seq + (size_t)L * D, (Lt - L) * D);   // contiguous per copy
 }
 
 int qa_check(const char* what, const void* x, int Nv, int A, int L, int Lt, int D) {
@@ -233,9 +197,9 @@ extern "C" int hero_qa_pool_fwd(const void* x, const float* mask, const float* w
   a.x = x; a.mask = mask; a.w_qa = w_qa; a.w_se = w_se;
   a.qa_pooled = qa_pooled; a.se_pooled = se_pooled; a.att_qa = att_qa; a.att_se = att_se;
   a.A = A; a.L = L; a.Lt = Lt; a.D = D;
-  if (dtype == HERO_F32) hipLaunchKernelGGL((qa_pool_fwd_kernel<float>), dim3(Nv), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  else hipLaunchKernelGGL((qa_pool_fwd_kernel<bf16_t>), dim3(Nv), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  return check_launch("hero_qa_pool_fwd");
+  return by_dtype(dtype, "hero_qa_pool_fwd", [&](auto tag) {
+    hipLaunchKernelGGL((qa_pool_fwd_kernel<typename decltype(tag)::type>), dim3(Nv), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  });
 }
 
 extern "C" int hero_qa_pool_bwd(const void* x, const float* mask, const float* w_qa, const float* w_se, const float* att_qa, const float* att_se,
@@ -250,7 +214,7 @@ extern "C" int hero_qa_pool_bwd(const void* x, const float* mask, const float* w
   a.att_qa = const_cast<float*>(att_qa); a.att_se = const_cast<float*>(att_se);
   a.dqa = dqa; a.dse = dse; a.dx = dx; a.dw_qa = dw_qa; a.dw_se = dw_se;
   a.A = A; a.L = L; a.Lt = Lt; a.D = D;
-  if (dtype == HERO_F32) hipLaunchKernelGGL((qa_pool_bwd_kernel<float>), dim3(Nv), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  else hipLaunchKernelGGL((qa_pool_bwd_kernel<bf16_t>), dim3(Nv), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  return check_launch("hero_qa_pool_bwd");
+  return by_dtype(dtype, "hero_qa_pool_bwd", [&](auto tag) {
+    hipLaunchKernelGGL((qa_pool_bwd_kernel<typename decltype(tag)::type>), dim3(Nv), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  });
 }

@@ -589,14 +589,11 @@ extern "C" int hero_gather_rows(const void* a, const void* b, const int32_t* idx
   HERO_REQUIRE(idx && out, "hero_gather_rows: null pointer");
   HERO_REQUIRE(cols > 0 && cols % 4 == 0, "hero_gather_rows: cols (%d) must be a multiple of 4", cols);
   if (rows <= 0) return HERO_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int grid = grid_for((size_t)rows * (cols >> 2));
-  if (dtype == HERO_F32)
-    hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)a, (const float*)b, idx, (float*)out, rows, cols);
-  else if (dtype == HERO_BF16)
-    hipLaunchKernelGGL(gather_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)a, (const bf16_t*)b, idx, (bf16_t*)out, rows, cols);
-  else { set_error("hero_gather_rows: bad dtype %d", dtype); return HERO_ERR_ARG; }
-  return check_launch("hero_gather_rows");
+  return by_dtype(dtype, "hero_gather_rows", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(grid_for((size_t)rows * (cols >> 2))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       (const T*)a, (const T*)b, idx, (T*)out, rows, cols);
+  });
 }
 
 extern "C" int hero_inverse_first(const int32_t* idx, int n, int32_t* inv, int na, int nb, hero_stream_t stream) {
@@ -614,14 +611,11 @@ extern "C" int hero_csr_gather_sum(const void* src, const int32_t* offsets, cons
   HERO_REQUIRE(src && offsets && out, "hero_csr_gather_sum: null pointer");
   HERO_REQUIRE(cols > 0 && cols % 4 == 0, "hero_csr_gather_sum: cols (%d) must be a multiple of 4", cols);
   if (rows <= 0) return HERO_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int grid = grid_for((size_t)rows * (cols >> 2));
-  if (dtype == HERO_F32)
-    hipLaunchKernelGGL(csr_gather_sum_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)src, offsets, entries, (float*)out, rows, cols);
-  else if (dtype == HERO_BF16)
-    hipLaunchKernelGGL(csr_gather_sum_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)src, offsets, entries, (bf16_t*)out, rows, cols);
-  else { set_error("hero_csr_gather_sum: bad dtype %d", dtype); return HERO_ERR_ARG; }
-  return check_launch("hero_csr_gather_sum");
+  return by_dtype(dtype, "hero_csr_gather_sum", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(csr_gather_sum_kernel<T>, dim3(grid_for((size_t)rows * (cols >> 2))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       (const T*)src, offsets, entries, (T*)out, rows, cols);
+  });
 }
 
 extern "C" int hero_scatter_add_rows(const void* src, const int32_t* idx, void* dst_a, void* dst_b, int rows, int cols,
@@ -673,10 +667,10 @@ extern "C" int hero_scatter_add_sorted(const void* src, const int32_t* idx, cons
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nblk = (rows + SEG_B - 1) / SEG_B, grid = (nblk + 3) / 4, skip = skip_idx >= 0 ? skip_idx : -1;
   float* part = static_cast<float*>(workspace);
-  if (src_dtype == HERO_BF16) hipLaunchKernelGGL((scatter_sorted_kernel<bf16_t, 3>), dim3(grid), dim3(256), 0, s, (const bf16_t*)src, idx, order, dst, part, rows, cols, skip);
-  else if (src_dtype == HERO_F32) hipLaunchKernelGGL((scatter_sorted_kernel<float, 3>), dim3(grid), dim3(256), 0, s, (const float*)src, idx, order, dst, part, rows, cols, skip);
-  else { set_error("hero_scatter_add_sorted: bad dtype %d", src_dtype); return HERO_ERR_ARG; }
-  int rc = check_launch("hero_scatter_add_sorted");
+  const int rc = by_dtype(src_dtype, "hero_scatter_add_sorted", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((scatter_sorted_kernel<T, 3>), dim3(grid), dim3(256), 0, s, (const T*)src, idx, order, dst, part, rows, cols, skip);
+  });
   if (rc) return rc;
   hipLaunchKernelGGL(scatter_sorted_fold_kernel, dim3(grid), dim3(256), 0, s, idx, order, dst, part, rows, cols, skip);
   return check_launch("hero_scatter_add_sorted(fold)");
@@ -698,12 +692,11 @@ extern "C" int hero_cast(const void* src, void* dst, size_t n, int sd, int dd, h
 extern "C" int hero_transpose_cast(const float* src, void* dst, int rows, int cols, int ldd, int dst_dtype, hero_stream_t stream) {
   HERO_REQUIRE(src && dst, "hero_transpose_cast: null pointer");
   if (rows <= 0 || cols <= 0) return HERO_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((cols + 31) / 32, (rows + 31) / 32);
-  if (dst_dtype == HERO_BF16) hipLaunchKernelGGL(transpose_cast_kernel<bf16_t>, grid, dim3(256), 0, s, src, (bf16_t*)dst, rows, cols, ldd);
-  else if (dst_dtype == HERO_F32) hipLaunchKernelGGL(transpose_cast_kernel<float>, grid, dim3(256), 0, s, src, (float*)dst, rows, cols, ldd);
-  else { set_error("hero_transpose_cast: bad dtype %d", dst_dtype); return HERO_ERR_ARG; }
-  return check_launch("hero_transpose_cast");
+  return by_dtype(dst_dtype, "hero_transpose_cast", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(transpose_cast_kernel<T>, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       src, (T*)dst, rows, cols, ldd);
+  });
 }
 
 extern "C" int hero_copy_multi(const HeroCopyDesc* descs, const int32_t* tile_desc, const int32_t* tile_index, int n_tiles,
@@ -718,36 +711,30 @@ extern "C" int hero_relu_bwd(const void* dy, const void* y, void* dx, size_t n, 
   HERO_REQUIRE(dy && y && dx, "hero_relu_bwd: null pointer");
   HERO_REQUIRE(n % 4 == 0, "hero_relu_bwd: n must be a multiple of 4");
   if (n == 0) return HERO_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int grid = grid_for(n >> 2);
-  if (dtype == HERO_F32) hipLaunchKernelGGL(relu_bwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)dy, (const float*)y, (float*)dx, n);
-  else if (dtype == HERO_BF16) hipLaunchKernelGGL(relu_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)y, (bf16_t*)dx, n);
-  else { set_error("hero_relu_bwd: bad dtype %d", dtype); return HERO_ERR_ARG; }
-  return check_launch("hero_relu_bwd");
+  return by_dtype(dtype, "hero_relu_bwd", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(relu_bwd_kernel<T>, dim3(grid_for(n >> 2)), dim3(256), 0, static_cast<hipStream_t>(stream), (const T*)dy, (const T*)y, (T*)dx, n);
+  });
 }
 
 extern "C" int hero_gelu_bwd(const void* dy, const void* u, void* dx, size_t n, int dtype, hero_stream_t stream) {
   HERO_REQUIRE(dy && u && dx, "hero_gelu_bwd: null pointer");
   HERO_REQUIRE(n % 4 == 0, "hero_gelu_bwd: n must be a multiple of 4");
   if (n == 0) return HERO_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int grid = grid_for(n >> 2);
-  if (dtype == HERO_F32) hipLaunchKernelGGL(gelu_bwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)dy, (const float*)u, (float*)dx, n);
-  else if (dtype == HERO_BF16) hipLaunchKernelGGL(gelu_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)u, (bf16_t*)dx, n);
-  else { set_error("hero_gelu_bwd: bad dtype %d", dtype); return HERO_ERR_ARG; }
-  return check_launch("hero_gelu_bwd");
+  return by_dtype(dtype, "hero_gelu_bwd", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(gelu_bwd_kernel<T>, dim3(grid_for(n >> 2)), dim3(256), 0, static_cast<hipStream_t>(stream), (const T*)dy, (const T*)u, (T*)dx, n);
+  });
 }
 
 extern "C" int hero_add(const void* a, const void* b, void* y, size_t n, int dtype, hero_stream_t stream) {
   HERO_REQUIRE(a && b && y, "hero_add: null pointer");
   HERO_REQUIRE(n % 4 == 0, "hero_add: n must be a multiple of 4");
   if (n == 0) return HERO_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int grid = grid_for(n >> 2);
-  if (dtype == HERO_F32) hipLaunchKernelGGL(add_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)a, (const float*)b, (float*)y, n);
-  else if (dtype == HERO_BF16) hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)y, n);
-  else { set_error("hero_add: bad dtype %d", dtype); return HERO_ERR_ARG; }
-  return check_launch("hero_add");
+  return by_dtype(dtype, "hero_add", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(add_kernel<T>, dim3(grid_for(n >> 2)), dim3(256), 0, static_cast<hipStream_t>(stream), (const T*)a, (const T*)b, (T*)y, n);
+  });
 }
 
 template <typename TO>
@@ -766,12 +753,10 @@ extern "C" int hero_fold_slabs(const float* slabs, int n_slabs, size_t stride, v
   HERO_REQUIRE(slabs && out && n_slabs >= 1, "hero_fold_slabs: null pointer / no slab");
   HERO_REQUIRE(n % 4 == 0 && stride % 4 == 0 && (((uintptr_t)slabs | (uintptr_t)out) & 7) == 0, "hero_fold_slabs: n and stride must be multiples of 4, pointers aligned");
   if (n == 0) return HERO_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int grid = grid_for(n >> 2);
-  if (out_dtype == HERO_F32) hipLaunchKernelGGL(fold_slabs_kernel<float>, dim3(grid), dim3(256), 0, s, slabs, n_slabs, stride, (float*)out, n >> 2);
-  else if (out_dtype == HERO_BF16) hipLaunchKernelGGL(fold_slabs_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, slabs, n_slabs, stride, (bf16_t*)out, n >> 2);
-  else { set_error("hero_fold_slabs: bad dtype %d", out_dtype); return HERO_ERR_ARG; }
-  return check_launch("hero_fold_slabs");
+  return by_dtype(out_dtype, "hero_fold_slabs", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(fold_slabs_kernel<T>, dim3(grid_for(n >> 2)), dim3(256), 0, static_cast<hipStream_t>(stream), slabs, n_slabs, stride, (T*)out, n >> 2);
+  });
 }
 
 extern "C" int hero_sumsq(const float* g, size_t n, float* sumsq, float* workspace, hero_stream_t stream) {

@@ -275,8 +275,7 @@ extern "C" int hero_sample_select(const void* logits, float* cum, int* fin, int*
   HERO_REQUIRE((((uintptr_t)seed_dev) & 7) == 0, "hero_sample_select: the seed word must be 8-byte aligned");
   const SampleSel a = {logits, seed_dev, pos_dev, cum, fin, len, ids, last, kept, pos, N, S, V, ld, Tcap, eos, top_k,
                        rows_vec4(logits, ld, dtype), inv_temperature, top_p};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HERO_F32) hipLaunchKernelGGL((sample_rows_kernel<float>), dim3(N * S), dim3(SM_NT), 0, st, a);
-  else hipLaunchKernelGGL((sample_rows_kernel<bf16_t>), dim3(N * S), dim3(SM_NT), 0, st, a);
-  return check_launch("hero_sample_select");
+  return by_dtype(dtype, "hero_sample_select", [&](auto tag) {
+    hipLaunchKernelGGL((sample_rows_kernel<typename decltype(tag)::type>), dim3(N * S), dim3(SM_NT), 0, static_cast<hipStream_t>(stream), a);
+  });
 }

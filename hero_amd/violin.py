@@ -10,7 +10,7 @@ from torch.nn import functional as F
 from . import _lib as L
 from . import functional as HF
 
-MAX_L, MAX_LT, MAX_D, MAX_K = 256, 512, 1024, 2048         # hero_amd/csrc/violin.hip
+MAX_L, MAX_LT, MAX_D, MAX_K = 256, 512, 1024, 2048         # hero_amd/csrc/pool.hip (FP_MAX_*), hero_amd/csrc/violin.hip (BCE_MAX_K)
 
 
 def _f32c(t):
