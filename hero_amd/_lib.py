@@ -29,7 +29,7 @@ EXPORTS = [
     "hero_dec_attention_in_envelope", "hero_dec_attention_fwd", "hero_dec_attention_bwd", "hero_smooth_ce_fwd", "hero_smooth_ce_bwd",
     "hero_dec_attention_row_in_envelope", "hero_dec_attention_row", "hero_dec_attention_step",
     "hero_dec_attention_row_grouped", "hero_dec_attention_step_beam", "hero_beam_in_envelope", "hero_beam_select",
-    "hero_sample_in_envelope", "hero_sample_select",
+    "hero_sample_in_envelope", "hero_sample_select", "hero_caption_in_envelope", "hero_caption_score",
     "hero_topk_rows", "hero_st_ed_probs", "hero_moment_topk", "hero_moment_nms", "hero_first_hit",
     "hero_collate_subs", "hero_collate_clip_mask", "hero_collate_frame_map", "hero_collate_gather_feats", "hero_derive_multi",
     "hero_comm_available", "hero_comm_unique_id", "hero_comm_init", "hero_comm_destroy", "hero_comm_rank", "hero_comm_world",
@@ -295,6 +295,8 @@ def lib():
         L.hero_beam_select.argtypes = [C.c_void_p] * 9 + [C.c_int] * 8 + [C.c_void_p]
         L.hero_sample_in_envelope.argtypes = [C.c_int] * 3
         L.hero_sample_select.argtypes = [C.c_void_p] * 9 + [C.c_int] * 7 + [C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p]
+        L.hero_caption_in_envelope.argtypes = [C.c_int] * 2
+        L.hero_caption_score.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p]
         L.hero_smooth_ce_fwd.argtypes = [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_double, C.c_longlong, C.c_void_p]
         L.hero_smooth_ce_bwd.argtypes = [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_double, C.c_longlong, C.c_void_p]
         L.hero_comm_unique_id.argtypes = [C.c_void_p]

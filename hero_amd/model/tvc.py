@@ -703,14 +703,16 @@ class TvcGenerator(object):
         return self._decode((), encoder_outputs, enc_mask, make)["out"]
 
     @torch.no_grad()
-    def greedy_decode(self, batch, encoder_outputs=None):
-        """encoder_outputs: what model.encode(batch) returned, when the caller already has it."""
+    def greedy_decode(self, batch, encoder_outputs=None, as_tensor=False):
+        """encoder_outputs: what model.encode(batch) returned, when the caller already has it.  as_tensor: the [N, max_step] id rows
+        as a device tensor of their own, not cut at `eos`, without a host transfer (hero_amd.caption scores them there)."""
         model = self.model
         if encoder_outputs is None:
             encoder_outputs = model.encode(batch)
         enc_mask = batch["cap_attn_mask"]
         if self.kv_cache:
-            return [self.cut_eos(ids) for ids in self._decode_cached(encoder_outputs, enc_mask).tolist()]
+            out = self._decode_cached(encoder_outputs, enc_mask)
+            return out.clone() if as_tensor else [self.cut_eos(ids) for ids in out.tolist()]
         N, dev = enc_mask.size(0), encoder_outputs.device
         # the buffer is padded with the pad id, whose embedding row and positions the causal mask hides from every earlier step
         input_ids = torch.full((N, self.max_step), model.v_encoder.f_encoder.embeddings.padding_idx, dtype=torch.long, device=dev)
@@ -729,7 +731,7 @@ class TvcGenerator(object):
                 scores = model._scores_torch(states[:, -1])
             last_out = scores[:, :model.config.f_config.vocab_size].float().argmax(dim=-1)
             output_ids[:, step] = last_out
-        return [self.cut_eos(ids) for ids in output_ids.tolist()]
+        return output_ids if as_tensor else [self.cut_eos(ids) for ids in output_ids.tolist()]
 
     # ---- beam search --------------------------------------------------------------------------------------------------------
     def _beam_state(self, encoder_outputs, enc_mask, beam_size):
@@ -754,16 +756,19 @@ class TvcGenerator(object):
         model.reorder_decode_state(state, rows)
         last.copy_(nxt)
 
-    def _pick(self, tb, N, per, length_penalty, return_all, return_scores):
+    def _pick(self, tb, N, per, length_penalty, return_all, return_scores, as_tensor=False):
         """Of the `per` rows of each of the N captions the one with the largest  cum / max(len, 1) ** length_penalty  - a stable
         sort: the lower row wins a tie - or, with return_all, every row in row order; ids and the fp32 scores' bits come to the
-        host in ONE int32 transfer.  -> list of id lists cut at `eos`[, list of their scores]."""
+        host in ONE int32 transfer.  -> list of id lists cut at `eos`[, list of their scores].  as_tensor: the same rows as a device
+        tensor [rows, max_step], not cut (a finished row carries `eos` to the end)[, their scores as a device tensor]: no transfer."""
         norm = tb.cum.view(N, per) / tb.len.view(N, per).clamp(min=1).to(torch.float32) ** float(length_penalty)
         if return_all:
             rows, picked = torch.arange(N * per, device=norm.device), norm.reshape(-1, 1)
         else:
             best = torch.sort(norm, dim=1, descending=True, stable=True).indices[:, :1]
             rows, picked = torch.arange(N, device=best.device) * per + best[:, 0], norm.gather(1, best)
+        if as_tensor:
+            return (tb.ids[rows], picked.reshape(-1)) if return_scores else tb.ids[rows]
         packed = torch.cat([tb.ids[rows].to(torch.int32), picked.contiguous().view(torch.int32)], dim=1).cpu()
         ids = [self.cut_eos(r) for r in packed[:, :-1].tolist()]
         if return_scores:
@@ -771,7 +776,8 @@ class TvcGenerator(object):
         return ids
 
     @torch.no_grad()
-    def beam_decode(self, batch, beam_size, length_penalty=1.0, encoder_outputs=None, return_scores=False, stop_at_eos=False):
+    def beam_decode(self, batch, beam_size, length_penalty=1.0, encoder_outputs=None, return_scores=False, stop_at_eos=False,
+                    as_tensor=False):
         """Beam search over the incremental decode (needs kv_cache=True): max_step steps of decode_step + selection for
         N * beam_size rows, no early exit - a finished beam carries `eos` at an unchanged score - then per caption the beam with
         the largest  cum / max(len, 1) ** length_penalty  (the lower beam among equals), ONE host transfer, and the ids cut at
@@ -779,7 +785,8 @@ class TvcGenerator(object):
         replicated; use_graph replays the step, captured once per (N, beam, Lv, max_step) into the graph table it shares with the
         greedy steps.  stop_at_eos: leave the loop once every beam of every caption has finished
         (one word read from the device after every `check_every` steps, outside the captured step); the result is that of the
-        full-length run.  -> list of id lists[, list of the picked beams' scores]."""
+        full-length run.  -> list of id lists[, list of the picked beams' scores]; as_tensor: the picked rows [N, max_step] as a
+        device tensor, not cut at `eos`, without the host transfer."""
         if not self.kv_cache:
             raise ValueError("TvcGenerator: beam_decode runs on the incremental decode step, it needs kv_cache=True")
         if beam_size < 1:
@@ -792,7 +799,7 @@ class TvcGenerator(object):
             state, last = self._beam_state(encoder_outputs, enc_mask, beam_size)
             return dict(state=state, last=last, step=lambda: self._beam_step(state, last))
         state = self._decode(("beam", beam_size), encoder_outputs, enc_mask, make, stop_at_eos=stop_at_eos)["state"]
-        return self._pick(state.tables, state.N, beam_size, length_penalty, False, return_scores)
+        return self._pick(state.tables, state.N, beam_size, length_penalty, False, return_scores, as_tensor)
 
     # ---- sampling -----------------------------------------------------------------------------------------------------------
     def _sample_step(self, state, last, seed, params):
@@ -815,7 +822,7 @@ class TvcGenerator(object):
 
     @torch.no_grad()
     def sample_decode(self, batch, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=1.0,
-                      return_all=False, return_scores=False, stop_at_eos=False, encoder_outputs=None):
+                      return_all=False, return_scores=False, stop_at_eos=False, encoder_outputs=None, as_tensor=False):
         """Sampled decoding over the incremental decode (needs kv_cache=True): n_samples independent captions per clip, drawn token
         by token from the step's scores under temperature, then top-k (0 = off), then top-p (>= 1 = off); the draw is a
         counter-based Gumbel-max, a function of (seed, position, row, token) alone.  The state is the beam state: N * n_samples
@@ -826,7 +833,8 @@ class TvcGenerator(object):
         On the kernels' route (n_samples within the beam envelope) the draw is hero_sample_select; use_graph replays the step,
         captured once per (N, samples, Lv, max_step, temperature, top_k, top_p) - the three are launch scalars of the captured
         kernel, the seed is a device word filled before the replays: a new seed does not recapture.  stop_at_eos as in
-        beam_decode.  top_k = 1 is greedy decoding."""
+        beam_decode.  top_k = 1 is greedy decoding.  as_tensor: the returned rows as a device tensor [N or N * n_samples, max_step],
+        not cut at `eos`, without the host transfer."""
         if not self.kv_cache:
             raise ValueError("TvcGenerator: sample_decode runs on the incremental decode step, it needs kv_cache=True")
         if n_samples < 1:
@@ -855,7 +863,7 @@ class TvcGenerator(object):
             else:
                 hit["seed"] = seed
         state = self._decode(("sample", n_samples) + params, encoder_outputs, enc_mask, make, prepare, stop_at_eos)["state"]
-        return self._pick(state.tables, state.N, n_samples, length_penalty, return_all, return_scores)
+        return self._pick(state.tables, state.N, n_samples, length_penalty, return_all, return_scores, as_tensor)
 
     def cut_eos(self, ids):
         out_ids = []

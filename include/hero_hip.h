@@ -55,6 +55,8 @@ const char* hero_last_error(void);
  * cache read through an ancestry table) were ADDED the same way.
  * Still 3: hero_sample_select and hero_sample_in_envelope (the sampling step of the captioning decode: temperature, top-k,
  * top-p, a Gumbel-max draw) were ADDED the same way.
+ * Still 3: hero_caption_score and hero_caption_in_envelope (BLEU statistics, ROUGE-L and CIDEr-D of decoded id rows against
+ * packed reference tables) were ADDED the same way.
  * INTEGRATION.md section 2 lists the breaks per version. */
 #define HERO_ABI_VERSION 3
 int hero_abi_version(void);
@@ -457,6 +459,36 @@ int hero_sample_in_envelope(int dtype, int V, int Tcap);
 int hero_sample_select(const void* logits, float* cum, int32_t* fin, int32_t* len, int32_t* ids, int32_t* last, int32_t* kept,
                        const unsigned long long* seed_dev, const int* pos_dev, int pos, int N, int S, int V, int ld, int Tcap,
                        int eos, float inv_temperature, int top_k, float top_p, int dtype, hero_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Caption metrics (BLEU statistics, ROUGE-L, CIDEr-D of decoded id rows; inference / rewards)  */
+/* ------------------------------------------------------------------------------------------ */
+/* One launch scores M caption rows against the references of their clips, as the reference's     */
+/* eval/pycocoevalcap does on words (BleuScorer n = 4 "closest", Rouge, CiderScorer n = 4,         */
+/* sigma = 6), restated on integer tokens.  ids [M, ld] int32 (ids_int64 = 0) or int64 rows as the  */
+/* decoders leave them; the caption h of a row is what stands before its first `eos` within Tcap -  */
+/* what follows is junk and reaches no count.  clip [M] int32 is the row's clip in the reference    */
+/* tables `refs`, ONE packed device buffer built once by hero_amd.caption.CaptionRefs (layout: the  */
+/* head of hero_amd/csrc/caption_metrics.hip); a clip outside the tables gives zeros.  With the     */
+/* references r_1..r_R of the clip:                                                               */
+/*   stats [M, ld_stats] int32, columns 0..9:  correct[n] = sum over the distinct n-grams g of h of  */
+/*       min(count_h(g), max_r count_r(g));  guess[n] = max(0, |h| - n + 1), n = 1..4;  testlen =    */
+/*       |h|;  reflen = the |r| with the smallest (||r| - |h||, |r|).  Columns >= 10 are left alone. */
+/*   rouge [M] fp32:  p = max_r LCS(h, r) / max(|h|, 1), q = max_r LCS(h, r) / |r|,                   */
+/*       2.44 p q / (q + 1.44 p), or 0 when p or q is 0.  lcs [M] int32 (may be NULL): max_r LCS.    */
+/*   cider [M] fp32:  weights w(g) = count(g) * idf_n(g), idf_n(g) = log C - log max(1, df_n(g));     */
+/*       per reference and order  sum_g min(w_h(g), w_r(g)) w_r(g), divided by |w_h| |w_r| when both  */
+/*       are non-zero, times exp(-delta^2 / 72), delta = max(|h| - 1, 0) - max(|r| - 1, 0); the mean   */
+/*       over the four orders, summed over the references, / R, * 10.  Sums and norms in float64.     */
+/* n-grams are exact 64-bit keys of four 16-bit tokens: ids in [0, 65536) is a PRECONDITION (the      */
+/* decoders guarantee it).  No atomics, nothing allocated, nothing read on the host: two runs give    */
+/* the same bits and the launch can be captured.                                                    */
+/* Envelope: 1 <= V <= 65536, 1 <= Tcap <= 128, ld >= Tcap, ld_stats >= 10, 0 <= eos < V, M >= 1;     */
+/* refs 8-byte aligned.  Outside it HERO_ERR_ARG, no launch.                                         */
+/* Plain arguments: a backward-compatible addition, HERO_ABI_VERSION stays.                          */
+int hero_caption_in_envelope(int V, int Tcap);
+int hero_caption_score(const void* ids, int ids_int64, const int32_t* clip, const void* refs, int32_t* stats, float* rouge,
+                       float* cider, int32_t* lcs, int M, int ld, int ld_stats, int Tcap, int eos, int V, hero_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Row gathers / scatters                                                                      */
