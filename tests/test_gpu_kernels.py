@@ -6,6 +6,8 @@ import os
 import pytest
 import torch
 
+from tests.dropout_reference import ln_keep
+
 pytestmark = pytest.mark.gpu
 
 DT = [torch.float32, torch.bfloat16]
@@ -673,6 +675,7 @@ def _ln_case(HF, rows, cols, dtype, p_out=0.0, eps=1e-12):
     g, b = rnd(cols, seed=2) * 0.1 + 1, rnd(cols, seed=3) * 0.1
     dy = rnd(rows, cols, dtype=dtype, seed=4)
     drop = HF.RNG.make(p_out, True, x.device)
+    site, seed = HF.RNG.site, int(HF.RNG.seed_tensor(x.device).item())           # what `drop` draws from
     y, mean, rstd, _ = HF.k_ln_fwd(x, g, b, eps, dtype, rows, cols, drop=drop)
     xf = x.float().clone().requires_grad_(True)
     gf, bf = g.clone().requires_grad_(True), b.clone().requires_grad_(True)
@@ -681,6 +684,7 @@ def _ln_case(HF, rows, cols, dtype, p_out=0.0, eps=1e-12):
         y0, _, _, _ = HF.k_ln_fwd(x, g, b, eps, dtype, rows, cols)
         dropped = (y == 0) & (y0 != 0)
         assert 0.5 * p_out < dropped.float().mean().item() < 1.5 * p_out
+        assert torch.equal(dropped.cpu(), ~ln_keep(seed, site, drop.threshold16, rows, cols))      # ... and it IS the host draw's
         ref = ref * (~dropped).float() / (1.0 - p_out)
     close(y, ref, dtype, scale=3)
     ref.backward(dy.float())
