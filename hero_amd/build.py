@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libhero_hip.so")
-SOURCES = ["api.cpp", "comm.cpp", "gemm.hip", "gemm_ws.hip", "layernorm.hip", "attention.hip", "attention_mfma.hip", "attention_mfma_long.hip", "dec_attention.hip", "beam.hip", "sample.hip", "caption_metrics.hip", "rows.hip", "head.hip", "pool.hip", "qa_pool.hip", "violin.hip", "retrieval.hip", "postproc.hip", "loss.hip", "collate.hip", "probe.hip"]
+SOURCES = ["api.cpp", "comm.cpp", "gemm.hip", "gemm_ws.hip", "layernorm.hip", "attention.hip", "attention_mfma.hip", "attention_mfma_long.hip", "dec_attention.hip", "beam.hip", "sample.hip", "caption_metrics.hip", "rows.hip", "head.hip", "pool.hip", "qa_pool.hip", "violin.hip", "retrieval.hip", "postproc.hip", "loss.hip", "collate.hip", "pretrain_mask.hip", "probe.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]
 

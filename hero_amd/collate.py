@@ -12,6 +12,13 @@ Host half - same names, inputs and outputs as the reference, so a reference Data
     violin_collate / violin_eval_collate                 data/violin.py:118-141, 163-170 (pinned by tests/golden/case_violin.npz)
     tvc_st_ed_label, tvc_item, tvc_val_item              data/tvc.py:39-49, 100-138, 170-190, 246-265
     tvc_collate / tvc_val_collate / tvc_eval_collate     data/tvc.py:140-161, 192-218, 267-291 (+ `cap_frame_index`)
+    random_word, mlm_item, mlm_collate                   data/mlm.py:21-75, 93-131, 134-176
+    frame_mask, mfm_item, mfm_collate                    data/mfm.py:19-39, 55-97
+    random_reorder, fom_item, fom_collate / fom_eval_collate   data/fom.py:31-133
+    vsm_item, vsm_collate                                data/vsm.py:35-145
+        (the four pre-training tasks; their draws come from Python's `random` in the reference's order, so after
+        random.seed(s) a batch is the reference's bit for bit: tests/golden/case_pretrain_collate.npz.  The device half of the
+        MLM / MFM / FOM draws is hero_amd.pretrain_data.PretrainMasker.)
 They are written over LENGTH arrays (one allocation per output, no pad_sequence / per-row python tensors) and also
 return the handful of int32 length arrays (`batch["lengths"]`) from which the device half rebuilds every index tensor.
 
@@ -336,6 +343,217 @@ def tvc_val_collate(inputs, with_gts=True):
 def tvc_eval_collate(inputs):
     """TvcEvalDataset.collate (data/tvc.py:267-291): tvc_val_collate without the ground-truth texts."""
     return tvc_val_collate(inputs, with_gts=False)
+
+
+# ---- the four pre-training tasks (host half; device half: hero_amd/pretrain_data.py) -----------------------------------------
+def random_word(tokens, v_range, mask, mask_prob=0.15):
+    """BERT's token masking, data/mlm.py:21-58: one random.random() per token; a drawn token becomes `mask` (80 %), a token
+    of range(*v_range) (10 %, one random.choice) or stays (10 %); a sentence with no drawn token masks its first one.
+    `tokens` is changed in place.  Returns (tokens, labels) with -1 for the tokens that were not drawn.  (An empty token list
+    comes back empty; the reference raises on it.)"""
+    import random
+    labels = []
+    for i, tok in enumerate(tokens):
+        prob = random.random()
+        if prob < mask_prob:
+            prob /= mask_prob
+            if prob < 0.8:
+                tokens[i] = mask
+            elif prob < 0.9:
+                tokens[i] = random.choice(range(*v_range))
+            labels.append(tok)
+        else:
+            labels.append(-1)
+    if tokens and all(lab == -1 for lab in labels):
+        labels[0] = tokens[0]
+        tokens[0] = mask
+    return tokens, labels
+
+
+def _sub_context(sub_tokens, sub_idx, sub_ctx_len, n_subs, max_txt_len, skip=()):
+    """The tokens of subtitle `sub_idx` behind those of its `sub_ctx_len` predecessors, each cut at max_txt_len (-1: whole)."""
+    toks = []
+    for j in range(sub_idx - sub_ctx_len, sub_idx + 1):
+        if 0 <= j < n_subs and j not in skip:
+            toks.extend(sub_tokens[j] if max_txt_len == -1 else sub_tokens[j][:max_txt_len])
+    return toks
+
+
+def mlm_item(v_feat, sub2frames, sub_tokens, mask, v_range, cls_=0, mask_prob=0.15, sub_ctx_len=0, max_txt_len=-1):
+    """One video -> VideoMlmDataset.__getitem__'s list of (input_ids, frame feats, attn mask, txt_mask_tgt, txt_labels), one per
+    subtitle (data/mlm.py:93-131 with create_mlm_io, :67-75): rows start with CLS, the token mask is shifted right by the row's
+    frame slots, and a subtitle without frames gets one zero slot whose attention mask is 0.  The frame lists are used as
+    they are (the reference does not filter them here)."""
+    n_subs, out = len(sub2frames), []
+    for sub_idx, frames in sub2frames:
+        toks, labels = random_word(_sub_context(sub_tokens, sub_idx, sub_ctx_len, n_subs, max_txt_len), v_range, mask, mask_prob)
+        ids = torch.tensor([cls_] + toks, dtype=torch.long)
+        labels = torch.tensor([-1] + labels, dtype=torch.long)
+        slots = max(len(frames), 1)
+        attn = torch.ones(slots + ids.shape[0], dtype=torch.long)
+        if frames:
+            feats = v_feat[torch.as_tensor(frames)]
+        else:
+            feats = v_feat.new_zeros(1, v_feat.shape[1])
+            attn[0] = 0
+        tgt = torch.zeros(slots + ids.shape[0], dtype=torch.bool)
+        tgt[slots:] = labels != -1
+        out.append((ids, feats, attn, tgt, labels))
+    return out
+
+
+def mlm_collate(inputs):
+    """list of mlm_item lists -> the reference's batch (data/mlm.py:134-176): input_ids padded with 1, position_ids (1, L),
+    v_feat, attn_masks, gather_index, txt_mask_tgt [T, out_size] and the compact txt_labels in row-major order."""
+    rows = [r for it in inputs for r in it]
+    ntok = np.array([r[0].shape[0] for r in rows], dtype=np.int32)
+    vlen = np.array([r[1].shape[0] for r in rows], dtype=np.int32)
+    max_sl, max_vl, T = int(ntok.max()), int(vlen.max()), len(rows)
+    out_size = max(int(r[2].shape[0]) for r in rows)
+    gidx = torch.arange(out_size, dtype=torch.long).repeat(T, 1)
+    for r in range(T):
+        gidx[r, vlen[r]:vlen[r] + ntok[r]] = torch.arange(max_vl, max_vl + int(ntok[r]))
+    labels = _pad_rows([r[4] for r in rows], max_sl, -1, torch.long)
+    return {"input_ids": _pad_rows([r[0] for r in rows], max_sl, PAD_ID, torch.long),
+            "position_ids": torch.arange(max_sl, dtype=torch.long).unsqueeze(0),
+            "v_feat": _pad_feats([r[1] for r in rows], max_vl),
+            "attn_masks": _pad_rows([r[2] for r in rows], out_size, 0, torch.long),
+            "gather_index": gidx,
+            "txt_mask_tgt": _pad_rows([r[3] for r in rows], max(int(r[3].shape[0]) for r in rows), False, torch.bool),
+            "txt_labels": labels[labels != -1]}
+
+
+def frame_mask(mask_prob, n):
+    """_get_img_mask, data/mfm.py:19-25: one random.random() per frame, at least one frame (one random.choice)."""
+    import random
+    m = [random.random() < mask_prob for _ in range(n)]
+    if not any(m):
+        m[random.choice(range(n))] = True
+    return torch.tensor(m)
+
+
+def mfm_item(video, mask_prob=0.15):
+    """video: a video_item tuple -> MfmDataset.__getitem__'s (video, per-subtitle frame masks, clip mask) (data/mfm.py:55-74):
+    the subtitle masks are the clip mask at the subtitle's frames, [False] for a subtitle without frames."""
+    c_mask = frame_mask(mask_prob, video[3].shape[0])
+    masks = [c_mask[torch.as_tensor(frames)] if len(frames) else torch.zeros(1, dtype=torch.bool) for _, frames in video[6]]
+    return (video, masks, c_mask)
+
+
+def mfm_collate(inputs):
+    """list of mfm_item tuples -> the reference's batch (data/mfm.py:77-97): video_collate's keys with f_v_feats / c_v_feats
+    zeroed at the masked frames, f_v_masks [T, max_vl], c_v_masks [B, NF] and feat_targets (taken before the zeroing)."""
+    batch = video_collate([it[0] for it in inputs])
+    f_masks = [m for it in inputs for m in it[1]]
+    f_mask = _pad_rows(f_masks, max(int(m.shape[0]) for m in f_masks), False, torch.bool)
+    c_mask = _pad_rows([it[2] for it in inputs], batch["c_v_feats"].shape[1], False, torch.bool)
+    batch["feat_targets"] = batch["c_v_feats"][c_mask]
+    batch["f_v_feats"] = batch["f_v_feats"].masked_fill(f_mask.unsqueeze(-1), 0)
+    batch["c_v_feats"] = batch["c_v_feats"].masked_fill(c_mask.unsqueeze(-1), 0)
+    batch["f_v_masks"], batch["c_v_masks"] = f_mask, c_mask
+    return batch
+
+
+def random_reorder(pos_ids, p=0.15):
+    """data/fom.py:96-115: one random.random() per position, the drawn positions are permuted among themselves by one
+    random.shuffle.  Returns (order, target): order[pos] = the position shown there, target[shown position] = pos, -1 elsewhere."""
+    import random
+    selected = [i for i in range(len(pos_ids)) if random.random() < p]
+    shuffled = [pos_ids[i] for i in selected]
+    random.shuffle(shuffled)
+    order, target = list(pos_ids), [-1] * len(pos_ids)
+    for pos, shown in zip(selected, shuffled):
+        order[pos] = shown
+        target[shown] = pos
+    return order, target
+
+
+def fom_item(video, p=0.15):
+    """video: a video_item tuple -> FomDataset.__getitem__'s (video, orders, targets) (data/fom.py:31-47)."""
+    order, target = random_reorder(list(range(video[3].shape[0])), p)
+    return (video, torch.tensor(order, dtype=torch.long), torch.tensor(target, dtype=torch.long))
+
+
+def fom_collate(inputs):
+    """list of fom_item tuples -> the reference's batch (data/fom.py:50-93): video_collate's keys, shuffled_orders (identity
+    in the padding) and targets (-1 there) [B, NF], and for every pair i < j of reordered frames of a clip the flat rows
+    (i, j, j, i) in reordered_frame_idx with binary_targets (0 where the first of a pair has the larger target) - built
+    per clip from index arrays, not pair by pair."""
+    batch = video_collate([it[0] for it in inputs])
+    B, NF = batch["c_v_feats"].shape[:2]
+    orders = torch.arange(NF, dtype=torch.long).repeat(B, 1)
+    targets = torch.full((B, NF), -1, dtype=torch.long)
+    idx, binary = [], []
+    for b, (_, o, t) in enumerate(inputs):
+        orders[b, :o.shape[0]] = o
+        targets[b, :t.shape[0]] = t
+        tn = t.numpy()
+        pos = np.nonzero(tn != -1)[0]
+        i, j = np.triu_indices(pos.shape[0], 1)                  # pairs in (i, j) row-major order, the reference's loop order
+        pi, pj = b * NF + pos[i], b * NF + pos[j]
+        idx.append(np.stack([pi, pj, pj, pi], 1).reshape(-1))
+        ti, tj = tn[pos[i]], tn[pos[j]]
+        binary.append(np.stack([ti <= tj, tj <= ti], 1).reshape(-1))
+    batch["shuffled_orders"], batch["targets"] = orders, targets
+    batch["reordered_frame_idx"] = torch.from_numpy(np.concatenate(idx).astype(np.int64))
+    batch["binary_targets"] = torch.from_numpy(np.concatenate(binary).astype(np.int64))
+    return batch
+
+
+def fom_eval_collate(inputs):
+    """list of (vid, *fom_item tuple) -> fom_collate's batch plus `vids` (data/fom.py:125-132)."""
+    batch = fom_collate([tuple(it[1:]) for it in inputs])
+    batch["vids"] = [it[0] for it in inputs]
+    return batch
+
+
+def vsm_item(v_feat, sub2frames, sub_tokens, vid, query_per_video=5, sep=2, cls_=0, sub_ctx_len=0, max_txt_len=-1):
+    """One video -> VsmDataset.__getitem__'s (video, vid, ((query ids, query mask, vid, target), ...)) (data/vsm.py:35-117):
+    up to `query_per_video` subtitles with frames are drawn (one random.sample), leave every subtitle context and become
+    the queries `[cls] tokens` with target (st, ed) = (first frame, min(max(first + 1, last frame), nframes - 1)); the last
+    query is repeated up to query_per_video.  The frame lists are used as they are."""
+    import random
+    n_subs, nframes = len(sub2frames), v_feat.shape[0]
+    matched = [sub_idx for sub_idx, frames in sub2frames if frames]
+    picked = set(random.sample(matched, min(len(matched), query_per_video)))
+    ids, feats, masks, queries = [], [], [], []
+    for sub_idx, frames in sub2frames:
+        toks = [sep] + _sub_context(sub_tokens, sub_idx, sub_ctx_len, n_subs, max_txt_len, skip=picked)
+        if frames:
+            feats.append(v_feat[torch.as_tensor(frames)])
+            masks.append(torch.ones(len(frames) + len(toks), dtype=torch.long))
+            if sub_idx in picked:
+                q = sub_tokens[sub_idx] if max_txt_len == -1 else sub_tokens[sub_idx][:max_txt_len]
+                q = torch.tensor([cls_] + list(q), dtype=torch.long)
+                st, ed = frames[0], min(max(frames[0] + 1, frames[-1]), nframes - 1)
+                assert 0 <= st <= ed < nframes, "vsm_item: target frames (%d, %d) outside a video of %d frames" % (st, ed, nframes)
+                queries.append((q, torch.ones_like(q), vid, torch.tensor([st, ed], dtype=torch.long)))
+        else:
+            feats.append(v_feat.new_zeros(1, v_feat.shape[1]))
+            m = torch.ones(1 + len(toks), dtype=torch.long)
+            m[0] = 0
+            masks.append(m)
+        ids.append(torch.tensor(toks, dtype=torch.long))
+    while len(queries) < query_per_video:
+        queries.append(queries[-1])
+    return ((ids, feats, masks, v_feat, torch.ones(nframes, dtype=torch.long), n_subs, sub2frames), vid, tuple(queries))
+
+
+def vsm_collate(inputs):
+    """list of vsm_item tuples -> the reference's batch (data/vsm.py:120-145): video_collate's keys, q_vidx, the padded
+    queries query_input_ids / query_pos_ids (not clamped) / query_attn_masks, targets (Nq, 2) and vids."""
+    vids = [it[1] for it in inputs]
+    qs = [q for it in inputs for q in it[2]]
+    batch = video_collate([it[0] for it in inputs])
+    where = {v: i for i, v in enumerate(vids)}
+    batch["q_vidx"] = torch.tensor([where[q[2]] for q in qs], dtype=torch.long)
+    Lq = max(q[0].shape[0] for q in qs)
+    batch.update({"query_input_ids": _pad_rows([q[0] for q in qs], Lq, PAD_ID, torch.long),
+                  "query_pos_ids": torch.arange(Lq, dtype=torch.long).unsqueeze(0),
+                  "query_attn_masks": _pad_rows([q[1] for q in qs], Lq, 0, torch.long),
+                  "targets": torch.stack([q[3] for q in qs]),
+                  "vids": vids})
+    return batch
 
 
 def _lengths(num_subs, sub2frm, sub_nfrm, sub_ntok, n_frames):

@@ -1019,6 +1019,23 @@ def refresh_memo(sources=None, skip_outputs=()):
     return done
 
 
+def forget_memo(sources):
+    """Drop the memoised tensors derived - directly or through other entries - from one of `sources`.  For a caller that has
+    rewritten them so that the STRUCTURE of what is derived changes (hero_amd.pretrain_data.PretrainMasker: a new mask has
+    another number of set rows): the version counters it moved make the old entries unreachable for memo(), but a later
+    refresh_memo() would redo them in place and refuse the new shape.  Returns the number of entries dropped."""
+    src = {t.data_ptr() for t in sources}
+    n = 0
+    for e in sorted(_MEMO.values(), key=lambda e: e.seq):       # creation order is dependency order: one pass
+        if any(t.data_ptr() in src for t in e.sources):
+            if isinstance(e.out, torch.Tensor):
+                src.add(e.out.data_ptr())
+            if _MEMO.get(e.key) is e:
+                del _MEMO[e.key]
+                n += 1
+    return n
+
+
 def restamp_memo(entries):
     """Re-key memo entries (refresh_memo's return value, in its order) to the CURRENT version counters of their sources,
     keeping their creation numbers.  For a caller that has just refreshed these entries in place by other means - a replayed

@@ -917,6 +917,49 @@ int hero_collate_frame_map(const int32_t* vid_sub_off, const int32_t* sub_frm_of
                            int32_t* counts, int32_t* entries, int32_t* inverse, int B, int NF, int Lf, int fill,
                            hero_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* The random draws of the pre-training batches on the device (data/mlm.py:21-58 random_word,    */
+/* data/mfm.py:19-25 _get_img_mask, data/fom.py:96-115 random_reorder): one clean video batch ->   */
+/* the MLM, MFM and FOM batch.  Inputs are DeviceCollate's length slots (int32, device), the clean */
+/* f_sub_input_ids [T, max_sl] int64 and c_v_feats [B, NF, D] fp32; the clean tensors are only     */
+/* read.  seed_dev is one device word, site a per-task constant, threshold = floor(p * 2^32)       */
+/* (<= 2^32: p = 1 selects everything).  The draw is counter-based:                                */
+/*   base = splitmix64(*seed_dev ^ site * 0xD6E8FEB86659FD93), k0 / k1 = its low / high half,      */
+/*   element e of the padded layout: h = mix32(e ^ k0) (selected iff h < threshold), h2 =           */
+/*   mix32(e ^ k1); a bounded integer is lo + ((uint64)x * n >> 32).                                */
+/* hero_mlm_mask: e = r * max_sl + c, 1 <= c < sub_ntok[r].  A selected token becomes mask_id when */
+/*   h < threshold * 4 / 5, v_lo + (h2 * (v_hi - v_lo) >> 32) when h < threshold * 9 / 10, else    */
+/*   stays; a row with sub_ntok >= 2 and no selection selects column 1 (mask_id); column 0 of      */
+/*   every row becomes first_token.  ids_out [T, max_sl] int64; txt_mask_tgt [T, out_size] bytes   */
+/*   0 / 1 at column max(sub_nfrm[r], 1) + c; txt_labels [T * (max_sl - 1)] int64 = the original   */
+/*   ids of the selected tokens in row-major order, -1 behind the count; txt_mask_rows             */
+/*   [T * (max_sl - 1)] int32 = their flat indices into [T * out_size], -1 behind the count;       */
+/*   count [1] int32.  T <= 4096.                                                                  */
+/* hero_mfm_mask: e = b * NF + f, f < vid_nfrm[b]; a video with frames and no selection selects     */
+/*   frame (mix32(~b ^ k1) * vid_nfrm[b]) >> 32.  c_v_masks [B, NF], f_v_masks [T, max_vl] bytes   */
+/*   0 / 1 (slot k of a row = the k-th frame of its list inside the video, the walk of              */
+/*   hero_collate_gather_feats; empty slots 0); feat_targets [B * NF, D] = the selected rows of     */
+/*   c_v_feats in (b, f) order, zero rows behind the count; count [1] int32; c_v_feats_out          */
+/*   [B, NF, D] and f_v_feats_out [T, max_vl, D] = masked copies (selected rows zero).  row_src     */
+/*   [2 * B * NF + T * max_vl] int32 is scratch.  D % 4 == 0, B <= 4096, 16-byte aligned features.  */
+/* hero_fom_shuffle: e = b * NF + f, f < vid_nfrm[b], no at-least-one rule.  With the selected      */
+/*   positions P[0] < P[1] < ... and the same positions S[i] ordered by (h2, position):             */
+/*   shuffled_orders[b, P[i]] = S[i], targets[b, S[i]] = P[i]; elsewhere f and -1.  Both [B, NF]    */
+/*   int64.  NF <= 2048.                                                                           */
+/* No atomics, nothing allocated, nothing read on the host: two runs give the same bits and every   */
+/* launch can be captured.  Plain arguments: a backward-compatible addition, HERO_ABI_VERSION stays. */
+/* ------------------------------------------------------------------------------------------ */
+int hero_mlm_mask(const int64_t* input_ids, const int32_t* sub_nfrm, const int32_t* sub_ntok, const unsigned long long* seed_dev,
+                  unsigned long long site, unsigned long long threshold, long long mask_id, long long v_lo, long long v_hi,
+                  long long first_token, int64_t* ids_out, unsigned char* txt_mask_tgt, int64_t* txt_labels, int32_t* txt_mask_rows,
+                  int32_t* count, int T, int max_sl, int out_size, hero_stream_t stream);
+int hero_mfm_mask(const float* c_v_feats, const int32_t* vid_nfrm, const int32_t* vid_sub_off, const int32_t* sub_frm_off,
+                  const int32_t* sub_frm, const unsigned long long* seed_dev, unsigned long long site, unsigned long long threshold,
+                  unsigned char* c_v_masks, unsigned char* f_v_masks, float* feat_targets, int32_t* count, float* c_v_feats_out,
+                  float* f_v_feats_out, int32_t* row_src, int T, int max_vl, int B, int NF, int D, hero_stream_t stream);
+int hero_fom_shuffle(const int32_t* vid_nfrm, const unsigned long long* seed_dev, unsigned long long site, unsigned long long threshold,
+                     int64_t* shuffled_orders, int64_t* targets, int B, int NF, hero_stream_t stream);
+
 /* Everything the model derives from the int64 index / mask tensors of a batch, in one launch: additive attention   */
 /* masks (1 - m) * -10000 (model/layers.py:299-302), fp32 masks, int32 row indices, and f_gather_index as flat rows   */
 /* of hero_gather_rows (>= 0: image row, <= -2: text row; model/encoder.py:271-279).  src int64, n elements.          */
