@@ -115,8 +115,7 @@ def notify_weights_updated():
 def clear_weight_cache():
     _WGEN[0] += 1
     _WCACHE.clear()
-    for k in [k for k in _REFRESH if k not in _REFRESH_PINNED]:
-        del _REFRESH[k]
+    _REFRESH.clear(keep_pinned=True)
 
 
 _TRUST = [False]
@@ -135,8 +134,68 @@ class weights_frozen:
         _TRUST[0] = self.prev
 
 
-_REFRESH = {}              # descriptor-table signature -> device tables of hero_copy_multi (several: the tasks of a multi-task run
-_REFRESH_PINNED = set()    # update different parameter sets); tables used under stream capture are never dropped (a graph holds their addresses)
+class _PinnedCache:
+    """Bounded key -> value cache of device tables that launches name by ADDRESS.  A captured hipGraph keeps such an address
+    for as long as it is replayed, so an entry that was built or looked up while the stream was capturing is pinned: no
+    eviction drops it, and the cache grows past `limit` instead if everything in it is pinned.  Past `limit` entries, a miss
+    drops the oldest `drop` unpinned ones.  A cached None ("nothing to launch with") is an entry like any other, never pinned."""
+
+    def __init__(self, limit, drop):
+        self.limit, self.drop, self.entries, self.pinned = limit, drop, {}, set()
+
+    def get(self, key, build):
+        hit = self.entries.get(key, self)           # self: no entry (None is a value)
+        if hit is self:
+            hit = build()
+            if len(self.entries) > self.limit:
+                for k in [k for k in self.entries if k not in self.pinned][:self.drop]:
+                    del self.entries[k]
+            self.entries[key] = hit
+        if hit is not None and torch.cuda.is_current_stream_capturing():
+            self.pinned.add(key)
+        return hit
+
+    def clear(self, keep_pinned):
+        if not keep_pinned:
+            self.pinned = set()
+        self.entries = {k: v for k, v in self.entries.items() if k in self.pinned}
+
+
+class _Copy(NamedTuple):
+    """One cached compute copy: `out` = the `params` cast (and, `transposed`, each turned) as of `sig`."""
+    sig: Any
+    out: Any
+    params: Any
+    transposed: bool
+
+
+# descriptor-table signature -> device tables of hero_copy_multi (several: the tasks of a multi-task run update different parameter sets)
+_REFRESH = _PinnedCache(16, 8)
+
+
+def _refresh_tables(entries):
+    descs, tdesc, tidx = [], [], []
+    for _, (_, out, params, transposed) in entries:
+        esz, code = out.element_size(), L.dt(out)
+        off = 0
+        for p in params:
+            if not p.is_contiguous() or p.dtype != torch.float32:
+                raise RuntimeError("hero_amd: master weights must be contiguous fp32")
+            rows = p.shape[0] if p.dim() > 1 else 1
+            cols = p.numel() // rows
+            if transposed:          # out [K, sum N]: this tensor's columns start at `off`
+                d = L.CopyDesc(p.data_ptr(), out.data_ptr() + off * esz, rows, cols, out.shape[1], 1, code, 0)
+                off += rows
+            else:                   # out [sum N, K] (or a flat concatenation of 1-D tensors)
+                d = L.CopyDesc(p.data_ptr(), out.data_ptr() + off * esz, rows, cols, cols, 0, code, 0)
+                off += rows * cols
+            nt = (-(-rows // 64)) * (-(-cols // 64))
+            tdesc += [len(descs)] * nt
+            tidx += list(range(nt))
+            descs.append(d)
+    dev = entries[0][1].out.device
+    raw = torch.frombuffer(bytearray(bytes((L.CopyDesc * len(descs))(*descs))), dtype=torch.uint8).to(dev)
+    return raw, torch.tensor(tdesc, dtype=torch.int32, device=dev), torch.tensor(tidx, dtype=torch.int32, device=dev), len(tdesc)
 
 
 def refresh_weight_cache():
@@ -149,43 +208,40 @@ def refresh_weight_cache():
     if not _WCACHE:
         return
     entries = list(_WCACHE.items())
-    tsig = tuple((key, val[1].data_ptr(), tuple(p.data_ptr() for p in val[2])) for key, val in entries)
-    if tsig not in _REFRESH:
-        if len(_REFRESH) > 16:
-            for k in [k for k in _REFRESH if k not in _REFRESH_PINNED][:8]:
-                del _REFRESH[k]
-        descs, tdesc, tidx = [], [], []
-        for key, (_, out, params) in entries:
-            transposed = len(key) == 3
-            esz, code = out.element_size(), L.dt(out)
-            off = 0
-            for p in params:
-                if not p.is_contiguous() or p.dtype != torch.float32:
-                    raise RuntimeError("hero_amd: master weights must be contiguous fp32")
-                rows = p.shape[0] if p.dim() > 1 else 1
-                cols = p.numel() // rows
-                if transposed:          # out [K, sum N]: this tensor's columns start at `off`
-                    d = L.CopyDesc(p.data_ptr(), out.data_ptr() + off * esz, rows, cols, out.shape[1], 1, code, 0)
-                    off += rows
-                else:                   # out [sum N, K] (or a flat concatenation of 1-D tensors)
-                    d = L.CopyDesc(p.data_ptr(), out.data_ptr() + off * esz, rows, cols, cols, 0, code, 0)
-                    off += rows * cols
-                nt = (-(-rows // 64)) * (-(-cols // 64))
-                tdesc += [len(descs)] * nt
-                tidx += list(range(nt))
-                descs.append(d)
-        dev = entries[0][1][1].device
-        arr = (L.CopyDesc * len(descs))(*descs)
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        _REFRESH[tsig] = (raw, torch.tensor(tdesc, dtype=torch.int32, device=dev),
-                          torch.tensor(tidx, dtype=torch.int32, device=dev), len(tdesc))
-    if torch.cuda.is_current_stream_capturing():
-        _REFRESH_PINNED.add(tsig)
-    raw, tdesc, tidx, n = _REFRESH[tsig]
+    tsig = tuple((key, val.out.data_ptr(), tuple(p.data_ptr() for p in val.params)) for key, val in entries)
+    raw, tdesc, tidx, n = _REFRESH.get(tsig, lambda: _refresh_tables(entries))
     L.check(L.lib().hero_copy_multi(raw.data_ptr(), tdesc.data_ptr(), tidx.data_ptr(), n, L.stream()))
     ep = _WEPOCH[0]
-    for key, (_, out, params) in entries:
-        _WCACHE[key] = ((tuple(p._version for p in params), tuple(p.data_ptr() for p in params), ep), out, params)
+    for key, val in entries:
+        sig = (tuple(p._version for p in val.params), tuple(p.data_ptr() for p in val.params), ep)
+        _WCACHE[key] = _Copy(sig, val.out, val.params, val.transposed)
+
+
+def _compute_copy(params, dtype, transposed):
+    """The cached copy of fp32 `params` in `dtype`: their rows back to back, or - `transposed` - their transposes side by side."""
+    key = (tuple(id(p) for p in params), dtype, "T") if transposed else (tuple(id(p) for p in params), dtype)
+    hit = _WCACHE.get(key)
+    if _TRUST[0] and hit is not None and hit.sig is not None and hit.sig[2] == _WEPOCH[0]:
+        return hit.out
+    sig = (tuple(p._version for p in params), tuple(p.data_ptr() for p in params), _WEPOCH[0])
+    if hit is not None and hit.sig == sig:
+        return hit.out
+    rows = sum(p.shape[0] for p in params)
+    shape = (params[0].shape[1], rows) if transposed else (rows,) + tuple(params[0].shape[1:])
+    reuse = hit is not None and tuple(hit.out.shape) == shape and hit.out.device == params[0].device
+    out = hit.out if reuse else torch.empty(shape, dtype=dtype, device=params[0].device)
+    off = 0
+    for p in params:
+        src = L.ptr(p.detach().contiguous())
+        if transposed:
+            L.check(L.lib().hero_transpose_cast(src, out.data_ptr() + off * out.element_size(), p.shape[0], shape[0], rows, L.dt(out), L.stream()))
+        else:
+            L.check(L.lib().hero_cast(src, out[off:off + p.shape[0]].data_ptr(), p.numel(), L.F32, L.dt(out), L.stream()))
+        off += p.shape[0]
+    if hit is None or not reuse:
+        _WGEN[0] += 1
+    _WCACHE[key] = _Copy(sig, out, params, transposed)
+    return out
 
 
 def packed(params, dtype):
@@ -193,55 +249,13 @@ def packed(params, dtype):
     params = tuple(params)
     if len(params) == 1 and dtype == torch.float32 and params[0].is_contiguous():
         return params[0].detach()
-    key = (tuple(id(p) for p in params), dtype)
-    hit = _WCACHE.get(key)
-    if _TRUST[0] and hit is not None and hit[0] is not None and hit[0][2] == _WEPOCH[0]:
-        return hit[1]
-    sig = (tuple(p._version for p in params), tuple(p.data_ptr() for p in params), _WEPOCH[0])
-    if hit is not None and hit[0] == sig:
-        return hit[1]
-    rows = sum(p.shape[0] for p in params)
-    shape = (rows,) + tuple(params[0].shape[1:])
-    reuse = hit is not None and tuple(hit[1].shape) == shape and hit[1].device == params[0].device
-    out = hit[1] if reuse else torch.empty(shape, dtype=dtype, device=params[0].device)
-    off = 0
-    for p in params:
-        n = p.numel()
-        dst = out[off:off + p.shape[0]]
-        L.check(L.lib().hero_cast(L.ptr(p.detach().contiguous()), dst.data_ptr(), n, L.F32,
-                                  L.dt(out), L.stream()))
-        off += p.shape[0]
-    if hit is None or not reuse:
-        _WGEN[0] += 1
-    _WCACHE[key] = (sig, out, params)
-    return out
+    return _compute_copy(params, dtype, False)
 
 
 def packed_t(params, dtype):
     """Transposed compute copy: [K_in, sum_i N_i] = concat_i(p_i^T) (cached like `packed`), used as
     the K-contiguous B operand of dgrad: dX = dY @ W  ==  dY @ (W^T)^T."""
-    params = tuple(params)
-    key = (tuple(id(p) for p in params), dtype, "T")
-    hit = _WCACHE.get(key)
-    if _TRUST[0] and hit is not None and hit[0] is not None and hit[0][2] == _WEPOCH[0]:
-        return hit[1]
-    sig = (tuple(p._version for p in params), tuple(p.data_ptr() for p in params), _WEPOCH[0])
-    if hit is not None and hit[0] == sig:
-        return hit[1]
-    kin = params[0].shape[1]
-    cols = sum(p.shape[0] for p in params)
-    reuse = hit is not None and tuple(hit[1].shape) == (kin, cols) and hit[1].device == params[0].device
-    out = hit[1] if reuse else torch.empty((kin, cols), dtype=dtype, device=params[0].device)
-    off = 0
-    for p in params:
-        L.check(L.lib().hero_transpose_cast(L.ptr(p.detach().contiguous()),
-                                            out.data_ptr() + off * out.element_size(), p.shape[0], kin,
-                                            cols, L.dt(out), L.stream()))
-        off += p.shape[0]
-    if hit is None or not reuse:
-        _WGEN[0] += 1
-    _WCACHE[key] = (sig, out, params)
-    return out
+    return _compute_copy(tuple(params), dtype, True)
 
 
 # --------------------------------------------------------------------------------------------- #
@@ -470,8 +484,8 @@ _WQ, _CQ = _GradQueue(), _GradQueue()
 WGRAD_RIDE_MAX_ROWS = [1 << 30]
 WGRAD_QUEUE_BYTES = [int(os.environ.get("HERO_WGRAD_QUEUE_MB", "4096")) << 20]   # dY bytes the queue may keep alive
 _WQ_HARD = {}            # device index -> hard cap in bytes (_wgrad_queue_full)
-_WPLANS = {}             # (rows, ((M, N), ...)) -> (device int32 plan, words) or None when the group is too small
-_WPLANS_PINNED = set()   # keys whose plan tensor a captured graph references by address
+# (rows, device, ((M, N), ...)) -> (device int32 plan, words) or None when the group is too small; ragged eager batches make a key per row count
+_WPLANS = _PinnedCache(256, 128)
 
 
 def _take_dst(seen, dst):
@@ -543,24 +557,13 @@ def _wgrad_limit():
 
 
 def _wgrad_plan(probs, n, rows, device):
-    key = (rows, device.index, tuple((probs[i].M, probs[i].N) for i in range(n)))
-    hit = _WPLANS.get(key, False)
-    if hit is False:
+    def build():
         buf = np.zeros(8 + 8 * 512 * 16, dtype=np.int32)
         words = L.lib().hero_wgrad_batch_plan(probs, n, rows, buf.ctypes.data, buf.size)
         if words < 0:
             L.check(words)
-        hit = (torch.from_numpy(buf[:words].copy()).to(device), words) if words > 0 else None
-        # Plans are never dropped while a captured hipGraph may hold their device address (as optim.adamw pins its
-        # tables): entries made or used under stream capture are pinned; the rest of the cache (ragged eager batches make
-        # a key per distinct row count) is bounded.
-        if len(_WPLANS) > 256:
-            for k in [k for k in _WPLANS if k not in _WPLANS_PINNED][:128]:
-                del _WPLANS[k]
-        _WPLANS[key] = hit
-    if hit is not None and torch.cuda.is_current_stream_capturing():
-        _WPLANS_PINNED.add(key)
-    return hit
+        return (torch.from_numpy(buf[:words].copy()).to(device), words) if words > 0 else None
+    return _WPLANS.get((rows, device.index, tuple((probs[i].M, probs[i].N) for i in range(n))), build)
 
 
 def deferred_flush():
@@ -934,13 +937,11 @@ def reset_caches():
     Not while a captured hipGraph that references those buffers is still going to be replayed."""
     global _MEMO_SEQ
     clear_weight_cache()
-    _REFRESH.clear()
-    _REFRESH_PINNED.clear()
+    _REFRESH.clear(keep_pinned=False)
     _MEMO.clear()
     _MEMO_SEQ = 0
     _WS.clear()
-    _WPLANS.clear()
-    _WPLANS_PINNED.clear()
+    _WPLANS.clear(keep_pinned=False)
     _SEQ_OFF.clear()
     _SLACK.clear()
     _WQ.clear()
@@ -1524,64 +1525,27 @@ def _qkv_bwd(dqkv, x2, qkv_params, D):
                          ncols=D)
 
 
-class SelfAttentionFn(torch.autograd.Function):
-    """BertSelfAttention (model/layers.py:124-164): ctx = MHA(x)."""
-
-    @staticmethod
-    def forward(ctx, x, mask_add, H, drop_p, wq, bq, wk, bk, wv, bv):
-        S, Lq, D = x.shape
-        x2 = _as2d(x)
-        Wqkv = packed((wq, wk, wv), x2.dtype)
-        bqkv = packed((bq, bk, bv), torch.float32)
-        qkv = k_linear(x2, Wqkv, bqkv)
-        ctxt, probs = k_attn_fwd(qkv, mask_add, S, Lq, H, drop=drop_p)
-        ctx.dims, ctx.drop, ctx.mask_add = (S, Lq, H, D), drop_p, mask_add
-        ctx.params = (wq, bq, wk, bk, wv, bv)
-        _use(*ctx.params)
-        ctx.save_for_backward(x2, packed_t((wq, wk, wv), x2.dtype), qkv, probs, ctxt)
-        return ctxt.view(S, Lq, D)
-
-    @staticmethod
-    def backward(ctx, dctx):
-        x2, Wqkv_t, qkv, probs, ctxt = ctx.saved_tensors
-        S, Lq, H, D = ctx.dims
-        dqkv = k_attn_bwd(qkv, probs, _as2d(dctx), S, Lq, H, drop=ctx.drop, ctx=ctxt, mask_add=ctx.mask_add)
-        dx = k_dgrad_t(dqkv, Wqkv_t).view(S, Lq, D) if ctx.needs_input_grad[0] else None
-        _qkv_bwd(dqkv, x2, ctx.params, D)
-        return (dx,) + (None,) * 9
+class Segment(NamedTuple):
+    """A sequence group inside a stack of rows: S sequences, L positions each (padded, rows back to back) - or, with
+    `seq_off` (int32 [S + 1]), a packed batch: sequence s is rows [seq_off[s], seq_off[s + 1]), L is the longest."""
+    S: int
+    L: int
+    seq_off: Any = None
 
 
-class ProjResLnFn(torch.autograd.Function):
-    """BertSelfOutput / BertOutput (model/layers.py:175-179, 250-254): LN(drop(h W^T + b) + res)."""
+def segment_rows(segs):
+    """(S, L, rows, seq_off) per segment of a row stack; `rows` is the slice of the stack a padded group occupies (they
+    follow each other) and None - all rows - for a packed one, whose seq_off addresses the stack itself."""
+    r0 = 0
+    for sg in segs:
+        S, Lq, off = Segment(*sg)
+        rows = slice(r0, r0 + S * Lq) if off is None else None
+        yield S, Lq, rows, off
+        r0 = r0 if rows is None else rows.stop
 
-    @staticmethod
-    def forward(ctx, h, res, eps, drop, w, b, gamma, beta):
-        h2, r2 = _as2d(h), _as2d(res)
-        Wc = packed((w,), h2.dtype)
-        y = k_linear(h2, Wc, b.detach(), residual=r2, drop=drop)
-        out, mean, rstd, _ = k_ln_fwd(y, gamma.detach(), beta.detach(), eps, y.dtype, y.shape[0], y.shape[1])
-        ctx.drop = drop
-        ctx.hshape, ctx.rshape = h.shape, res.shape
-        ctx.params = (w, b, gamma, beta)
-        _use(*ctx.params)
-        ctx.save_for_backward(h2, packed_t((w,), h2.dtype), y, mean, rstd, gamma.detach())
-        return out.view(res.shape)
 
-    @staticmethod
-    def backward(ctx, dout):
-        h2, Wt, y, mean, rstd, gamma = ctx.saved_tensors
-        w, b, gp, bp = ctx.params
-        dgd, dbd = ln_param_dsts(gp, bp)
-        fuse_b = b.requires_grad and y.shape[1] <= 1024
-        dy, dyd, _, _ = k_ln_bwd(y, _as2d(dout), gamma, mean, rstd, drop_in=ctx.drop, dgamma=dgd,
-                                 dbeta=dbd, grad_beta=1.0, want_params=False,
-                                 dbias_in=SINK.dst(b) if fuse_b else None)
-        ln_params_done(gp, bp)
-        if fuse_b:
-            SINK.done(b)
-        acc_linear_grads(dyd, h2, w, None if fuse_b else b)
-        dh = k_dgrad_t(dyd, Wt).view(ctx.hshape)
-        return (dh, dy.view(ctx.rshape)) + (None,) * 6
+def _rows(t, rows):
+    return t if rows is None else t[rows]
 
 
 ONE_ATTN_LAUNCH = [True]    # False: one attention launch per sequence group (lab A/B)
@@ -1594,16 +1558,16 @@ def _one_attention_launch(segs, masks, drops, x2):
     moved), the additive masks are stacked into one [sum S, max L] tensor (HeroAttn.mask is indexed [s, max L] with a
     seq_off too).  The query group's launch - 384 waves, ~5 us forward / ~7 us backward plus two kernel boundaries per layer -
     disappears into the subtitle one.  bf16 matrix-core kernels with row statistics only (L <= 64)."""
-    if not (ONE_ATTN_LAUNCH[0] and len(segs) > 1 and all(len(sg) == 2 for sg in segs) and x2.dtype == torch.bfloat16 and x2.is_cuda):
+    if not (ONE_ATTN_LAUNCH[0] and len(segs) > 1 and all(sg.seq_off is None for sg in segs) and x2.dtype == torch.bfloat16 and x2.is_cuda):
         return segs, masks, drops
-    lmax = max(sg[1] for sg in segs)
+    lmax = max(sg.L for sg in segs)
     if ATTN_SAVE_PROBS or not L.lib().hero_attention_stats_ok(L.BF16, lmax) or any(m is not None and m.requires_grad for m in masks):
         return segs, masks, drops
-    key = (tuple(segs), x2.device.index)
+    key = (segs, x2.device.index)
     off = _SEQ_OFF.get(key)
     if off is None:
         o, r = [0], 0
-        for S_, L_ in segs:
+        for S_, L_, _ in segs:
             for _ in range(S_):
                 r += L_
                 o.append(r)
@@ -1613,18 +1577,106 @@ def _one_attention_launch(segs, masks, drops, x2):
     else:
         def build():
             parts = []
-            for (S_, L_), m in zip(segs, masks):
+            for (S_, L_, _), m in zip(segs, masks):
                 mm = m.reshape(S_, L_).float() if m is not None else torch.zeros((S_, L_), dtype=torch.float32, device=x2.device)
                 parts.append(torch.nn.functional.pad(mm, (0, lmax - L_)) if L_ < lmax else mm)
             return torch.cat(parts, 0).contiguous()
-        mcat = memo("attn_mask_cat", tuple(m for m in masks if m is not None), build, (tuple(segs),))
-    return (("packed", sum(sg[0] for sg in segs), lmax, off),), (mcat,), (drops[0],)
+        mcat = memo("attn_mask_cat", tuple(m for m in masks if m is not None), build, (segs,))
+    return (Segment(sum(sg.S for sg in segs), lmax, off),), (mcat,), (drops[0],)
+
+
+# The two halves the blocks are made of - plain functions, the autograd nodes below sequence them.  They take the straight
+# compute copies from their callers: each node makes its copies in an order of its own, ahead of its first GEMM.
+def _attn_fwd(x2, Wqkv, bqkv, segs, masks, H, drops):
+    """Attention front: qkv = x2 Wqkv^T + bqkv, then MHA per segment (after _one_attention_launch) into one context tensor.
+    Returns (qkv, ctxt, what k_attn_bwd needs per segment, the (segs, masks, drops) that were launched)."""
+    qkv = k_linear(x2, Wqkv, bqkv)
+    ctxt = torch.empty((x2.shape[0], H * 64), dtype=x2.dtype, device=x2.device)
+    segs, masks, drops = _one_attention_launch(tuple(Segment(*sg) for sg in segs), masks, drops, x2)
+    saved = [k_attn_fwd(_rows(qkv, rows), m, S, Lq, H, drop=dr, out=_rows(ctxt, rows), seq_off=off)[1]
+             for (S, Lq, rows, off), m, dr in zip(segment_rows(segs), masks, drops)]
+    return qkv, ctxt, saved, (segs, masks, drops)
+
+
+def _attn_bwd(qkv, ctxt, dctx, saved, H, segs, masks, drops):
+    """d qkv of _attn_fwd from d ctxt; the callers go on to the parameter gradients (_qkv_bwd) and the input dgrad."""
+    dqkv = torch.empty_like(qkv)
+    for (S, Lq, rows, off), p, m, dr in zip(segment_rows(segs), saved, masks, drops):
+        k_attn_bwd(_rows(qkv, rows), p, _rows(dctx, rows), S, Lq, H, drop=dr, out=_rows(dqkv, rows), seq_off=off,
+                   ctx=_rows(ctxt, rows), mask_add=m)
+    return dqkv
+
+
+def _res_ln_fwd(h2, r2, eps, drop, Wc, b, gamma, beta):
+    """Residual-LayerNorm tail: LN(y), y = drop(h2 Wc^T + b) + r2.  Returns (out, y, mean, rstd)."""
+    y = k_linear(h2, Wc, b.detach(), residual=r2, drop=drop)
+    out, mean, rstd, _ = k_ln_fwd(y, gamma.detach(), beta.detach(), eps, y.dtype, y.shape[0], y.shape[1])
+    return out, y, mean, rstd
+
+
+def _res_ln_bwd(dout2, h2, y, mean, rstd, gamma, drop, w, b, gamma_p, beta_p):
+    """Backward of the tail up to its input dgrad: LayerNorm backward with the gradients of gamma, beta and - up to 1024 columns, from
+    the same pass - b into the gradient sink, then w's.  Returns (dy, dy_dropped): d residual, and d (h2 Wc^T) for the caller's dgrad."""
+    dgd, dbd = ln_param_dsts(gamma_p, beta_p)
+    fuse_b = b.requires_grad and y.shape[1] <= 1024
+    dy, dyd, _, _ = k_ln_bwd(y, dout2, gamma, mean, rstd, drop_in=drop, dgamma=dgd, dbeta=dbd, grad_beta=1.0,
+                             want_params=False, dbias_in=SINK.dst(b) if fuse_b else None)
+    ln_params_done(gamma_p, beta_p)
+    if fuse_b:
+        SINK.done(b)
+    acc_linear_grads(dyd, h2, w, None if fuse_b else b)
+    return dy, dyd
+
+
+class SelfAttentionFn(torch.autograd.Function):
+    """BertSelfAttention (model/layers.py:124-164): ctx = MHA(x)."""
+
+    @staticmethod
+    def forward(ctx, x, mask_add, H, drop_p, wq, bq, wk, bk, wv, bv):
+        S, Lq, D = x.shape
+        x2 = _as2d(x)
+        qkv, ctxt, saved, ctx.launched = _attn_fwd(x2, packed((wq, wk, wv), x2.dtype), packed((bq, bk, bv), torch.float32),
+                                                   ((S, Lq),), (mask_add,), H, (drop_p,))
+        ctx.H, ctx.xshape = H, x.shape
+        ctx.params = (wq, bq, wk, bk, wv, bv)
+        _use(*ctx.params)
+        ctx.save_for_backward(x2, packed_t((wq, wk, wv), x2.dtype), qkv, saved[0], ctxt)
+        return ctxt.view(S, Lq, D)
+
+    @staticmethod
+    def backward(ctx, dctx):
+        x2, Wqkv_t, qkv, saved, ctxt = ctx.saved_tensors
+        dqkv = _attn_bwd(qkv, ctxt, _as2d(dctx), (saved,), ctx.H, *ctx.launched)
+        dx = k_dgrad_t(dqkv, Wqkv_t).view(ctx.xshape) if ctx.needs_input_grad[0] else None
+        _qkv_bwd(dqkv, x2, ctx.params, x2.shape[1])
+        return (dx,) + (None,) * 9
+
+
+class ProjResLnFn(torch.autograd.Function):
+    """BertSelfOutput / BertOutput (model/layers.py:175-179, 250-254): LN(drop(h W^T + b) + res)."""
+
+    @staticmethod
+    def forward(ctx, h, res, eps, drop, w, b, gamma, beta):
+        h2 = _as2d(h)
+        out, y, mean, rstd = _res_ln_fwd(h2, _as2d(res), eps, drop, packed((w,), h2.dtype), b, gamma, beta)
+        ctx.drop, ctx.hshape, ctx.rshape = drop, h.shape, res.shape
+        ctx.params = (w, b, gamma, beta)
+        _use(*ctx.params)
+        ctx.save_for_backward(h2, packed_t((w,), h2.dtype), y, mean, rstd, gamma.detach())
+        return out.view(res.shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        h2, Wt, y, mean, rstd, gamma = ctx.saved_tensors
+        dy, dyd = _res_ln_bwd(_as2d(dout), h2, y, mean, rstd, gamma, ctx.drop, *ctx.params)
+        dh = k_dgrad_t(dyd, Wt).view(ctx.hshape)
+        return (dh, dy.view(ctx.rshape)) + (None,) * 6
 
 
 class AttnBlockFn(torch.autograd.Function):
     """BertAttention (model/layers.py:217-222) as ONE node: a = LN(drop(MHA(x) Wo^T + bo) + x).
 
-    `x` is [rows, D]; `segs` = ((S, L), ...) lists the sequence groups stacked along the rows
+    `x` is [rows, D]; `segs` = ((S, L), ...) or Segments lists the sequence groups stacked along the rows
     (sum S*L == rows).  Everything except the attention itself is row-wise, so several groups with
     different lengths — e.g. HERO's subtitle rows (L = frames+tokens) and its query rows — share the
     GEMM / LayerNorm launches and only the attention kernel is called per group."""
@@ -1632,63 +1684,26 @@ class AttnBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, segs, masks, H, eps, drops_attn, drop_hid, wq, bq, wk, bk, wv, bv, wo, bo, g1, b1):
         x2 = _as2d(x)
-        D = x2.shape[1]
-        Wqkv = packed((wq, wk, wv), x2.dtype)
-        bqkv = packed((bq, bk, bv), torch.float32)
+        Wqkv, bqkv = packed((wq, wk, wv), x2.dtype), packed((bq, bk, bv), torch.float32)
         Wo = packed((wo,), x2.dtype)
-        qkv = k_linear(x2, Wqkv, bqkv)
-        ctxt = torch.empty((x2.shape[0], D), dtype=x2.dtype, device=x2.device)
-        segs, masks, drops_attn = _one_attention_launch(segs, masks, drops_attn, x2)
-        probs = []
-        r0 = 0
-        for seg, m, dr in zip(segs, masks, drops_attn):          # each group writes its row slice
-            if len(seg) == 4:                                    # ("packed", S, Lmax, seq_off): all rows
-                _, S, Lq, off = seg
-                _, p = k_attn_fwd(qkv, m, S, Lq, H, drop=dr, out=ctxt, seq_off=off)
-                probs.append(p)
-                continue
-            S, Lq = seg
-            _, p = k_attn_fwd(qkv[r0:r0 + S * Lq], m, S, Lq, H, drop=dr, out=ctxt[r0:r0 + S * Lq])
-            probs.append(p)
-            r0 += S * Lq
-        y1 = k_linear(ctxt, Wo, bo.detach(), residual=x2, drop=drop_hid)
-        a, mean, rstd, _ = k_ln_fwd(y1, g1.detach(), b1.detach(), eps, y1.dtype, x2.shape[0], D)
-        ctx.meta = (segs, H, D, drops_attn, drop_hid, x.shape)
-        ctx.masks = masks                 # additive masks (derived, no grad): the backward rebuilds P from q, k with them
+        # `launched` keeps the additive masks (derived, no grad): the backward rebuilds P from q, k with them
+        qkv, ctxt, saved, ctx.launched = _attn_fwd(x2, Wqkv, bqkv, segs, masks, H, drops_attn)
+        a, y1, mean, rstd = _res_ln_fwd(ctxt, x2, eps, drop_hid, Wo, bo, g1, b1)
+        ctx.meta = (H, drop_hid, x.shape)
         ctx.params = (wq, bq, wk, bk, wv, bv, wo, bo, g1, b1)
         _use(*ctx.params)
         ctx.save_for_backward(x2, packed_t((wq, wk, wv), x2.dtype), packed_t((wo,), x2.dtype), qkv, ctxt, y1,
-                              mean, rstd, g1.detach(), *probs)
+                              mean, rstd, g1.detach(), *saved)
         return a.view(x.shape)
 
     @staticmethod
     def backward(ctx, da):
         x2, Wqkv_t, Wo_t, qkv, ctxt, y1, mean, rstd, g1 = ctx.saved_tensors[:9]
-        probs = ctx.saved_tensors[9:]
-        segs, H, D, drops_attn, drop_hid, xshape = ctx.meta
-        wq, bq, wk, bk, wv, bv, wo, bo, g1p, b1p = ctx.params
-        dgd, dbd = ln_param_dsts(g1p, b1p)
-        fuse_b = bo.requires_grad and D <= 1024
-        dy1, dy1d, _, _ = k_ln_bwd(y1, _as2d(da), g1, mean, rstd, drop_in=drop_hid, dgamma=dgd,
-                                   dbeta=dbd, grad_beta=1.0, want_params=False,
-                                   dbias_in=SINK.dst(bo) if fuse_b else None)
-        ln_params_done(g1p, b1p)
-        if fuse_b:
-            SINK.done(bo)
-        acc_linear_grads(dy1d, ctxt, wo, None if fuse_b else bo)
+        H, drop_hid, xshape = ctx.meta
+        dy1, dy1d = _res_ln_bwd(_as2d(da), ctxt, y1, mean, rstd, g1, drop_hid, *ctx.params[6:])
         dctx = k_dgrad_t(dy1d, Wo_t)
-        dqkv = torch.empty_like(qkv)
-        r0 = 0
-        for seg, p, dr, m in zip(segs, probs, drops_attn, ctx.masks):
-            if len(seg) == 4:
-                _, S, Lq, off = seg
-                k_attn_bwd(qkv, p, dctx, S, Lq, H, drop=dr, out=dqkv, seq_off=off, ctx=ctxt, mask_add=m)
-                continue
-            S, Lq = seg
-            k_attn_bwd(qkv[r0:r0 + S * Lq], p, dctx[r0:r0 + S * Lq], S, Lq, H, drop=dr,
-                       out=dqkv[r0:r0 + S * Lq], ctx=ctxt[r0:r0 + S * Lq], mask_add=m)
-            r0 += S * Lq
-        _qkv_bwd(dqkv, x2, (wq, bq, wk, bk, wv, bv), D)
+        dqkv = _attn_bwd(qkv, ctxt, dctx, ctx.saved_tensors[9:], H, *ctx.launched)
+        _qkv_bwd(dqkv, x2, ctx.params[:6], x2.shape[1])
         dx = k_dgrad_t(dqkv, Wqkv_t, residual=dy1).view(xshape)    # + residual-path gradient, fused
         return (dx,) + (None,) * 16
 
@@ -1707,8 +1722,7 @@ class FfnBlockFn(torch.autograd.Function):
         # rcp / polynomial per 12000 x 3072 launch, tools/lab/gelu_ab.py)
         u = torch.empty((a2.shape[0], W1.shape[0]), dtype=a2.dtype, device=a2.device)
         hg = k_linear(a2, W1, b1.detach(), act=L.ACT_GELU_DG, aux=u)
-        y2 = k_linear(hg, W2, b2.detach(), residual=a2, drop=drop_hid)
-        out, mean, rstd, _ = k_ln_fwd(y2, g2.detach(), bt2.detach(), eps, y2.dtype, y2.shape[0], y2.shape[1])
+        out, y2, mean, rstd = _res_ln_fwd(hg, a2, eps, drop_hid, W2, b2, g2, bt2)
         ctx.drop, ctx.shp = drop_hid, shp
         ctx.params = (w1, b1, w2, b2, g2, bt2)
         _use(*ctx.params)
@@ -1719,16 +1733,8 @@ class FfnBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         a2, W1_t, W2_t, u, hg, y2, mean, rstd, g2 = ctx.saved_tensors
-        w1, b1, w2, b2, g2p, bt2p = ctx.params
-        dgd, dbd = ln_param_dsts(g2p, bt2p)
-        fuse_b = b2.requires_grad and y2.shape[1] <= 1024
-        dy2, dy2d, _, _ = k_ln_bwd(y2, _as2d(dout), g2, mean, rstd, drop_in=ctx.drop, dgamma=dgd,
-                                   dbeta=dbd, grad_beta=1.0, want_params=False,
-                                   dbias_in=SINK.dst(b2) if fuse_b else None)
-        ln_params_done(g2p, bt2p)
-        if fuse_b:
-            SINK.done(b2)
-        acc_linear_grads(dy2d, hg, w2, None if fuse_b else b2)
+        w1, b1 = ctx.params[:2]
+        dy2, dy2d = _res_ln_bwd(_as2d(dout), hg, y2, mean, rstd, g2, ctx.drop, *ctx.params[2:])
         # db1 = column sums of du.  bf16: the gelu' epilogue writes each tile's column sums to a [rows / 64, 3072] table
         # (HeroGemmEpilogue.colsum_partial: plain stores, no atomics), folded in fixed order by the deferred multi-sum - or at
         # once where gradients must become final layer by layer; riding on hero_wgrad_batch cost that launch +0.09 ms per

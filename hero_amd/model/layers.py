@@ -400,7 +400,7 @@ class BertEncoder(nn.Module):
         if plan is not None:
             gather, inverse, inv, back, off, n_seq, lmax = plan
             x = HF.PermuteRowsFn.apply(x.contiguous(), gather, inverse)
-            packed = (("packed", n_seq, lmax, off),)
+            packed = (HF.Segment(n_seq, lmax, off),)
             for layer in self.layer:
                 x = layer.forward_rows(x, packed, (None,))
             return [HF.PermuteRowsFn.apply(x, i_, b_).view(S, Lq, D) for i_, b_, (S, Lq) in zip(inv, back, segs)]

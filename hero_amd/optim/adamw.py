@@ -26,22 +26,21 @@ class AdamW(Optimizer):
         if len(self.param_groups) > 8:
             raise ValueError("hero_amd AdamW supports up to 8 parameter groups")
         self._global_step = 0
-        self._tables = {}         # signature -> (device tensors, n_chunks)
-        self._pinned = []         # tables built or used while a hipGraph was capturing: the graph holds their addresses
+        self._tables = HF._PinnedCache(16, 8)     # signature -> (device tensors, n_chunks); eager multi-task runs change it often
         self._tsteps = None       # device-state mode: per-parameter step counts on the device (int32 [n params])
         self._slots = None        # parameter -> slot in _tsteps
         self.last_active = []     # (group index, parameter) of the last step(): what TrainStep hands to prebuild()
 
     def load_state_dict(self, state_dict):
         """A restore replaces the moment tensors the descriptor tables point at: drop the tables (the ones captured
-        graphs use stay alive in `_pinned`, but such graphs must be re-captured - TrainStep refuses the restore)."""
+        graphs use stay, but such graphs must be re-captured - TrainStep refuses the restore)."""
         super().load_state_dict(state_dict)
-        self._tables = {}
+        self._tables.clear(keep_pinned=True)
         self._tsteps = None       # re-seeded from the restored state['step'] at the next device-state step
 
     def __setstate__(self, state):
         super().__setstate__(state)
-        self._tables, self._pinned = {}, []
+        self._tables = HF._PinnedCache(16, 8)
         self._tsteps = self._slots = None
 
     # ---- gradient norm ---------------------------------------------------------------------------
@@ -133,8 +132,7 @@ class AdamW(Optimizer):
             return loss
         tsteps = self._device_steps(active[0][1].device) if device_state else None
         self.last_active = active
-        sig = self._table_for(active, device_state)
-        raw, t_ct, t_ci, n_chunks = self._tables[sig]
+        raw, t_ct, t_ci, n_chunks = self._table_for(active, device_state)
         return self._launch(raw, t_ct, t_ci, n_chunks, len(active), tsteps, grad_sumsq, max_grad_norm, grad_scale, step_tensor, lr_tensor, loss)
 
     def prebuild(self, active, device_state=True):
@@ -156,14 +154,7 @@ class AdamW(Optimizer):
         else:
             sig = tuple((id(p), p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(),
                          self.state[p]["exp_avg_sq"].data_ptr(), self._global_step - self.state[p]["step"]) for _, p in active)
-        capturing = torch.cuda.is_current_stream_capturing()
-        if sig not in self._tables:
-            if len(self._tables) >= 16 and not capturing:
-                self._tables = {}                 # eager multi-task runs change the signature often; pinned tables survive
-            self._tables[sig] = self._build_table(active, slots=device_state)
-        if capturing and not any(t is self._tables[sig] for t in self._pinned):
-            self._pinned.append(self._tables[sig])
-        return sig
+        return self._tables.get(sig, lambda: self._build_table(active, slots=device_state))
 
     def _launch(self, raw, t_ct, t_ci, n_chunks, n_active, tsteps, grad_sumsq, max_grad_norm, grad_scale, step_tensor, lr_tensor, loss):
         a = L.AdamWMulti()
