@@ -27,6 +27,7 @@ EXPORTS = [
     "hero_cross_entropy_fwd", "hero_cross_entropy_bwd", "hero_qa_pool_fwd", "hero_qa_pool_bwd",
     "hero_frame_pool_fwd", "hero_frame_pool_bwd", "hero_bce_head_fwd", "hero_bce_head_bwd",
     "hero_dec_attention_in_envelope", "hero_dec_attention_fwd", "hero_dec_attention_bwd", "hero_smooth_ce_fwd", "hero_smooth_ce_bwd",
+    "hero_ce_eval", "hero_feat_eval",
     "hero_dec_attention_row_in_envelope", "hero_dec_attention_row", "hero_dec_attention_step",
     "hero_dec_attention_row_grouped", "hero_dec_attention_step_beam", "hero_beam_in_envelope", "hero_beam_select",
     "hero_sample_in_envelope", "hero_sample_select", "hero_caption_in_envelope", "hero_caption_score",
@@ -303,6 +304,8 @@ def lib():
         L.hero_caption_score.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p]
         L.hero_smooth_ce_fwd.argtypes = [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_double, C.c_longlong, C.c_void_p]
         L.hero_smooth_ce_bwd.argtypes = [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_double, C.c_longlong, C.c_void_p]
+        L.hero_ce_eval.argtypes = [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_float, C.c_longlong] + [C.c_void_p] * 4
+        L.hero_feat_eval.argtypes = [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p] * 3
         L.hero_comm_unique_id.argtypes = [C.c_void_p]
         L.hero_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.hero_comm_destroy.argtypes = [C.c_void_p]

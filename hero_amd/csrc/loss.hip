@@ -224,10 +224,181 @@ __global__ __launch_bounds__(256) void smooth_ce_bwd_kernel(SmoothCe a) {
   }
 }
 
+// ---- validation counters of the pre-training heads (pretrain.py:462-608) --------------------------------------------
+// One pass over the raw logits gives what validate_mlm / validate_mfm_nce / validate_fom take from F.cross_entropy(sum) and
+// scores.max(-1): the row loss (the arithmetic of ce_fwd_kernel, statement for statement) and the arg-max of the STORED
+// values, lowest column first among equal maxima.  Row results go to a workspace; one workgroup folds them into float64
+// counters in a fixed order (no atomics: two runs give the same bits).
+template <typename T>
+__global__ __launch_bounds__(256) void ce_eval_kernel(const T* logits, const long long* labels, int cols, int ld, float t, long long ignore_index,
+                                                      float* row_loss, float* row_hit, float* row_valid, int32_t* pred) {
+  __shared__ float sm[4], ss[4];
+  __shared__ unsigned long long sb[4];
+  const int row = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const T* x = logits + (size_t)row * ld;
+  float m = -3.0e38f, s = 0.f;
+  float bv = -INFINITY;                                               // a thread meets its columns in ascending order, so a
+  int bi = 0x7fffffff;                                                // strict > keeps the first of equal values
+  const int vec_end = ((ld & 7) == 0) ? (cols & ~7) : 0;
+  for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
+    float v[8];
+    ld8<T>(x + c, v);
+    float mx = v[0] * t;
+#pragma unroll
+    for (int k = 1; k < 8; ++k) mx = fmaxf(mx, v[k] * t);
+    float e = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) e += __expf(v[k] * t - mx);
+    ms_merge(m, s, mx, e);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (v[k] > bv) { bv = v[k]; bi = c + k; }
+  }
+  for (int c = vec_end + threadIdx.x; c < cols; c += 256) {
+    const float v = ld1<T>(x + c);
+    ms_merge(m, s, v * t, 1.f);
+    if (v > bv) { bv = v; bi = c; }
+  }
+  if (bi == 0x7fffffff) {                                             // nothing above -inf: the thread's first column, if it has one
+    const int first = ((int)threadIdx.x * 8 < vec_end) ? (int)threadIdx.x * 8 : vec_end + (int)threadIdx.x;
+    if (first < cols) bi = first;
+  }
+  // larger composite = larger value, then lower column (-0 and +0 tie): the maximum over the row is the prediction
+  unsigned long long best = compose(order_bits(bv), (uint32_t)bi);
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) {
+    const unsigned long long o = __shfl_xor(best, w, 64);
+    best = o > best ? o : best;
+  }
+  const float wm = wave_max(m);
+  s = wave_sum(s * __expf(m - wm));
+  if (lane == 0) { sm[wave] = wm; ss[wave] = s; sb[wave] = best; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float M = sm[0], S = ss[0];
+    unsigned long long B = sb[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      ms_merge(M, S, sm[w], ss[w]);
+      B = sb[w] > B ? sb[w] : B;
+    }
+    const float lse = M + __logf(S);
+    const int p = (int)~(uint32_t)B;
+    const long long y = labels[row];
+    const bool live = !(y == ignore_index || y < 0 || y >= cols);
+    row_loss[row] = live ? lse - ld1<T>(x + y) * t : 0.f;
+    row_hit[row] = (live && (long long)p == y) ? 1.f : 0.f;
+    row_valid[row] = live ? 1.f : 0.f;
+    if (pred) pred[row] = p;
+  }
+}
+
+// Per row of [rows, ld] predictions and targets: l2 = |p - t|, cos = p.t / (max(|p|, eps) max(|t|, eps)), eps = 1e-8
+// (F.cosine_similarity), sums in fp32: each thread adds its columns in ascending order, then the 256 partial sums are
+// added pairwise (lanes 2i and 2i+1, then pairs of pairs, ..., then the four waves the same way).
+template <typename T>
+__global__ __launch_bounds__(256) void feat_eval_kernel(const T* pred, const T* target, int cols, int ld_p, int ld_t, float* row_l2, float* row_cos) {
+  __shared__ float sq[4][4];
+  const int row = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const T* p = pred + (size_t)row * ld_p;
+  const T* g = target + (size_t)row * ld_t;
+  float dd = 0.f, pg = 0.f, pp = 0.f, gg = 0.f;
+  const int vec_end = (((ld_p | ld_t) & 7) == 0) ? (cols & ~7) : 0;
+  for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
+    float a[8], b[8];
+    ld8<T>(p + c, a);
+    ld8<T>(g + c, b);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float d = a[k] - b[k];
+      dd += d * d; pg += a[k] * b[k]; pp += a[k] * a[k]; gg += b[k] * b[k];
+    }
+  }
+  for (int c = vec_end + threadIdx.x; c < cols; c += 256) {
+    const float a = ld1<T>(p + c), b = ld1<T>(g + c), d = a - b;
+    dd += d * d; pg += a * b; pp += a * a; gg += b * b;
+  }
+  dd = wave_sum(dd); pg = wave_sum(pg); pp = wave_sum(pp); gg = wave_sum(gg);
+  if (lane == 0) { sq[0][wave] = dd; sq[1][wave] = pg; sq[2][wave] = pp; sq[3][wave] = gg; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = (sq[k][0] + sq[k][1]) + (sq[k][2] + sq[k][3]);
+    row_l2[row] = sqrtf(q[0]);
+    row_cos[row] = q[1] / (fmaxf(sqrtf(q[2]), 1e-8f) * fmaxf(sqrtf(q[3]), 1e-8f));
+  }
+}
+
+// acc[0..2] += (sum a, sum b, sum c) in float64 (c == nullptr: the row count): one workgroup, thread i adds rows i, i + 256,
+// ... in order, then a fixed tree
+__global__ __launch_bounds__(256) void eval_fold_kernel(const float* a, const float* b, const float* c, int rows, double* acc) {
+  __shared__ double ps[3][256];
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (int r = threadIdx.x; r < rows; r += 256) {
+    s0 += (double)a[r];
+    s1 += (double)b[r];
+    s2 += c ? (double)c[r] : 1.0;
+  }
+  ps[0][threadIdx.x] = s0; ps[1][threadIdx.x] = s1; ps[2][threadIdx.x] = s2;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) ps[k][threadIdx.x] += ps[k][threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) acc[threadIdx.x] += ps[threadIdx.x][0];
+}
+
 }  // namespace
 }  // namespace hero
 
 using namespace hero;
+
+extern "C" int hero_ce_eval(const void* logits, const long long* labels, int rows, int cols, int ld, int dtype, float inv_temp,
+                            long long ignore_index, double* acc, int32_t* pred, void* workspace, hero_stream_t stream) {
+  HERO_REQUIRE(rows >= 0 && cols > 0 && ld >= cols, "hero_ce_eval: bad dims rows=%d cols=%d ld=%d", rows, cols, ld);
+  HERO_REQUIRE(dtype == HERO_F32 || dtype == HERO_BF16, "hero_ce_eval: bad dtype %d", dtype);
+  HERO_REQUIRE(inv_temp > 0.f, "hero_ce_eval: inv_temp must be positive, got %g", (double)inv_temp);
+  if (rows == 0) return HERO_OK;
+  HERO_REQUIRE(logits && labels && acc && workspace, "hero_ce_eval: null pointer");
+  HERO_REQUIRE((((uintptr_t)logits) & 15) == 0, "hero_ce_eval: logits must be 16-byte aligned");
+  HERO_REQUIRE((((uintptr_t)acc) & 7) == 0 && (((uintptr_t)workspace) & 3) == 0 && (((uintptr_t)pred) & 3) == 0,
+               "hero_ce_eval: acc / workspace / pred misaligned");
+  float* ws = static_cast<float*>(workspace);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = by_dtype(dtype, "hero_ce_eval", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(ce_eval_kernel<T>, dim3(rows), dim3(256), 0, s, static_cast<const T*>(logits), labels, cols, ld, inv_temp, ignore_index,
+                       ws, ws + rows, ws + 2 * (size_t)rows, pred);
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(eval_fold_kernel, dim3(1), dim3(256), 0, s, ws, ws + rows, ws + 2 * (size_t)rows, rows, acc);
+  return check_launch("hero_ce_eval");
+}
+
+extern "C" int hero_feat_eval(const void* pred, const void* target, int rows, int cols, int ld_p, int ld_t, int dtype, double* acc,
+                              void* workspace, hero_stream_t stream) {
+  HERO_REQUIRE(rows >= 0 && cols > 0 && ld_p >= cols && ld_t >= cols, "hero_feat_eval: bad dims rows=%d cols=%d ld_p=%d ld_t=%d", rows, cols, ld_p,
+               ld_t);
+  HERO_REQUIRE(dtype == HERO_F32 || dtype == HERO_BF16, "hero_feat_eval: bad dtype %d", dtype);
+  if (rows == 0) return HERO_OK;
+  HERO_REQUIRE(pred && target && acc && workspace, "hero_feat_eval: null pointer");
+  HERO_REQUIRE(((((uintptr_t)pred) | ((uintptr_t)target)) & 15) == 0, "hero_feat_eval: pred / target must be 16-byte aligned");
+  HERO_REQUIRE((((uintptr_t)acc) & 7) == 0 && (((uintptr_t)workspace) & 3) == 0, "hero_feat_eval: acc / workspace misaligned");
+  float* ws = static_cast<float*>(workspace);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = by_dtype(dtype, "hero_feat_eval", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(feat_eval_kernel<T>, dim3(rows), dim3(256), 0, s, static_cast<const T*>(pred), static_cast<const T*>(target), cols, ld_p,
+                       ld_t, ws, ws + rows);
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(eval_fold_kernel, dim3(1), dim3(256), 0, s, ws, ws + rows, static_cast<const float*>(nullptr), rows, acc);
+  return check_launch("hero_feat_eval");
+}
 
 static int check_ce(const HeroCrossEntropy* a, bool bwd) {
   HERO_REQUIRE(a && a->logits && a->labels && a->lse, "hero_cross_entropy: null pointer");

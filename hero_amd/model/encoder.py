@@ -202,14 +202,25 @@ class CrossModalTrm(RobertaPreTrainedModel):
         pooled = self.pooler(seq) if self.run_pooler else None
         return (seq, pooled)
 
-    def forward_mlm(self, input_ids, position_ids, img_feat, img_pos_ids, attention_mask,
-                    gather_index, txt_mask_tgt, txt_labels=None, compute_loss=True):
+    def _mlm_masked_rows(self, input_ids, position_ids, img_feat, img_pos_ids, attention_mask, gather_index, txt_mask_tgt):
         emb = self._compute_img_txt_embeddings(input_ids, position_ids, img_feat, img_pos_ids,
                                                gather_index, attention_mask=attention_mask)
         seq = self.encoder(emb, attention_mask)[0]
         rows = HF.memo("mask_rows", (txt_mask_tgt,),     # once per batch object: nonzero synchronises (no graph capture)
                        lambda: torch.nonzero(txt_mask_tgt.reshape(-1), as_tuple=False).reshape(-1).to(torch.int32).contiguous())
-        masked = HF.GatherRowsFn.apply(seq.reshape(-1, seq.shape[-1]), None, rows)
+        return HF.GatherRowsFn.apply(seq.reshape(-1, seq.shape[-1]), None, rows)
+
+    def mlm_logits(self, batch):
+        """(logits, ncols) of an MLM batch: the vocabulary GEMM's own output [n_masked, vocab + padding] in the compute dtype
+        and the number of real columns - what hero_amd.pretrain_eval scores without the slice and the fp32 copy."""
+        masked = self._mlm_masked_rows(batch["input_ids"], batch["position_ids"], batch["v_feat"], batch["f_pos_ids"],
+                                       batch["attn_masks"], batch["gather_index"], batch["txt_mask_tgt"])
+        logits = self.lm_head(masked, raw=True)
+        return logits, logits.shape[1] - self.vocab_pad
+
+    def forward_mlm(self, input_ids, position_ids, img_feat, img_pos_ids, attention_mask,
+                    gather_index, txt_mask_tgt, txt_labels=None, compute_loss=True):
+        masked = self._mlm_masked_rows(input_ids, position_ids, img_feat, img_pos_ids, attention_mask, gather_index, txt_mask_tgt)
         if compute_loss:      # fused log-softmax + NLL over the vocabulary GEMM output, padding columns excluded
             logits = self.lm_head(masked, raw=True)
             return HF.cross_entropy(logits, txt_labels, ncols=logits.shape[1] - self.vocab_pad)

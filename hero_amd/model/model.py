@@ -218,19 +218,31 @@ class HierarchicalVlModel(VideoPreTrainedModel):
             return F.mse_loss(pred, targets, reduction="none")
         return self.mfm_nce(pred, targets, neg)
 
-    def mfm_nce(self, masked_output, pos_output, neg_output, compute_loss=True):
+    def mfm_nce_logits(self, masked_output, pos_output, neg_output):
+        """(logits, n): the candidate GEMM's own output [n_masked, n_masked + n_neg (+ padding)] in the compute dtype,
+        undivided by the temperature, and its number of real columns."""
         cd = HF.compute_dtype()
         cand = torch.cat([pos_output, neg_output], 0)
         n = cand.shape[0]
         if n % 8:                                               # GEMM column granularity; the loss ignores the padding
             cand = torch.cat([cand, cand.new_zeros(8 - n % 8, cand.shape[1])], 0)
-        logits = HF.matmul_nt(HF.cast(masked_output, cd), HF.cast(cand, cd))      # [n_masked, n_masked + n_neg (+pad)]
+        return HF.matmul_nt(HF.cast(masked_output, cd), HF.cast(cand, cd)), n    # [n_masked, n_masked + n_neg (+pad)]
+
+    def mfm_nce(self, masked_output, pos_output, neg_output, compute_loss=True):
+        logits, n = self.mfm_nce_logits(masked_output, pos_output, neg_output)
         if not compute_loss:
             return logits[:, :n].float()
         tgt = torch.arange(masked_output.size(0), device=logits.device)
         return HF.cross_entropy(logits, tgt, ncols=n, inv_temp=1.0 / self.nce_temp)
 
-    def forward_fom(self, batch, compute_loss=True):
+    def mlm_logits(self, batch):
+        return self.f_encoder.mlm_logits(defaultdict(lambda: None, batch))
+
+    def fom_logits(self, batch):
+        """[B * L, max_clip_len] frame-order logits as the head's GEMM wrote them (no fp32 copy)."""
+        return self.forward_fom(defaultdict(lambda: None, batch), compute_loss=False, raw=True)
+
+    def forward_fom(self, batch, compute_loss=True, raw=False):
         order = batch["shuffled_orders"]
         feats = self.forward_repr(batch, encode_clip=False)               # (B, L, D) fp32
         B, Lc, D = feats.shape
@@ -242,7 +254,10 @@ class HierarchicalVlModel(VideoPreTrainedModel):
         shuffled = HF.GatherRowsFn.apply(feats.reshape(B * Lc, D), None, inv).view(B, Lc, D)
         enc = self.c_encoder(clip_level_frame_feat=shuffled, clip_level_pos_ids=None,
                              attention_mask=batch["c_attn_masks"])
-        logits = HF.cast(self.fom_output(enc.reshape(B * Lc, D)), torch.float32)
+        logits = self.fom_output(enc.reshape(B * Lc, D))
+        if raw:
+            return logits
+        logits = HF.cast(logits, torch.float32)
         if compute_loss:                                        # mean over the rows that carry a target
             tgt = batch["targets"].reshape(-1)
             rows = HF.cross_entropy(logits, tgt, ignore_index=-1)

@@ -57,6 +57,7 @@ const char* hero_last_error(void);
  * top-p, a Gumbel-max draw) were ADDED the same way.
  * Still 3: hero_caption_score and hero_caption_in_envelope (BLEU statistics, ROUGE-L and CIDEr-D of decoded id rows against
  * packed reference tables) were ADDED the same way.
+ * Still 3: hero_ce_eval and hero_feat_eval (the validation counters of the pre-training heads) were ADDED the same way.
  * INTEGRATION.md section 2 lists the breaks per version. */
 #define HERO_ABI_VERSION 3
 int hero_abi_version(void);
@@ -891,6 +892,27 @@ int hero_smooth_ce_fwd(const void* logits, const long long* labels, float* loss,
 int hero_smooth_ce_bwd(const void* logits, const long long* labels, const float* lse, const float* dloss, const float* dloss_rows,
                        const float* mean_cnt, void* dlogits, int rows, int cols, int ld, int dtype, double eps,
                        long long ignore_index, hero_stream_t stream);
+
+/* Validation counters of the pre-training heads (pretrain.py:462-608: validate_mlm / _mffr / _mfm_nce / _fom), one pass over  */
+/* the raw head outputs, counters kept on the device.                                                                          */
+/* hero_ce_eval: logits [rows, ld] (fp32 / bf16, 16-byte aligned), the first `cols` columns count, x = logits * inv_temp        */
+/* (inv_temp > 0).  A row is valid when its label is not ignore_index and lies in [0, cols).  Per valid row: loss = lse(x[:cols]) */
+/* - x[label] in fp32, the arithmetic of hero_cross_entropy_fwd; prediction = the lowest column among those whose STORED value  */
+/* (converted to fp32, unscaled; -0 equals +0) is the row maximum - a column in [cols, ld) never wins; the row is correct when   */
+/* the prediction equals the label.  acc[0..2] += (sum of the valid rows' losses, rows correct, rows valid) in float64: the two */
+/* counts are exact integers.  pred (optional, int32 [rows]) is written for every row, valid or not.  NaN logits are not        */
+/* ordered: a row that holds one has an unspecified prediction.                                                                */
+/* hero_feat_eval: per row of pred [rows, ld_p] / target [rows, ld_t] (one dtype, 16-byte aligned) over `cols` columns, sums in */
+/* fp32: l2 = sqrt(sum (p - t)^2), cos = p.t / (max(|p|, 1e-8) * max(|t|, 1e-8)) (F.cosine_similarity; a zero row gives 0).      */
+/* acc[0..2] += (sum l2, sum cos, rows) in float64.                                                                            */
+/* Both: a 256-thread workgroup per row writes the row results to `workspace` (at least 12 * rows bytes for hero_ce_eval,       */
+/* 8 * rows bytes for hero_feat_eval, 4-byte aligned; contents unspecified afterwards), then ONE workgroup adds them to acc in  */
+/* a fixed order - no atomics, two runs give the same bits.  rows == 0: no launch, acc untouched.  Nothing is read on the host; */
+/* both launches can be captured into a hipGraph.  Plain arguments: a backward-compatible addition, HERO_ABI_VERSION stays.     */
+int hero_ce_eval(const void* logits, const long long* labels, int rows, int cols, int ld, int dtype, float inv_temp,
+                 long long ignore_index, double* acc, int32_t* pred, void* workspace, hero_stream_t stream);
+int hero_feat_eval(const void* pred, const void* target, int rows, int cols, int ld_p, int ld_t, int dtype, double* acc,
+                   void* workspace, hero_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Collate on the device: the index tensors of a batch from per-subtitle / per-video length      */
