@@ -21,9 +21,10 @@ EXPORTS = [
     "hero_layernorm_bwd_workspace_bytes", "hero_layernorm_bwd", "hero_colsum_workspace_bytes",
     "hero_colsum", "hero_colsum_multi", "hero_colsum_multi_workspace_bytes", "hero_layernorm_bwd_blocks", "hero_attention_fwd", "hero_attention_bwd", "hero_attention_max_len", "hero_attention_max_packed_len", "hero_attention_stats_ok", "hero_attention_force_ppw",
     "hero_gather_rows", "hero_inverse_first", "hero_csr_gather_sum", "hero_scatter_add_rows", "hero_segment_sort_workspace_bytes", "hero_scatter_add_sorted_workspace_bytes", "hero_segment_sort", "hero_scatter_add_sorted", "hero_cast", "hero_transpose_cast", "hero_copy_multi",
-    "hero_relu_bwd", "hero_gelu_bwd", "hero_add", "hero_sumsq", "hero_adamw", "hero_adamw_multi", "hero_adamw_multi_chunk",
+    "hero_relu_bwd", "hero_gelu_bwd", "hero_add", "hero_sumsq", "hero_adamw", "hero_adamw_multi", "hero_adamw_multi_gated", "hero_adamw_multi_chunk",
     "hero_query_pool_fwd", "hero_query_pool_bwd", "hero_rownorm_fwd", "hero_rownorm_bwd", "hero_score_max_fwd",
     "hero_score_max_bwd", "hero_rank_loss", "hero_sums_scaled", "hero_st_ed_fwd", "hero_st_ed_bwd", "hero_st_ed_bwd_workspace_bytes",
+    "hero_st_ed_fwd_gated", "hero_st_ed_bwd_gated",
     "hero_cross_entropy_fwd", "hero_cross_entropy_bwd", "hero_qa_pool_fwd", "hero_qa_pool_bwd",
     "hero_frame_pool_fwd", "hero_frame_pool_bwd", "hero_bce_head_fwd", "hero_bce_head_bwd",
     "hero_dec_attention_in_envelope", "hero_dec_attention_fwd", "hero_dec_attention_bwd", "hero_smooth_ce_fwd", "hero_smooth_ce_bwd",
@@ -260,6 +261,9 @@ def lib():
         L.hero_sumsq.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hero_adamw.argtypes = [C.POINTER(AdamW), C.c_void_p]
         L.hero_adamw_multi.argtypes = [C.POINTER(AdamWMulti), C.c_void_p]
+        L.hero_adamw_multi_gated.argtypes = [C.POINTER(AdamWMulti), C.c_void_p, C.c_void_p]
+        L.hero_st_ed_fwd_gated.argtypes = [C.POINTER(StEd), C.c_void_p, C.c_void_p]
+        L.hero_st_ed_bwd_gated.argtypes = [C.POINTER(StEd), C.c_void_p, C.c_void_p]
         L.hero_copy_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         for fn, st in (("hero_query_pool_fwd", QueryPool), ("hero_query_pool_bwd", QueryPool),
                        ("hero_rownorm_fwd", RowNorm), ("hero_rownorm_bwd", RowNorm),

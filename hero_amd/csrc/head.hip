@@ -233,7 +233,13 @@ __global__ __launch_bounds__(256) void rank_loss_kernel(HeroRankLoss a) {
 constexpr int MAXK = 15;
 
 template <typename T>
-__global__ __launch_bounds__(256) void st_ed_fwd_kernel(HeroStEd a) {
+__global__ __launch_bounds__(256) void st_ed_fwd_kernel(HeroStEd a, const int32_t* gate) {
+  // gate (hero_st_ed_fwd_gated): one device word, the same for every workgroup - a uniform branch above the first barrier.
+  // Off: the pair's loss row is +0 and nothing else is read or written (p_st / p_ed / sim keep what they held).
+  if (gate && *gate == 0) {
+    if (threadIdx.x == 0) a.loss_rows[blockIdx.x] = 0.f;
+    return;
+  }
   extern __shared__ float sm[];                      // sim[L], lg[2][L]
   __shared__ float red[4];
   float* sim = sm;
@@ -306,7 +312,18 @@ __global__ __launch_bounds__(256) void st_ed_fwd_kernel(HeroStEd a) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void st_ed_bwd_kernel(HeroStEd a) {
+__global__ __launch_bounds__(256) void st_ed_bwd_kernel(HeroStEd a, const int32_t* gate) {
+  // gate (hero_st_ed_bwd_gated): the same device word in every workgroup, so ALL of them leave here or none does - above the
+  // first barrier and above the ticket, which then sees either B arrivals or none (the counter stays at zero).  Off: exact +0
+  // into this pair's dq2 / dctx rows; no saved tensor, no upstream gradient, no workspace and no dw_st / dw_ed is touched.
+  if (gate && *gate == 0) {
+    T* dctx = static_cast<T*>(a.dctx) + (size_t)blockIdx.x * a.L * a.D;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    const size_t n = (size_t)a.L * a.D;              // D % 4 == 0: whole 4-element segments
+    for (size_t i = (size_t)threadIdx.x * 4; i < n; i += 1024) V4<T>::st(dctx + i, z);
+    for (int d = threadIdx.x * 4; d < a.D; d += 1024) *reinterpret_cast<float4*>(a.dq2 + (size_t)blockIdx.x * a.D + d) = z;
+    return;
+  }
   extern __shared__ float sm[];                      // dl[2][L], dsim[L], sim[L]
   __shared__ float red[4];
   float* dl = sm;
@@ -494,19 +511,20 @@ extern "C" int hero_rank_loss(const HeroRankLoss* a, hero_stream_t stream) {
   return check_launch("hero_rank_loss");
 }
 
-extern "C" int hero_st_ed_fwd(const HeroStEd* a, hero_stream_t stream) {
+extern "C" int hero_st_ed_fwd_gated(const HeroStEd* a, const int32_t* gate, hero_stream_t stream) {
   HERO_REQUIRE(a && a->q2 && a->ctx && a->mask && a->w_st && a->w_ed && a->targets && a->loss_rows && a->p_st && a->p_ed && a->sim,
                "hero_st_ed_fwd: null pointer");
   HERO_REQUIRE(a->L > 0 && a->L <= 2048 && a->D % 4 == 0 && a->K >= 1 && a->K <= MAXK && (a->K & 1), "hero_st_ed_fwd: bad dims L=%d D=%d K=%d",
                a->L, a->D, a->K);
   if (a->B <= 0) return HERO_OK;
   return by_dtype(a->dtype, "hero_st_ed_fwd", [&](auto tag) {
-    hipLaunchKernelGGL((st_ed_fwd_kernel<typename decltype(tag)::type>), dim3(a->B), dim3(256), 3 * a->L * sizeof(float), static_cast<hipStream_t>(stream), *a);
+    hipLaunchKernelGGL((st_ed_fwd_kernel<typename decltype(tag)::type>), dim3(a->B), dim3(256), 3 * a->L * sizeof(float), static_cast<hipStream_t>(stream), *a, gate);
   });
 }
+extern "C" int hero_st_ed_fwd(const HeroStEd* a, hero_stream_t stream) { return hero_st_ed_fwd_gated(a, nullptr, stream); }
 extern "C" size_t hero_st_ed_bwd_workspace_bytes(int B) { return ((size_t)(B > 0 ? B : 0) * 2 * (MAXK + 1) + 4) * sizeof(float); }
 
-extern "C" int hero_st_ed_bwd(const HeroStEd* a, hero_stream_t stream) {
+extern "C" int hero_st_ed_bwd_gated(const HeroStEd* a, const int32_t* gate, hero_stream_t stream) {
   HERO_REQUIRE(a && a->q2 && a->ctx && a->mask && a->w_st && a->w_ed && a->targets && a->p_st && a->p_ed && a->sim && a->g && a->dq2 && a->dctx,
                "hero_st_ed_bwd: null pointer");
   HERO_REQUIRE(a->L > 0 && a->L <= 2048 && a->D % 4 == 0 && a->K >= 1 && a->K <= MAXK && (a->K & 1), "hero_st_ed_bwd: bad dims L=%d D=%d K=%d",
@@ -514,9 +532,10 @@ extern "C" int hero_st_ed_bwd(const HeroStEd* a, hero_stream_t stream) {
   HERO_REQUIRE(a->ws || !(a->dw_st || a->dw_ed), "hero_st_ed_bwd: dw_st / dw_ed need the workspace (hero_st_ed_bwd_workspace_bytes)");
   if (a->B <= 0) return HERO_OK;
   return by_dtype(a->dtype, "hero_st_ed_bwd", [&](auto tag) {
-    hipLaunchKernelGGL((st_ed_bwd_kernel<typename decltype(tag)::type>), dim3(a->B), dim3(256), 4 * a->L * sizeof(float), static_cast<hipStream_t>(stream), *a);
+    hipLaunchKernelGGL((st_ed_bwd_kernel<typename decltype(tag)::type>), dim3(a->B), dim3(256), 4 * a->L * sizeof(float), static_cast<hipStream_t>(stream), *a, gate);
   });
 }
+extern "C" int hero_st_ed_bwd(const HeroStEd* a, hero_stream_t stream) { return hero_st_ed_bwd_gated(a, nullptr, stream); }
 
 extern "C" int hero_sums_scaled(const float* src, int n_segs, int seg_len, const float* scales, float* out, hero_stream_t stream) {
   HERO_REQUIRE(src && out && scales && n_segs >= 1 && n_segs <= 4 && seg_len >= 1, "hero_sums_scaled: 1..4 segments of >= 1 element");

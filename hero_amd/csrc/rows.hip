@@ -511,12 +511,16 @@ __global__ void adamw_kernel(HeroAdamW a, float bc1, float bc2) {
 // One launch over many tensors (descriptor tables live in device memory, one block per 16K-element
 // chunk).  Same arithmetic as adamw_kernel.
 constexpr int MT_CHUNK = 16384;
-__global__ void adamw_steps_inc_kernel(const HeroTensorDesc* descs, int n, int32_t* steps) {
+// tensor_gate (hero_adamw_multi_gated): one device word per descriptor, or NULL.  A tensor whose word is 0 is skipped as a whole -
+// its step count stays, and every chunk workgroup of it leaves before it reads or writes p, g, m or v: the reference's
+// `if p.grad is None: continue` (optim/adamw.py), decided on the device.
+__global__ void adamw_steps_inc_kernel(const HeroTensorDesc* descs, int n, int32_t* steps, const int32_t* tensor_gate) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) steps[descs[i].step_lag] += 1;            // slots are distinct per tensor
+  if (i < n && !(tensor_gate && tensor_gate[i] == 0)) steps[descs[i].step_lag] += 1;            // slots are distinct per tensor
 }
-__global__ __launch_bounds__(256) void adamw_multi_kernel(HeroAdamWMulti a) {
+__global__ __launch_bounds__(256) void adamw_multi_kernel(HeroAdamWMulti a, const int32_t* tensor_gate) {
   const int ti = a.chunk_tensor[blockIdx.x];
+  if (tensor_gate && tensor_gate[ti] == 0) return;     // uniform over the workgroup
   const HeroTensorDesc d = a.descs[ti];
   const HeroAdamWGroup gr = a.groups[d.group];
   const size_t beg = (size_t)a.chunk_index[blockIdx.x] * MT_CHUNK;
@@ -782,18 +786,21 @@ extern "C" int hero_adamw(const HeroAdamW* a, hero_stream_t stream) {
   return check_launch("hero_adamw");
 }
 
-extern "C" int hero_adamw_multi(const HeroAdamWMulti* a, hero_stream_t stream) {
+extern "C" int hero_adamw_multi_gated(const HeroAdamWMulti* a, const int32_t* tensor_gate, hero_stream_t stream) {
   HERO_REQUIRE(a && a->descs && a->chunk_tensor && a->chunk_index, "hero_adamw_multi: null pointer");
   HERO_REQUIRE(a->step >= 1 || a->step_ptr || a->tensor_steps, "hero_adamw_multi: step must be >= 1");
+  // a skipped tensor's step count must stay behind the others': only the per-tensor device counters can do that
+  HERO_REQUIRE(!tensor_gate || (a->tensor_steps && a->n_tensors > 0), "hero_adamw_multi_gated: a gate table needs tensor_steps and n_tensors");
   if (a->n_chunks <= 0) return HERO_OK;
   if (a->tensor_steps) {
     HERO_REQUIRE(a->n_tensors > 0, "hero_adamw_multi: tensor_steps needs n_tensors");
     hipLaunchKernelGGL(adamw_steps_inc_kernel, dim3((a->n_tensors + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a->descs,
-                       a->n_tensors, a->tensor_steps);
+                       a->n_tensors, a->tensor_steps, tensor_gate);
     const int rc = check_launch("hero_adamw_multi(steps)");
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(adamw_multi_kernel, dim3(a->n_chunks), dim3(256), 0, static_cast<hipStream_t>(stream), *a);
+  hipLaunchKernelGGL(adamw_multi_kernel, dim3(a->n_chunks), dim3(256), 0, static_cast<hipStream_t>(stream), *a, tensor_gate);
   return check_launch("hero_adamw_multi");
 }
+extern "C" int hero_adamw_multi(const HeroAdamWMulti* a, hero_stream_t stream) { return hero_adamw_multi_gated(a, nullptr, stream); }
 extern "C" int hero_adamw_multi_chunk(void) { return MT_CHUNK; }

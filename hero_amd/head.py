@@ -6,6 +6,7 @@ every other training configuration keeps the PyTorch formulation in that module,
 parity tests compare these nodes against.  Inference over a whole corpus (eval_vcmr.py) has its own forward-only
 kernels: hero_amd/retrieval.py."""
 import ctypes as C
+import random
 
 import torch
 
@@ -160,13 +161,54 @@ def _sted_workspace(B, dev):
     return t
 
 
+class StEdGate:
+    """The per-step draw of the start / end term (model/pretrain.py:74-75: `random.random() > drop_svmr_prob`) as device
+    words, so that ONE captured launch sequence serves both outcomes.  `gate` (int32[1]) is what the head kernels read
+    (hero_st_ed_fwd_gated / hero_st_ed_bwd_gated); `used` (int32[1]) is what the gated AdamW reads for the parameters only
+    this term reaches: 1 iff at least one micro-step of the accumulation window had the gate on - the reference's
+    `if p.grad is None: continue`.  The host keeps a mirror (`on`, and the window's OR) and never reads the words back."""
+
+    def __init__(self, device):
+        self.gate = torch.zeros(1, dtype=torch.int32, device=device)
+        self.used = torch.zeros(1, dtype=torch.int32, device=device)
+        self.on = False               # host mirror of `gate`
+        self.window = False           # OR of `on` over the micro-steps since the last close_window()
+        self.tensor_gates = {}        # parameter -> device word, for AdamW.step(tensor_gates=...): filled by attach()
+
+    def attach(self, model):
+        """Make `model` run its start / end term behind this gate (HeroForPretraining.st_ed_gate)."""
+        model.st_ed_gate = self
+        self.tensor_gates = {p: self.used for p in model.st_ed_only_parameters()}
+        return self
+
+    def set(self, on):
+        """Stream-ordered scalar fill (no pinned buffer, no host synchronisation)."""
+        self.on = bool(on)
+        self.gate.fill_(int(self.on))
+        self.window = self.window or self.on
+
+    def draw(self, p):
+        """One number from `random`, as the model's eager branch draws it: after random.seed(s) a gated run sees the draws
+        of a classic eager run."""
+        self.set(random.random() > p)
+        return self.on
+
+    def close_window(self):
+        """Before the boundary micro-step's optimiser launch: `used` = the window's OR; a new window starts."""
+        used, self.window = self.window, False
+        self.used.fill_(int(used))
+        return used
+
+
 class StEdLossFn(torch.autograd.Function):
     """loss_st_ed of matched (query, video) pairs: similarity, the two 1-D convolutions, mask_logits
     and both cross-entropies (model/pretrain.py:96-110, 128-166) -> scalar."""
 
     @staticmethod
-    def forward(ctx, q2, ctxf, mask, w_st, w_ed, targets, weight=1.0):
-        """weight: lw_st_ed, folded into the final sum and the backward's upstream gradient."""
+    def forward(ctx, q2, ctxf, mask, w_st, w_ed, targets, weight=1.0, gate=None):
+        """weight: lw_st_ed, folded into the final sum and the backward's upstream gradient.
+        gate: a StEdGate - the gated entry points run and read its device word (off: zero loss, zero gradients); None: the
+        plain ones."""
         B, Lc, D = ctxf.shape
         q2, ctxf, mask = _f32c(q2), ctxf.contiguous(), _f32c(mask)
         dev = q2.device
@@ -176,9 +218,13 @@ class StEdLossFn(torch.autograd.Function):
         saved = torch.empty((3, B, Lc), dtype=torch.float32, device=dev)      # p_st, p_ed, sim
         a = StEdLossFn._args(q2, ctxf, mask, w_st, w_ed, tg, saved, K)
         a.loss_rows = L.ptr(rows)
-        L.check(L.lib().hero_st_ed_fwd(C.byref(a), L.stream()))
+        if gate is None:
+            L.check(L.lib().hero_st_ed_fwd(C.byref(a), L.stream()))
+        else:
+            L.check(L.lib().hero_st_ed_fwd_gated(C.byref(a), L.ptr(gate.gate), L.stream()))
         ctx.save_for_backward(q2, ctxf, mask, tg, saved)
         ctx.ws = (w_st, w_ed)
+        ctx.gate = gate
         ctx.weight = float(weight)
         HF._use(w_st, w_ed)
         out = torch.empty((1,), dtype=torch.float32, device=dev)
@@ -215,9 +261,12 @@ class StEdLossFn(torch.autograd.Function):
         a.g_scale = ctx.weight
         a.dq2, a.dctx, a.dw_st, a.dw_ed = L.ptr(dq2), L.ptr(dctx), L.ptr(dws), L.ptr(dwe)
         a.ws = L.ptr(_sted_workspace(q2.shape[0], dev))
-        L.check(L.lib().hero_st_ed_bwd(C.byref(a), L.stream()))
+        if ctx.gate is None:
+            L.check(L.lib().hero_st_ed_bwd(C.byref(a), L.stream()))
+        else:
+            L.check(L.lib().hero_st_ed_bwd_gated(C.byref(a), L.ptr(ctx.gate.gate), L.stream()))
         if sink:
             HF.SINK.done(w_st)
             HF.SINK.done(w_ed)
-            return dq2, dctx, None, None, None, None, None
-        return dq2, dctx, None, dws.view_as(w_st), dwe.view_as(w_ed), None, None
+            return dq2, dctx, None, None, None, None, None, None
+        return dq2, dctx, None, dws.view_as(w_st), dwe.view_as(w_ed), None, None, None

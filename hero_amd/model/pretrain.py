@@ -38,6 +38,11 @@ class HeroForPretraining(HeroModel):
         self.gather_gpus = True
         self.fuse_query_pass = True   # subtitle rows and query rows share the cross-modal layer launches
         self.fused_head = True        # loss head on the hero_* head kernels when the configuration allows
+        # hero_amd.head.StEdGate, or None.  Attached (in training, lw_st_ed != 0): the start / end term is ALWAYS part of the
+        # step and a device word decides whether it counts; the model draws nothing - whoever owns the gate draws
+        # (TrainStep, once per micro-step) - so the step can be captured once and replayed under either outcome.
+        self.st_ed_gate = None
+        self.head_generation = 0      # grows when set_hard_negative / set_train_st_ed change a value: captured steps are stale
         self.video_query_linear = nn.Linear(config.q_config.hidden_size, config.c_config.hidden_size)
         conv = dict(in_channels=1, out_channels=1, kernel_size=conv_kernel_size, stride=conv_stride,
                     padding=conv_kernel_size // 2, bias=False)
@@ -77,8 +82,9 @@ class HeroForPretraining(HeroModel):
             return self._fused_losses(batch, frame_embeddings, modularized_query)
 
         q2video_scores = st_prob = ed_prob = None
+        gate = self.st_ed_gate if self.training else None
         if self.lw_st_ed != 0:
-            if random.random() > self.drop_svmr_prob or not self.training:
+            if gate is not None or random.random() > self.drop_svmr_prob or not self.training:
                 st_prob, ed_prob = self.get_pred_from_mod_query(
                     frame_embeddings, batch["c_attn_masks"], modularized_query)
         if self.lw_neg_ctx != 0 or self.lw_neg_q != 0:
@@ -97,6 +103,8 @@ class HeroForPretraining(HeroModel):
             tg = batch["targets"]
             loss_st_ed = (F.cross_entropy(st_prob, tg[:, 0].long(), reduction=reduction, ignore_index=-1)
                           + F.cross_entropy(ed_prob, tg[:, 1].long(), reduction=reduction, ignore_index=-1))
+            if gate is not None:                             # the device word as a factor: no host read, capturable
+                loss_st_ed = loss_st_ed * gate.gate.to(loss_st_ed.dtype)[0]
         if q2video_scores is not None:
             loss_neg_ctx, loss_neg_q = self.get_video_level_loss(q2video_scores, reduction)
         return (self.lw_st_ed * loss_st_ed, self.lw_neg_ctx * loss_neg_ctx,
@@ -125,7 +133,8 @@ class HeroForPretraining(HeroModel):
         from ..head import RowNormFn, StEdLossFn, VideoRankLossFn
         loss_st_ed = loss_neg_ctx = loss_neg_q = None        # a zero tensor only for a term that is really absent (no fill otherwise)
         cmask = batch["c_attn_masks"]
-        if self.lw_st_ed != 0 and random.random() > self.drop_svmr_prob:       # model/pretrain.py:74-75
+        gate = self.st_ed_gate
+        if self.lw_st_ed != 0 and (gate is not None or random.random() > self.drop_svmr_prob):       # model/pretrain.py:74-75
             q2 = HF.linear(modularized_query, self.video_query_linear.weight, self.video_query_linear.bias)
             ctx_pairs, mask_pairs = frame_embeddings, cmask
             if modularized_query.shape[0] != frame_embeddings.shape[0]:
@@ -135,7 +144,7 @@ class HeroForPretraining(HeroModel):
                 mask_pairs = HF.memo("pair_mask", (cmask, batch["q_vidx"]),          # fp32 at once: what the head kernels read
                                        lambda: cmask.index_select(0, batch["q_vidx"].reshape(-1)).to(torch.float32).contiguous())
             loss_st_ed = StEdLossFn.apply(q2, ctx_pairs, mask_pairs, self.video_st_predictor.weight,
-                                          self.video_ed_predictor.weight, batch["targets"], float(self.lw_st_ed))
+                                          self.video_ed_predictor.weight, batch["targets"], float(self.lw_st_ed), gate)
         if self.lw_neg_ctx != 0 or self.lw_neg_q != 0:
             qn = RowNormFn.apply(modularized_query, 1e-5)
             cn = RowNormFn.apply(frame_embeddings, 1e-5)
@@ -258,10 +267,18 @@ class HeroForPretraining(HeroModel):
         m = context_mask.transpose(0, 1).unsqueeze(0).to(scores.dtype)
         return mask_logits(scores, m).max(dim=1)[0]
 
+    def st_ed_only_parameters(self):
+        """The parameters nothing but the start / end term reaches: what a step that drops the term leaves alone."""
+        return [self.video_query_linear.weight, self.video_query_linear.bias,
+                self.video_st_predictor.weight, self.video_ed_predictor.weight]
+
     def set_hard_negative(self, use_hard_negative, hard_pool_size, hard_neg_weight):
-        self.use_hard_negative = use_hard_negative
-        self.hard_pool_size = hard_pool_size
-        self.hard_neg_weight = hard_neg_weight
+        new = (use_hard_negative, hard_pool_size, hard_neg_weight)
+        if new != (self.use_hard_negative, self.hard_pool_size, self.hard_neg_weight):
+            self.head_generation += 1
+        self.use_hard_negative, self.hard_pool_size, self.hard_neg_weight = new
 
     def set_train_st_ed(self, lw_st_ed):
+        if lw_st_ed != self.lw_st_ed:
+            self.head_generation += 1
         self.lw_st_ed = lw_st_ed

@@ -83,7 +83,7 @@ class AdamW(Optimizer):
                 self.state[p]["step"] = host[i]
         self._global_step = max([self._global_step] + host)
 
-    def _build_table(self, active, slots=False):
+    def _build_table(self, active, slots=False, gates=None):
         chunk = L.lib().hero_adamw_multi_chunk()
         descs = (L.TensorDesc * len(active))()
         ct, ci = [], []
@@ -101,15 +101,41 @@ class AdamW(Optimizer):
         raw = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
         t_ct = torch.from_numpy(np.asarray(ct, dtype=np.int32)).to(dev)
         t_ci = torch.from_numpy(np.asarray(ci, dtype=np.int32)).to(dev)
-        return raw, t_ct, t_ci, len(ct)
+        return raw, t_ct, t_ci, len(ct), self._build_gate_table(active, gates, dev)
+
+    @staticmethod
+    def _gated(active, gates):
+        """(descriptor index, gate word) of the active parameters that have a gate."""
+        return [(i, gates[p]) for i, (_, p) in enumerate(active) if p in gates] if gates else []
+
+    def _build_gate_table(self, active, gates, dev):
+        """The per-descriptor gate table of hero_adamw_multi_gated (int32 [n active], 1 = update) and, per distinct gate
+        word, the descriptors that follow it: _launch copies the word into their entries on the device."""
+        gated = self._gated(active, gates)
+        if not gated:
+            return None
+        table = torch.ones(len(active), dtype=torch.int32, device=dev)
+        follow = []
+        for word in {id(w): w for _, w in gated}.values():
+            idx = [i for i, w in gated if w is word]
+            follow.append((torch.tensor(idx, dtype=torch.int64, device=dev), word, len(idx)))
+        return table, follow
 
     @torch.no_grad()
     def step(self, closure=None, grad_sumsq=None, max_grad_norm=0.0, grad_scale=1.0, skip=None,
-             step_tensor=None, lr_tensor=None):
+             step_tensor=None, lr_tensor=None, tensor_gates=None):
         """step_tensor (int32[1]) / lr_tensor (float32[8]) on the device override the host-side step
-        count and per-group learning rates — required when the step is captured in a hipGraph."""
+        count and per-group learning rates — required when the step is captured in a hipGraph.
+        tensor_gates: {parameter: int32[1] device word} (or an object carrying such a mapping as `.tensor_gates`,
+        hero_amd.head.StEdGate): a parameter whose word is 0 WHEN THE KERNEL RUNS is skipped, state and step count
+        included - the `p.grad is None` rule for a gradient whose presence only the device knows.  Needs step_tensor
+        (per-parameter step counts on the device)."""
         loss = closure() if closure is not None else None
         device_state = step_tensor is not None
+        gates = getattr(tensor_gates, "tensor_gates", tensor_gates) or None
+        if gates and not device_state:
+            raise RuntimeError("AdamW.step(tensor_gates=...) needs the device-side step counts (step_tensor): a host-side "
+                               "step count cannot follow a skip that is decided on the device")
         if not device_state:
             if self._tsteps is not None:                 # back from device-state mode: the device counters are the truth
                 self.sync_steps_from_device()
@@ -132,19 +158,20 @@ class AdamW(Optimizer):
             return loss
         tsteps = self._device_steps(active[0][1].device) if device_state else None
         self.last_active = active
-        raw, t_ct, t_ci, n_chunks = self._table_for(active, device_state)
-        return self._launch(raw, t_ct, t_ci, n_chunks, len(active), tsteps, grad_sumsq, max_grad_norm, grad_scale, step_tensor, lr_tensor, loss)
+        raw, t_ct, t_ci, n_chunks, gate_table = self._table_for(active, device_state, gates)
+        return self._launch(raw, t_ct, t_ci, n_chunks, len(active), tsteps, grad_sumsq, max_grad_norm, grad_scale, step_tensor, lr_tensor, loss,
+                            gate_table)
 
-    def prebuild(self, active, device_state=True):
+    def prebuild(self, active, device_state=True, tensor_gates=None):
         """Build (outside any stream capture) the descriptor table a later captured step() over the same parameters will
         need: a table holds the addresses of the parameters' straight compute copies, and a copy created since the last
         capture (another task's first forward) means a new table - whose upload is not capturable.  TrainStep calls this
         before it re-captures a task."""
         if active:
             self._device_steps(active[0][1].device)
-            self._table_for(list(active), device_state)
+            self._table_for(list(active), device_state, getattr(tensor_gates, "tensor_gates", tensor_gates) or None)
 
-    def _table_for(self, active, device_state):
+    def _table_for(self, active, device_state, gates=None):
         if device_state:
             # per-parameter counts live on the device and are advanced by the kernel for the ACTIVE parameters only:
             # graphs of other tasks never touch the counters of parameters they skip (the reference's state['step'],
@@ -154,9 +181,13 @@ class AdamW(Optimizer):
         else:
             sig = tuple((id(p), p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(),
                          self.state[p]["exp_avg_sq"].data_ptr(), self._global_step - self.state[p]["step"]) for _, p in active)
-        return self._tables.get(sig, lambda: self._build_table(active, slots=device_state))
+        gated = self._gated(active, gates)
+        if gated:
+            sig = sig + (("gates",) + tuple((i, w.data_ptr()) for i, w in gated),)
+        return self._tables.get(sig, lambda: self._build_table(active, slots=device_state, gates=gates))
 
-    def _launch(self, raw, t_ct, t_ci, n_chunks, n_active, tsteps, grad_sumsq, max_grad_norm, grad_scale, step_tensor, lr_tensor, loss):
+    def _launch(self, raw, t_ct, t_ci, n_chunks, n_active, tsteps, grad_sumsq, max_grad_norm, grad_scale, step_tensor, lr_tensor, loss,
+                gate_table=None):
         a = L.AdamWMulti()
         a.descs, a.chunk_tensor, a.chunk_index, a.n_chunks = raw.data_ptr(), t_ct.data_ptr(), t_ci.data_ptr(), n_chunks
         for gi, group in enumerate(self.param_groups):
@@ -167,6 +198,12 @@ class AdamW(Optimizer):
         a.tensor_steps, a.n_tensors = L.ptr(tsteps), n_active
         a.grad_sumsq = L.ptr(grad_sumsq)
         a.max_grad_norm, a.grad_scale = max_grad_norm, grad_scale
-        L.check(L.lib().hero_adamw_multi(C.byref(a), L.stream()))
+        if gate_table is None:
+            L.check(L.lib().hero_adamw_multi(C.byref(a), L.stream()))
+        else:
+            table, follow = gate_table
+            for idx, word, n in follow:                  # device-to-device, capturable: the entries take their word's value of NOW
+                table.index_copy_(0, idx, word.expand(n))
+            L.check(L.lib().hero_adamw_multi_gated(C.byref(a), L.ptr(table), L.stream()))
         HF.notify_weights_updated()
         return loss

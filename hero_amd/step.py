@@ -40,6 +40,20 @@ QA_TASKS = ("tvqa", "how2qa")
 # the task head's two optimiser groups keep lr * lr_mul (train_videoQA.py:185-190, train_violin.py:184, train_tvc.py:193-197: for
 # captioning the "head" is everything outside v_encoder - the decoder, its position embedding and emb_LayerNorm)
 HEAD_LR_TASKS = QA_TASKS + ("violin", "tvc")
+# tasks that run the VSM / VCMR head (HeroForPretraining 'vsm', HeroForVcmr's fine-tuning tasks): the ones whose start / end
+# term is drawn per micro-step (drop_svmr_prob)
+VSM_TASKS = ("vsm", "tvr", "how2r", "didemo_video_sub", "didemo_video_only")
+
+
+def draw_st_ed_gate(model, task):
+    """The per-micro-step draw of a model that runs its start / end term behind a gate (hero_amd.head.StEdGate): one number
+    from `random` where the model's own branch would have drawn one (model/pretrain.py:74-75: a head task, lw_st_ed != 0), none
+    otherwise.  Returns the gate when it drew."""
+    gate = getattr(model, "st_ed_gate", None)
+    if gate is None or task not in VSM_TASKS or not model.training or model.lw_st_ed == 0:
+        return None
+    gate.draw(model.drop_svmr_prob)
+    return gate
 
 
 def qkv_groups(model):
@@ -114,6 +128,9 @@ class TrainStep:
             graph_collectives = os.environ.get("HERO_DP_GRAPH", "0") not in ("", "0")
         self.use_graph = use_graph and (not D.collectives_active() or (graph_collectives and uniform_shapes))
         self.counts = {"replayed": 0, "eager_in_graph_mode": 0, "captures": 0}
+        self._head_gen = {}           # graph key -> model.head_generation its graphs were recorded at
+        self._head_warm = {}          # graph key -> whether its last whole eager window ran the start / end term (that step's lazy state exists)
+        self._eager_window = False    # graph mode: the current window runs eagerly (a loss term joined the step)
         self._graphs = {}             # task, or (task, bucket) for a feeder's bucket batches -> (plain graph, its loss, boundary graph, its loss, static batch)
         self._window = []             # tasks of the micro-steps accumulated since the last optimiser step
         # compute copies of the weights are cached per optimiser step: anything else that rewrites parameters
@@ -157,7 +174,37 @@ class TrainStep:
             loss.backward()
         return loss.detach()
 
-    def _optimise(self, device_state):
+    def _gate(self, task):
+        """The model's StEdGate if `task`'s step runs behind it."""
+        gate = getattr(self.model, "st_ed_gate", None)
+        return gate if gate is not None and task in VSM_TASKS and self.model.lw_st_ed != 0 else None
+
+    def _ensure_gate(self, task):
+        """Graph mode, at a window start: a head whose start / end term is drawn per micro-step gets its device gate (a
+        capture cannot branch on the host).  Returns True if one was created - the step changed shape."""
+        m = self.model
+        if (task not in VSM_TASKS or getattr(m, "drop_svmr_prob", 0) <= 0 or getattr(m, "lw_st_ed", 0) == 0
+                or getattr(m, "st_ed_gate", None) is not None):
+            return False
+        if D.collectives_active():
+            raise RuntimeError("graph mode cannot replay a data-parallel step whose start / end term is drawn per step "
+                               "(drop_svmr_prob > 0, model/pretrain.py:74-75): every rank would have to see the same draw for the "
+                               "gated optimiser step to stay consistent, and nothing exchanges it; run eagerly")
+        from .head import StEdGate
+        StEdGate(next(m.parameters()).device).attach(m)
+        return True
+
+    def _begin_micro(self, task, boundary):
+        """Host side of a micro-step that no capture may hold: the draw of the start / end gate, and - on the boundary
+        micro-step - the window's verdict for the gated optimiser step.  Both are stream-ordered fills in front of the launches
+        (or the graph replay) that read them.  Returns the gate if this step runs behind one."""
+        gate = draw_st_ed_gate(self.model, task)
+        if gate is not None and boundary:
+            gate.close_window()
+        return gate
+
+    def _optimise(self, device_state, task=None):
+        gate = self._gate(task or self.task)         # read by the (captured) AdamW launch; written by _begin_micro
         self.arena.finish()
         untouched = [p for p in self.arena.params if p not in self.arena.touched]
         sumsq = self.optimizer.grad_sumsq(self.arena.flat) if self.opts.grad_norm != -1 else None
@@ -166,7 +213,8 @@ class TrainStep:
         self.optimizer.step(grad_sumsq=sumsq, max_grad_norm=float(self.opts.grad_norm),
                             grad_scale=1.0 / D.world_size(), skip=set(untouched),
                             step_tensor=self._step_t if device_state else None,
-                            lr_tensor=self._lr_t if device_state else None)
+                            lr_tensor=self._lr_t if device_state else None,
+                            **(dict(tensor_gates=gate) if gate is not None else {}))
         HF.refresh_weight_cache()                    # every compute copy of the weights in one launch
         self.arena.zero()
 
@@ -202,11 +250,14 @@ class TrainStep:
         accum = self.opts.gradient_accumulation_steps
         boundary = (self.micro + 1) % accum == 0
         self.arena.set_sync(boundary)
+        gate = self._begin_micro(task, boundary)     # None unless a StEdGate was attached to the model by hand
         loss = self._fwd_bwd(batch, task)
         self.micro += 1
         if boundary:
-            self._set_lr()
-            self._optimise(device_state=False)
+            lr = self._set_lr()
+            if gate is not None:                     # the gated optimiser step keeps its step counts on the device
+                self._fill_lr(lr)
+            self._optimise(device_state=gate is not None, task=task)
         return loss
 
     # ---- hipGraph ------------------------------------------------------------------------------------
@@ -214,24 +265,24 @@ class TrainStep:
         """Warm up eagerly (all lazy state: kernel attributes, index maps, workspaces, optimiser
         tables), then capture two graphs on the same static batch: plain micro-step and boundary
         micro-step (with clip + AdamW + weight-copy refresh + gradient zeroing)."""
-        if getattr(self.model, "drop_svmr_prob", 0) > 0 and getattr(self.model, "lw_st_ed", 0) != 0:
-            raise RuntimeError("graph mode cannot capture a step whose loss terms are drawn per step on the host "
-                               "(drop_svmr_prob > 0, model/pretrain.py:74-75): the branch taken at capture would be replayed "
-                               "forever; run eagerly")
+        self._ensure_gate(task)                      # drop_svmr_prob > 0: the term runs behind a device gate from the warm-up on
         accum = self.opts.gradient_accumulation_steps
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
+        self.warmup_losses = []                      # of the last capture's eager micro-steps (device tensors): they are steps of the run
         with torch.cuda.stream(side):
             for i in range(2 * accum):
                 self.arena.set_sync((i + 1) % accum == 0)
-                self._fwd_bwd(batch, task)
+                self._begin_micro(task, (i + 1) % accum == 0)
+                self.warmup_losses.append(self._fwd_bwd(batch, task))
                 if (i + 1) % accum == 0:
                     lr = self._set_lr()
                     self._fill_lr(lr)
-                    self._optimise(device_state=True)
+                    self._optimise(device_state=True, task=task)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.micro += 2 * accum
+        self._head_warm[self._key(batch, task)] = getattr(self.model, "lw_st_ed", 0) != 0
         self._record(batch, task)
 
     @staticmethod
@@ -252,11 +303,12 @@ class TrainStep:
         if boundary:
             self._window = []
         self.arena.set_sync(boundary)
+        self._begin_micro(task, boundary)
         loss = self._fwd_bwd(batch, task)
         self.micro += 1
         if boundary:
             self._fill_lr(self._set_lr())
-            self._optimise(device_state=True)
+            self._optimise(device_state=True, task=task)
         return loss
 
     def _record(self, batch, task):
@@ -274,10 +326,11 @@ class TrainStep:
         self.arena.set_sync(True)                    # boundary: bucket all-reduces (RCCL's stream joins the capture)
         with torch.cuda.graph(gb, pool=ga.pool(), **mode):
             loss_b = self._fwd_bwd(batch, task)
-            self._optimise(device_state=True)
+            self._optimise(device_state=True, task=task)
         key = self._key(batch, task)
         self.counts["captures"] += 1
         self._graphs[key] = (ga, loss_a, gb, loss_b, batch)
+        self._head_gen[key] = getattr(self.model, "head_generation", 0)
         self._graph_gen = getattr(self, "_graph_gen", {})
         self._graph_gen[key] = HF.weight_cache_generation()
         self._active_of = getattr(self, "_active_of", {})
@@ -327,11 +380,27 @@ class TrainStep:
                         self._record(batch, task)
                     return loss
         accum = self.opts.gradient_accumulation_steps
-        if self.micro % accum == 0 and self._graph_gen[key] != HF.weight_cache_generation():
-            torch.cuda.synchronize()                 # window start: re-capture against the current set of weight copies
-            if hasattr(self.optimizer, "prebuild"):  # its descriptor table holds the copies' addresses: build the new one eagerly
-                self.optimizer.prebuild(self._active_of.get(key, []))
-            self._record(self._graphs[key][4], task)
+        if self.micro % accum == 0:
+            # window start - the only place where graphs are re-recorded.  The head's schedule (set_hard_negative,
+            # set_train_st_ed: host scalars baked into the captured launches) makes them stale like a new weight copy does.
+            head_stale = task in VSM_TASKS and self._head_gen[key] != getattr(self.model, "head_generation", 0)
+            if head_stale and (self._ensure_gate(task) or self._head_warm.get(key) != (getattr(self.model, "lw_st_ed", 0) != 0)):
+                # the start / end term JOINS the step (lw_st_ed 0 -> a weight; or leaves it): workspaces, optimiser state and
+                # the descriptor table of the other parameter set do not exist yet.  This window runs eagerly and creates them
+                # (as a feeder's new bucket does, `_seen_eager`); the graphs are re-recorded at the next window start.
+                self._eager_window = True
+            elif head_stale or self._graph_gen[key] != HF.weight_cache_generation():
+                torch.cuda.synchronize()             # re-capture against the current set of weight copies / head schedule
+                if hasattr(self.optimizer, "prebuild"):  # its descriptor table holds the copies' addresses: build the new one eagerly
+                    gate = self._gate(task)
+                    self.optimizer.prebuild(self._active_of.get(key, []), **(dict(tensor_gates=gate) if gate is not None else {}))
+                self._record(self._graphs[key][4], task)
+        if self._eager_window:
+            loss = self._eager_step_in_graph_mode(batch, task)
+            if self.micro % accum == 0:              # the window is closed
+                self._eager_window = False
+                self._head_warm[key] = getattr(self.model, "lw_st_ed", 0) != 0
+            return loss
         ga, loss_a, gb, loss_b, static_batch = self._graphs[key]
         if batch is not static_batch:
             raise RuntimeError("graph mode replays the captured batch buffers (and the index / mask tensors derived "
@@ -346,6 +415,7 @@ class TrainStep:
             self._window = []
         self.micro += 1
         self.counts["replayed"] += 1
+        self._begin_micro(task, boundary)        # the draw of this micro-step: a fill the replay reads, never part of a capture
         if boundary:
             self._fill_lr(self._set_lr())        # stream-ordered scalar fill (no pinned-buffer race)
             gb.replay()

@@ -612,6 +612,17 @@ typedef struct HeroAdamWMulti {
 } HeroAdamWMulti;
 int hero_adamw_multi(const HeroAdamWMulti* a, hero_stream_t stream);
 int hero_adamw_multi_chunk(void);
+/* hero_adamw_multi with a per-tensor DEVICE gate: `tensor_gate` is an int32 array in device memory, */
+/* one entry per descriptor (n_tensors of them), read by the kernels when they run; NULL =           */
+/* hero_adamw_multi.  A tensor whose entry is 0 is skipped completely - every chunk workgroup of it  */
+/* returns before it reads or writes p, g, m or v, and its slot in tensor_steps does not advance:    */
+/* the reference's `if p.grad is None: continue` (optim/adamw.py) decided on the device, so that a   */
+/* captured optimiser step can leave out parameters whose loss term was gated off for the whole      */
+/* accumulation window.  Tensors with a non-zero entry get hero_adamw_multi's arithmetic and bits.   */
+/* A gate table needs tensor_steps and n_tensors (a skipped tensor's step count has to fall behind;  */
+/* a host-side `step` cannot), else HERO_ERR_ARG and no launch.  Plain extra argument: a             */
+/* backward-compatible addition, HERO_ABI_VERSION stays.                                             */
+int hero_adamw_multi_gated(const HeroAdamWMulti* a, const int32_t* tensor_gate, hero_stream_t stream);
 
 /* Multi-tensor refresh of the compute copies of the fp32 master weights (after an optimiser     */
 /* step): ONE launch casts / transposes every tensor of a device-resident descriptor table.     */
@@ -802,6 +813,19 @@ typedef struct HeroStEd {
 size_t hero_st_ed_bwd_workspace_bytes(int B);
 int hero_st_ed_fwd(const HeroStEd* a, hero_stream_t stream);
 int hero_st_ed_bwd(const HeroStEd* a, hero_stream_t stream);
+/* The same two kernels behind a DEVICE gate word (the reference drops this term on a per-step   */
+/* draw, model/pretrain.py:74-75; a captured launch cannot branch on the host).  `gate` points   */
+/* to one int32 in device memory, read by the kernel when it runs - never by the host - so one   */
+/* captured launch serves both values; NULL = the entry points above, which are this case.       */
+/*   *gate != 0: exactly hero_st_ed_fwd / hero_st_ed_bwd.                                        */
+/*   *gate == 0, fwd: loss_rows[b] = +0.0f for every pair; p_st, p_ed and sim keep their bytes.  */
+/*   *gate == 0, bwd: exact +0 to all of dq2 and dctx (in dctx's dtype); nothing is added to     */
+/*     dw_st / dw_ed; `ws` - shares and arrival counter - is not touched (the counter is still   */
+/*     zero for the next gated-on launch); p_st, p_ed, sim, ctx and g are NOT READ: a NaN in     */
+/*     them reaches no output.  A branch at the top of the kernel, uniform over the grid.        */
+/* Plain extra argument: a backward-compatible addition, HERO_ABI_VERSION stays.                 */
+int hero_st_ed_fwd_gated(const HeroStEd* a, const int32_t* gate, hero_stream_t stream);
+int hero_st_ed_bwd_gated(const HeroStEd* a, const int32_t* gate, hero_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Full-corpus moment retrieval (eval_vcmr.py:232-323, 327-338; utils/tvr_eval_utils.py:95-129, */
