@@ -160,9 +160,13 @@ __device__ __forceinline__ void emit_probs(float (&p)[16], float inv, float* pro
 // RC: no saved probabilities - rebuilt from S^T (the same MFMAs on the same operands as the forward's), then the same scale /
 // mask / exp / normalise with the saved row maximum st.x and 1 / row sum st.y: bit-identical P.
 // Else prow = row min(i, L - 1) of the saved fp32 [Lm][Lm] matrix.  The probabilities of this lane's 16 accumulator slots are 4
-// runs of 4 consecutive columns: four 16-byte loads when the row stride allows it, used UNCONDITIONALLY (masked by a
-// multiplication).  Written as `(i < L && j < L) ? prow[j] : 0` the compiler sank each of the 16 scalar loads into its own
-// conditional block, each followed by s_waitcnt vmcnt(0): 16 serial round trips per 32-row block.
+// runs of 4 consecutive columns: four 16-byte loads when the row stride allows it, issued UNCONDITIONALLY; the columns outside
+// the sequence are then dropped by a SELECT on the loaded value, never by a multiplication: in a packed batch the forward
+// writes only columns j < L of a row of stride Lm, the cells behind them hold whatever the allocator left there, and NaN * 0
+// is NaN.  (The row factor stays a multiplication: row min(i, L - 1) is one the forward wrote.)  Written as
+// `(i < L && j < L) ? prow[j] : 0` the compiler sank each of the 16 scalar loads into its own conditional block, each
+// followed by s_waitcnt vmcnt(0): 16 serial round trips per 32-row block - a select per component of a float4 that is already
+// loaded leaves the load where it is.
 template <int NK, bool RC>
 __device__ __forceinline__ void probs_row(const f32x16_t (&sc)[NK], const float (&mk)[NK][16], const float2& st, float scale,
                                           const float* __restrict__ prow, int Lm, int L, float rowok, int half, float (&pr)[NK][16]) {
@@ -183,10 +187,10 @@ __device__ __forceinline__ void probs_row(const f32x16_t (&sc)[NK], const float 
       for (int q = 0; q < 4; ++q) {
         const int j0 = 32 * jt + 8 * q + 4 * half;
         const float4 v = *reinterpret_cast<const float4*>(prow + min(j0, Lm - 4));
-        pr[jt][4 * q + 0] = v.x * (j0 + 0 < L ? rowok : 0.f);
-        pr[jt][4 * q + 1] = v.y * (j0 + 1 < L ? rowok : 0.f);
-        pr[jt][4 * q + 2] = v.z * (j0 + 2 < L ? rowok : 0.f);
-        pr[jt][4 * q + 3] = v.w * (j0 + 3 < L ? rowok : 0.f);
+        pr[jt][4 * q + 0] = j0 + 0 < L ? v.x * rowok : 0.f;
+        pr[jt][4 * q + 1] = j0 + 1 < L ? v.y * rowok : 0.f;
+        pr[jt][4 * q + 2] = j0 + 2 < L ? v.z * rowok : 0.f;
+        pr[jt][4 * q + 3] = j0 + 3 < L ? v.w * rowok : 0.f;
       }
   } else {
 #pragma unroll

@@ -204,8 +204,17 @@ struct Loader {
       // A is [K, lda] with the tile's M columns at m0; B is [K, ldb] with the N columns at n0
       pa = reinterpret_cast<const char*>(p.A + (size_t)p.k0 * p.lda + p.m0);
       pb = reinterpret_cast<const char*>(p.B + (size_t)p.k0 * p.ldb + p.n0);
-      ra_left = ((unsigned long long)(p.K - p.k0) * p.lda - p.m0) * 2;
-      rb_left = ((unsigned long long)(p.K - p.k0) * p.ldb - p.n0) * 2;
+      // The operand ends behind column M - 1 (N - 1) of its LAST row, not a whole leading dimension behind that row's first
+      // column: a tile that reaches past M reads, in the last row, columns that belong to nobody - with A a column slice of
+      // a wider tensor (dY[:, col0:]) up to col0 elements behind the end of the allocation, whatever the allocator left there.
+      // Those columns are never stored, but the selector MFMA of the bias-gradient ride spreads a NaN among them (0 x NaN)
+      // over the sums of the wave's other column blocks.  Out of range reads as 0.
+      // This closes the LAST row only.  In the rows before it a tile wider than M still loads what stands to the right of the
+      // slice in the same tensor - the neighbouring slice, the pad columns of the leading dimension, the start of the next
+      // row - and the selector multiplies it by 0: the ride REQUIRES every element of the rows [0, K) of the tensor that A
+      // is a slice of, pad columns included, to be finite (a NaN or Inf there reaches the bias gradients of valid columns).
+      ra_left = ((unsigned long long)(p.K - 1 - p.k0) * p.lda + (p.M - p.m0)) * 2;
+      rb_left = ((unsigned long long)(p.K - 1 - p.k0) * p.ldb + (p.N - p.n0)) * 2;
       sa = 64u * (unsigned)p.lda * 2u;
       sb = 64u * (unsigned)p.ldb * 2u;
     }
