@@ -35,6 +35,7 @@ EXPORTS = [
     "hero_topk_rows", "hero_st_ed_probs", "hero_moment_topk", "hero_moment_nms", "hero_first_hit",
     "hero_collate_subs", "hero_collate_clip_mask", "hero_collate_frame_map", "hero_collate_gather_feats", "hero_derive_multi",
     "hero_mlm_mask", "hero_mfm_mask", "hero_fom_shuffle",
+    "hero_ce_counted_fwd", "hero_ce_counted_bwd", "hero_mask_partition", "hero_nce_pack_fwd", "hero_nce_pack_bwd",
     "hero_comm_available", "hero_comm_unique_id", "hero_comm_init", "hero_comm_destroy", "hero_comm_rank", "hero_comm_world",
     "hero_comm_allreduce_buckets", "hero_comm_broadcast", "hero_comm_allgather", "hero_comm_allgather_var",
 ]
@@ -284,6 +285,11 @@ def lib():
         L.hero_mlm_mask.argtypes = [C.c_void_p] * 4 + [C.c_uint64] * 2 + [C.c_longlong] * 4 + [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]
         L.hero_mfm_mask.argtypes = [C.c_void_p] * 6 + [C.c_uint64] * 2 + [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p]
         L.hero_fom_shuffle.argtypes = [C.c_void_p] * 2 + [C.c_uint64] * 2 + [C.c_void_p] * 2 + [C.c_int] * 2 + [C.c_void_p]
+        L.hero_ce_counted_fwd.argtypes = [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float, C.c_longlong, C.c_void_p]
+        L.hero_ce_counted_bwd.argtypes = [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_longlong, C.c_void_p]
+        L.hero_mask_partition.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.hero_nce_pack_fwd.argtypes = [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]
+        L.hero_nce_pack_bwd.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]
         L.hero_cross_entropy_fwd.argtypes = [C.POINTER(CrossEntropy), C.c_void_p]
         L.hero_cross_entropy_bwd.argtypes = [C.POINTER(CrossEntropy), C.c_void_p]
         L.hero_qa_pool_fwd.argtypes = [C.c_void_p] * 8 + [C.c_int] * 6 + [C.c_void_p]

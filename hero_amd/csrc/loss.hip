@@ -44,14 +44,14 @@ __device__ __forceinline__ void ms_merge(float& m, float& s, float m2, float s2)
   m = mx;
 }
 
+// One row, the whole 256-thread workgroup: thread 0 writes lse and the loss.  The one statement of the row arithmetic -
+// ce_fwd_kernel and ce_counted_fwd_kernel both call it, so their bits agree by construction.
 template <typename T>
-__global__ __launch_bounds__(256) void ce_fwd_kernel(HeroCrossEntropy a) {
-  __shared__ float sm[4], ss[4];
-  const int row = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const T* x = static_cast<const T*>(a.logits) + (size_t)row * a.ld;
-  const float t = a.inv_temp;
+__device__ __forceinline__ void ce_row_fwd(const T* x, long long y, int cols, int ld, float t, long long ignore_index, float* lse_out,
+                                           float* loss_out, float (&sm)[4], float (&ss)[4]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float m = -3.0e38f, s = 0.f;
-  const int vec_end = ((a.ld & 7) == 0) ? (a.cols & ~7) : 0;          // 16-byte loads need aligned rows
+  const int vec_end = ((ld & 7) == 0) ? (cols & ~7) : 0;              // 16-byte loads need aligned rows
   for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
     float v[8];
     ld8<T>(x + c, v);
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(HeroCrossEntropy a) {
     for (int k = 0; k < 8; ++k) e += __expf(v[k] * t - mx);
     ms_merge(m, s, mx, e);
   }
-  for (int c = vec_end + threadIdx.x; c < a.cols; c += 256) ms_merge(m, s, ld1<T>(x + c) * t, 1.f);
+  for (int c = vec_end + threadIdx.x; c < cols; c += 256) ms_merge(m, s, ld1<T>(x + c) * t, 1.f);
   // wave, then block
   const float wm = wave_max(m);
   s = wave_sum(s * __expf(m - wm));
@@ -74,22 +74,15 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(HeroCrossEntropy a) {
 #pragma unroll
     for (int w = 1; w < 4; ++w) ms_merge(M, S, sm[w], ss[w]);
     const float lse = M + __logf(S);
-    const long long y = a.labels[row];
-    a.lse[row] = lse;
-    a.loss[row] = (y == a.ignore_index || y < 0 || y >= a.cols) ? 0.f : lse - ld1<T>(x + y) * t;
+    *lse_out = lse;
+    *loss_out = (y == ignore_index || y < 0 || y >= cols) ? 0.f : lse - ld1<T>(x + y) * t;
   }
 }
 
+// One gradient row with upstream g (already times inv_temp); dx may alias x: a thread reads its columns before it writes them
 template <typename T>
-__global__ __launch_bounds__(256) void ce_bwd_kernel(HeroCrossEntropy a) {
-  const int row = blockIdx.x;
-  const T* x = static_cast<const T*>(a.logits) + (size_t)row * a.ld;
-  T* dx = static_cast<T*>(a.dlogits) + (size_t)row * a.ld;
-  const long long y = a.labels[row];
-  const bool live = !(y == a.ignore_index || y < 0 || y >= a.cols);
-  const float t = a.inv_temp, lse = a.lse[row];
-  const float g = live ? a.dloss[row] * t : 0.f;
-  const int vec_end = ((a.ld & 7) == 0) ? (a.cols & ~7) : 0;
+__device__ __forceinline__ void ce_row_bwd(const T* x, T* dx, long long y, int cols, int ld, float t, float lse, float g) {
+  const int vec_end = ((ld & 7) == 0) ? (cols & ~7) : 0;
   for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
     float v[8];
     ld8<T>(x + c, v);
@@ -97,11 +90,105 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(HeroCrossEntropy a) {
     for (int k = 0; k < 8; ++k) v[k] = (__expf(v[k] * t - lse) - ((long long)(c + k) == y ? 1.f : 0.f)) * g;
     st8<T>(dx + c, v);
   }
-  for (int c = vec_end + threadIdx.x; c < a.ld; c += 256) {
+  for (int c = vec_end + threadIdx.x; c < ld; c += 256) {
     float v = 0.f;
-    if (c < a.cols) v = (__expf(ld1<T>(x + c) * t - lse) - ((long long)c == y ? 1.f : 0.f)) * g;
+    if (c < cols) v = (__expf(ld1<T>(x + c) * t - lse) - ((long long)c == y ? 1.f : 0.f)) * g;
     st1<T>(dx + c, v);                                               // padding columns get a zero gradient
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ce_fwd_kernel(HeroCrossEntropy a) {
+  __shared__ float sm[4], ss[4];
+  const int row = blockIdx.x;
+  ce_row_fwd<T>(static_cast<const T*>(a.logits) + (size_t)row * a.ld, a.labels[row], a.cols, a.ld, a.inv_temp, a.ignore_index, a.lse + row,
+                a.loss + row, sm, ss);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ce_bwd_kernel(HeroCrossEntropy a) {
+  const int row = blockIdx.x;
+  const long long y = a.labels[row];
+  const bool live = !(y == a.ignore_index || y < 0 || y >= a.cols);
+  const float t = a.inv_temp;
+  ce_row_bwd<T>(static_cast<const T*>(a.logits) + (size_t)row * a.ld, static_cast<T*>(a.dlogits) + (size_t)row * a.ld, y, a.cols, a.ld, t,
+                a.lse[row], live ? a.dloss[row] * t : 0.f);
+}
+
+// ---- the same loss with the LIVE ROW COUNT ON THE DEVICE (fixed-capacity pre-training heads under graph replay) ------
+// Row r is live when r < min(*count, rows) (count == nullptr: rows) and its label is valid.  Rows at or behind the count give
+// loss = lse = 0 and a row of +0 gradients and their logits are never read (whatever they hold - the zero rows of a
+// fixed-capacity gather, NaN - stays out); a row below the count with an ignored label computes lse and has loss 0, as above.
+// One workgroup then folds the live rows' losses in float64 in a fixed order: mean_cnt = (mean over the live rows, their
+// number); the backward divides the device scalar dloss[0] by that number on the device.  No atomics, no host read.
+struct CeCounted {
+  const void* logits;
+  const long long* labels;
+  const int32_t* count;
+  float *loss, *lse, *mean_cnt;
+  const float* dloss;
+  void* dlogits;
+  int rows, cols, ld;
+  float inv_temp;
+  long long ignore_index;
+};
+
+__device__ __forceinline__ int ce_live_rows(const CeCounted& a) { return a.count ? min(max(*a.count, 0), a.rows) : a.rows; }
+
+template <typename T>
+__global__ __launch_bounds__(256) void ce_counted_fwd_kernel(CeCounted a) {
+  __shared__ float sm[4], ss[4];
+  const int row = blockIdx.x;
+  if (row >= ce_live_rows(a)) {                                       // uniform over the workgroup
+    if (threadIdx.x == 0) { a.loss[row] = 0.f; a.lse[row] = 0.f; }
+    return;
+  }
+  ce_row_fwd<T>(static_cast<const T*>(a.logits) + (size_t)row * a.ld, a.labels[row], a.cols, a.ld, a.inv_temp, a.ignore_index, a.lse + row,
+                a.loss + row, sm, ss);
+}
+
+// thread i adds rows i, i + 256, ... in order, then a fixed tree (eval_fold_kernel's pattern); rows == 0 gives (0, 0)
+__global__ __launch_bounds__(256) void ce_counted_fold_kernel(CeCounted a) {
+  __shared__ double ps[2][256];
+  const int n = ce_live_rows(a);
+  double s = 0.0, c = 0.0;
+  for (int r = threadIdx.x; r < n; r += 256) {
+    const long long y = a.labels[r];
+    if (!(y == a.ignore_index || y < 0 || y >= a.cols)) { s += (double)a.loss[r]; c += 1.0; }
+  }
+  ps[0][threadIdx.x] = s;
+  ps[1][threadIdx.x] = c;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) { ps[0][threadIdx.x] += ps[0][threadIdx.x + w]; ps[1][threadIdx.x] += ps[1][threadIdx.x + w]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double live = ps[1][0];
+    a.mean_cnt[0] = (float)(ps[0][0] / (live > 1.0 ? live : 1.0));
+    a.mean_cnt[1] = (float)live;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ce_counted_bwd_kernel(CeCounted a) {
+  const int row = blockIdx.x;
+  T* dx = static_cast<T*>(a.dlogits) + (size_t)row * a.ld;
+  bool live = row < ce_live_rows(a);
+  long long y = -1;
+  if (live) {
+    y = a.labels[row];
+    live = !(y == a.ignore_index || y < 0 || y >= a.cols);
+  }
+  if (!live) {                                                        // +0 over all ld columns, nothing read
+    const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int vec_end = ((a.ld & 7) == 0) ? a.ld : 0;
+    for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) st8<T>(dx + c, z);
+    for (int c = vec_end + threadIdx.x; c < a.ld; c += 256) st1<T>(dx + c, 0.f);
+    return;
+  }
+  const float t = a.inv_temp, g = a.dloss[0] / fmaxf(a.mean_cnt[1], 1.f);
+  ce_row_bwd<T>(static_cast<const T*>(a.logits) + (size_t)row * a.ld, dx, y, a.cols, a.ld, t, a.lse[row], g * t);
 }
 
 // ---- label-smoothed loss of the captioning decoder (model/tvc.py:19-64) -------------------------
@@ -425,6 +512,45 @@ extern "C" int hero_cross_entropy_bwd(const HeroCrossEntropy* a, hero_stream_t s
   if (a->rows == 0) return HERO_OK;
   return by_dtype(a->dtype, "hero_cross_entropy_bwd", [&](auto tag) {
     hipLaunchKernelGGL(ce_bwd_kernel<typename decltype(tag)::type>, dim3(a->rows), dim3(256), 0, static_cast<hipStream_t>(stream), *a);
+  });
+}
+
+static int check_counted(const char* what, const void* logits, const long long* labels, const float* lse, const float* mean_cnt, int rows,
+                         int cols, int ld, int dtype, float inv_temp) {
+  HERO_REQUIRE(rows >= 0 && cols > 0 && ld >= cols, "%s: bad dims rows=%d cols=%d ld=%d", what, rows, cols, ld);
+  HERO_REQUIRE(dtype == HERO_F32 || dtype == HERO_BF16, "%s: bad dtype %d", what, dtype);
+  HERO_REQUIRE(inv_temp > 0.f, "%s: inv_temp must be positive, got %g", what, (double)inv_temp);
+  HERO_REQUIRE(mean_cnt && (((uintptr_t)mean_cnt) & 3) == 0, "%s: mean_cnt required (4-byte aligned)", what);
+  if (rows == 0) return HERO_OK;
+  HERO_REQUIRE(logits && labels && lse, "%s: null pointer", what);
+  HERO_REQUIRE((((uintptr_t)logits) & 15) == 0, "%s: logits must be 16-byte aligned", what);
+  return HERO_OK;
+}
+
+extern "C" int hero_ce_counted_fwd(const void* logits, const long long* labels, const int32_t* count, float* loss, float* lse, float* mean_cnt,
+                                   int rows, int cols, int ld, int dtype, float inv_temp, long long ignore_index, hero_stream_t stream) {
+  if (const int rc = check_counted("hero_ce_counted_fwd", logits, labels, lse, mean_cnt, rows, cols, ld, dtype, inv_temp)) return rc;
+  HERO_REQUIRE(rows == 0 || loss, "hero_ce_counted_fwd: loss required");
+  const CeCounted a = {logits, labels, count, loss, lse, mean_cnt, nullptr, nullptr, rows, cols, ld, inv_temp, ignore_index};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (rows > 0) {
+    if (dtype == HERO_BF16) hipLaunchKernelGGL(ce_counted_fwd_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(ce_counted_fwd_kernel<float>, dim3(rows), dim3(256), 0, s, a);
+  }
+  hipLaunchKernelGGL(ce_counted_fold_kernel, dim3(1), dim3(256), 0, s, a);    // rows == 0: the pair is (0, 0)
+  return check_launch("hero_ce_counted_fwd");
+}
+
+extern "C" int hero_ce_counted_bwd(const void* logits, const long long* labels, const int32_t* count, const float* lse, const float* dloss,
+                                   const float* mean_cnt, void* dlogits, int rows, int cols, int ld, int dtype, float inv_temp,
+                                   long long ignore_index, hero_stream_t stream) {
+  if (const int rc = check_counted("hero_ce_counted_bwd", logits, labels, lse, mean_cnt, rows, cols, ld, dtype, inv_temp)) return rc;
+  if (rows == 0) return HERO_OK;
+  HERO_REQUIRE(dloss && dlogits && (((uintptr_t)dlogits) & 15) == 0, "hero_ce_counted_bwd: dloss / dlogits required (16-byte aligned)");
+  const CeCounted a = {logits, labels, count, nullptr, const_cast<float*>(lse), const_cast<float*>(mean_cnt), dloss, dlogits, rows, cols, ld,
+                       inv_temp, ignore_index};
+  return by_dtype(dtype, "hero_ce_counted_bwd", [&](auto tag) {
+    hipLaunchKernelGGL(ce_counted_bwd_kernel<typename decltype(tag)::type>, dim3(rows), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   });
 }
 

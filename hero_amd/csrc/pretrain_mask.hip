@@ -282,10 +282,135 @@ __global__ __launch_bounds__(256) void fom_shuffle_kernel(const int32_t* __restr
   }
 }
 
+// ---- fixed-capacity consumers: the stable partition of a mask and the NCE operand pack ------------------------------------
+// order = the set indices in ascending order, then the unset ones in ascending order - the row order of the reference's
+// cat([pos, neg]) in mfm_nce (masked frames in torch.nonzero order, then every unmasked frame, padding included); rank is its
+// inverse.  One workgroup: a first pass counts the set elements, a second walks the mask in chunks of the workgroup size
+// with a ballot per wave and a scan of the wave counts in LDS.
+__global__ __launch_bounds__(DRAW_THREADS) void mask_partition_kernel(const uint8_t* __restrict__ mask, int n, int32_t* __restrict__ order,
+                                                                      int32_t* __restrict__ rank, int32_t* __restrict__ count) {
+  constexpr int WAVES = DRAW_THREADS / 64;
+  __shared__ int32_t wsum[WAVES], total;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int mine = 0;
+  for (int i = tid; i < n; i += DRAW_THREADS) mine += mask[i] ? 1 : 0;
+  for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d);
+  if (lane == 0) wsum[wave] = mine;
+  __syncthreads();
+  if (tid == 0) {
+    int m = 0;
+    for (int w = 0; w < WAVES; ++w) m += wsum[w];
+    total = m;
+  }
+  __syncthreads();
+  const int m = total;
+  int before = 0;                                               // set elements in front of the chunk
+  for (int i0 = 0; i0 < n; i0 += DRAW_THREADS) {
+    const int i = i0 + tid;
+    const bool set = i < n && mask[i] != 0;
+    const uint64_t b = __ballot(set);
+    __syncthreads();                                            // the previous chunk's reads of wsum are over
+    if (lane == 0) wsum[wave] = __popcll(b);
+    __syncthreads();
+    int ahead = 0, chunk = 0;
+    for (int w = 0; w < WAVES; ++w) {
+      const int c = wsum[w];
+      ahead += w < wave ? c : 0;
+      chunk += c;
+    }
+    if (i < n) {
+      const int s = before + ahead + lanes_below(b, lane);      // set elements in front of i
+      const int pos = set ? s : m + (i - s);
+      order[pos] = i;
+      rank[i] = pos;
+    }
+    before += chunk;
+  }
+  if (tid == 0) count[0] = m;
+}
+
+// cand[r] = targets[r] (r < m) | out[r] (m <= r < n) | 0 (n <= r < n8) and masked[r] = out[r] (r < cap), both converted to T:
+// the two operands of the NCE logits GEMM from the regressed rows in partition order.  One wave per destination row,
+// 16-byte source segments.
+template <typename T>
+__global__ __launch_bounds__(256) void nce_pack_fwd_kernel(const float* __restrict__ out, const float* __restrict__ targets,
+                                                           const int32_t* __restrict__ count, T* __restrict__ cand, T* __restrict__ masked, int n,
+                                                           int n8, int cap, int D) {
+  const int lane = threadIdx.x & 63, jobs = n8 + cap, m = min(max(count[0], 0), n);
+  for (int job = blockIdx.x * 4 + (threadIdx.x >> 6); job < jobs; job += gridDim.x * 4) {
+    const int r = job < n8 ? job : job - n8;
+    T* dst = job < n8 ? cand + (size_t)r * D : masked + (size_t)r * D;
+    if (job < n8 && r >= n) {
+      for (int c = lane * 4; c < D; c += 256) V4<T>::st(dst + c, make_float4(0.f, 0.f, 0.f, 0.f));
+      continue;
+    }
+    const float* src = (job < n8 && r < m ? targets : out) + (size_t)r * D;
+    for (int c = lane * 4; c < D; c += 256) V4<T>::st(dst + c, ldf4(src + c));
+  }
+}
+
+// d_out[r] = (r < cap ? d_masked[r] : 0) + (r >= m ? d_cand[r] : 0) in fp32; the targets receive nothing
+template <typename T>
+__global__ __launch_bounds__(256) void nce_pack_bwd_kernel(const T* __restrict__ d_cand, const T* __restrict__ d_masked,
+                                                           const int32_t* __restrict__ count, float* __restrict__ d_out, int n, int cap, int D) {
+  const int lane = threadIdx.x & 63, m = min(max(count[0], 0), n);
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += gridDim.x * 4) {
+    const bool from_masked = d_masked && r < cap, from_cand = d_cand && r >= m;
+    for (int c = lane * 4; c < D; c += 256) {
+      const float4 a = from_masked ? V4<T>::ld(d_masked + (size_t)r * D + c) : z;
+      const float4 b = from_cand ? V4<T>::ld(d_cand + (size_t)r * D + c) : z;
+      stf4(d_out + (size_t)r * D + c, make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w));
+    }
+  }
+}
+
 }  // namespace
 }  // namespace hero
 
 using namespace hero;
+
+extern "C" int hero_mask_partition(const unsigned char* mask, int n, int32_t* order, int32_t* rank, int32_t* count, hero_stream_t stream) {
+  HERO_REQUIRE(mask && order && rank && count, "hero_mask_partition: null pointer");
+  HERO_REQUIRE(n >= 1 && n <= (1 << 20), "hero_mask_partition: 1 <= n <= 2^20, got %d", n);
+  hipLaunchKernelGGL(mask_partition_kernel, dim3(1), dim3(DRAW_THREADS), 0, static_cast<hipStream_t>(stream), mask, n, order, rank, count);
+  return check_launch("hero_mask_partition");
+}
+
+static int check_pack(const char* what, const int32_t* count, int n, int cap, int D, int dtype) {
+  HERO_REQUIRE(count, "%s: count required", what);
+  HERO_REQUIRE(n >= 1 && cap >= 1 && cap <= n && D >= 4 && D % 4 == 0 && (long long)(n + 8 + cap) * D < (1ll << 40),
+               "%s: bad dims n=%d cap=%d D=%d (1 <= cap <= n, D a multiple of 4)", what, n, cap, D);
+  HERO_REQUIRE(dtype == HERO_F32 || dtype == HERO_BF16, "%s: bad dtype %d", what, dtype);
+  return HERO_OK;
+}
+
+extern "C" int hero_nce_pack_fwd(const float* out, const float* targets, const int32_t* count, void* cand, void* masked, int n, int cap,
+                                 int D, int dtype, hero_stream_t stream) {
+  if (const int rc = check_pack("hero_nce_pack_fwd", count, n, cap, D, dtype)) return rc;
+  HERO_REQUIRE(out && targets && cand && masked, "hero_nce_pack_fwd: null pointer");
+  HERO_REQUIRE(((uintptr_t)out | (uintptr_t)targets | (uintptr_t)cand | (uintptr_t)masked) % 16 == 0, "hero_nce_pack_fwd: buffers must be 16-byte aligned");
+  const int n8 = (n + 7) / 8 * 8, jobs = n8 + cap;
+  const int grid = (jobs + 3) / 4 < 1024 ? (jobs + 3) / 4 : 1024;
+  return by_dtype(dtype, "hero_nce_pack_fwd", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(nce_pack_fwd_kernel<T>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), out, targets, count,
+                       static_cast<T*>(cand), static_cast<T*>(masked), n, n8, cap, D);
+  });
+}
+
+extern "C" int hero_nce_pack_bwd(const void* d_cand, const void* d_masked, const int32_t* count, float* d_out, int n, int cap, int D,
+                                 int dtype, hero_stream_t stream) {
+  if (const int rc = check_pack("hero_nce_pack_bwd", count, n, cap, D, dtype)) return rc;
+  HERO_REQUIRE(d_out, "hero_nce_pack_bwd: d_out required");
+  HERO_REQUIRE(((uintptr_t)d_cand | (uintptr_t)d_masked | (uintptr_t)d_out) % 16 == 0, "hero_nce_pack_bwd: buffers must be 16-byte aligned");
+  const int grid = (n + 3) / 4 < 1024 ? (n + 3) / 4 : 1024;
+  return by_dtype(dtype, "hero_nce_pack_bwd", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(nce_pack_bwd_kernel<T>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const T*>(d_cand),
+                       static_cast<const T*>(d_masked), count, d_out, n, cap, D);
+  });
+}
 
 extern "C" int hero_mlm_mask(const int64_t* input_ids, const int32_t* sub_nfrm, const int32_t* sub_ntok, const unsigned long long* seed_dev,
                              unsigned long long site, unsigned long long threshold, long long mask_id, long long v_lo, long long v_hi,

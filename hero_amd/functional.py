@@ -1020,17 +1020,20 @@ def refresh_memo(sources=None, skip_outputs=()):
     return done
 
 
-def forget_memo(sources):
+def forget_memo(sources, tags=None):
     """Drop the memoised tensors derived - directly or through other entries - from one of `sources`.  For a caller that has
     rewritten them so that the STRUCTURE of what is derived changes (hero_amd.pretrain_data.PretrainMasker: a new mask has
     another number of set rows): the version counters it moved make the old entries unreachable for memo(), but a later
-    refresh_memo() would redo them in place and refuse the new shape.  Returns the number of entries dropped."""
+    refresh_memo() would redo them in place and refuse the new shape.  tags: only entries with one of these tags (and what is
+    derived from them).  Returns the number of entries dropped."""
     src = {t.data_ptr() for t in sources}
+    gone = set()                                                # outputs of the entries dropped so far
     n = 0
     for e in sorted(_MEMO.values(), key=lambda e: e.seq):       # creation order is dependency order: one pass
-        if any(t.data_ptr() in src for t in e.sources):
+        ptrs = [t.data_ptr() for t in e.sources]
+        if any(p in gone for p in ptrs) or ((tags is None or e.tag in tags) and any(p in src for p in ptrs)):
             if isinstance(e.out, torch.Tensor):
-                src.add(e.out.data_ptr())
+                gone.add(e.out.data_ptr())
             if _MEMO.get(e.key) is e:
                 del _MEMO[e.key]
                 n += 1
@@ -1189,6 +1192,155 @@ class CrossEntropyFn(torch.autograd.Function):
 def cross_entropy(logits, labels, ncols=None, ignore_index=-100, inv_temp=1.0):
     return CrossEntropyFn.apply(logits, labels, logits.shape[1] if ncols is None else ncols, ignore_index,
                                 float(inv_temp))
+
+
+# ---- loss heads of the fixed-capacity pre-training batches: counts stay on the device ---------------
+def _fixed_kernel_ok(*ts):
+    return all(t.is_cuda and t.dim() == 2 and t.dtype in (torch.float32, torch.bfloat16) and t.is_contiguous()
+               and t.data_ptr() % 16 == 0 for t in ts)
+
+
+def _live_rows(count, rows, device):
+    """min(max(count, 0), rows) as a 0-dim device tensor (no host read); None = rows."""
+    if count is None:
+        return torch.tensor(rows, device=device)
+    return count.reshape(-1)[0].to(torch.int64).clamp(0, rows)
+
+
+def counted_cross_entropy_torch(logits, labels, count=None, ncols=None, ignore_index=-100, inv_temp=1.0):
+    """The statement of hero_ce_counted_fwd / _bwd in float64 PyTorch ops (differentiable through autograd): the mean over the
+    live rows - rows below min(count, rows) with a valid label - as a 0-dim fp32 tensor; rows that are not live are never
+    looked at (a NaN there stays out of the loss and of the gradient, which is exactly zero)."""
+    rows, ld = logits.shape
+    ncols = ld if ncols is None else int(ncols)
+    y = labels.reshape(-1).to(torch.int64)
+    live = (torch.arange(rows, device=logits.device) < _live_rows(count, rows, logits.device)) & (y != ignore_index) & (y >= 0) & (y < ncols)
+    x = logits[:, :ncols].double() * float(inv_temp)
+    x = torch.where(live.unsqueeze(1), x, torch.zeros_like(x))
+    loss = torch.logsumexp(x, dim=1) - x.gather(1, y.clamp(0, ncols - 1).unsqueeze(1)).squeeze(1)
+    total = torch.where(live, loss, torch.zeros_like(loss)).sum()
+    return (total / live.sum().clamp(min=1)).to(torch.float32)
+
+
+class CountedCrossEntropyFn(torch.autograd.Function):
+    """0-dim MEAN softmax cross-entropy over the live rows of [rows, ld] logits (hero_ce_counted_*): the live row count is a
+    device word, so a captured launch serves every count.  The backward writes the gradient INTO the saved logits (the
+    vocabulary GEMM's own output: no second [capacity, 50272] buffer) - one backward per forward, and nothing else may read the
+    logits afterwards."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, count, ncols, ignore_index, inv_temp):
+        x2 = logits.contiguous()
+        rows, ld = x2.shape
+        lab = labels.reshape(-1).contiguous().to(torch.int64)
+        if lab.numel() != rows:
+            raise ValueError("counted_cross_entropy: %d labels for %d rows" % (lab.numel(), rows))
+        cnt = count.reshape(-1)[:1].contiguous() if count is not None else None
+        if cnt is not None and cnt.dtype != torch.int32:
+            raise TypeError("counted_cross_entropy: count must be an int32 device word")
+        loss = torch.empty((rows,), dtype=torch.float32, device=x2.device)
+        lse = torch.empty((rows,), dtype=torch.float32, device=x2.device)
+        mean_cnt = torch.empty((2,), dtype=torch.float32, device=x2.device)
+        L.check(L.lib().hero_ce_counted_fwd(L.ptr(x2), L.ptr(lab), L.ptr(cnt), L.ptr(loss), L.ptr(lse), L.ptr(mean_cnt), rows, ncols, ld,
+                                            L.dt(x2), inv_temp, ignore_index, L.stream()))
+        ctx.save_for_backward(x2, lab, lse, mean_cnt)
+        ctx.cnt = cnt
+        ctx.meta = (ncols, ignore_index, inv_temp)
+        return mean_cnt[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        x2, lab, lse, mean_cnt = ctx.saved_tensors
+        ncols, ignore_index, inv_temp = ctx.meta
+        rows, ld = x2.shape
+        g = dloss.reshape(1).contiguous().float()
+        L.check(L.lib().hero_ce_counted_bwd(L.ptr(x2), L.ptr(lab), L.ptr(ctx.cnt), L.ptr(lse), L.ptr(g), L.ptr(mean_cnt), L.ptr(x2), rows,
+                                            ncols, ld, L.dt(x2), inv_temp, ignore_index, L.stream()))
+        return x2, None, None, None, None, None
+
+
+def counted_cross_entropy(logits, labels, count=None, ncols=None, ignore_index=-100, inv_temp=1.0):
+    """Mean cross-entropy over the rows r < min(count, rows) whose label is valid, as a 0-dim fp32 tensor; count is a device
+    word (int32, None = every row).  No live row gives 0 and zero gradients.  CPU tensors, and whatever the kernels refuse,
+    take counted_cross_entropy_torch."""
+    if not _fixed_kernel_ok(logits) or not labels.is_cuda or (count is not None and (not count.is_cuda or count.dtype != torch.int32)):
+        return counted_cross_entropy_torch(logits, labels, count, ncols, ignore_index, inv_temp)
+    return CountedCrossEntropyFn.apply(logits, labels, count, logits.shape[1] if ncols is None else int(ncols), int(ignore_index),
+                                       float(inv_temp))
+
+
+def mask_partition_torch(mask):
+    """(order, rank, count) of hero_mask_partition in PyTorch ops: the set indices, then the unset ones, both ascending."""
+    m = mask.reshape(-1) != 0
+    order = torch.sort((~m).to(torch.int8), stable=True).indices.to(torch.int32)
+    rank = torch.empty_like(order)
+    rank[order.long()] = torch.arange(order.numel(), dtype=torch.int32, device=order.device)
+    return order, rank, m.sum().to(torch.int32).reshape(1)
+
+
+def mask_partition(mask, order=None, rank=None, count=None):
+    """Stable partition of a 0/1 byte (or bool) mask: order[r] = the r-th set index, then the unset ones; rank = its inverse;
+    count[0] = the number set.  Writes into order / rank / count (int32) when given - fixed addresses for a captured step."""
+    flat = mask.reshape(-1)
+    n = flat.numel()
+    if not (flat.is_cuda and flat.is_contiguous() and flat.dtype in (torch.bool, torch.uint8) and 1 <= n <= 1 << 20):
+        o, r, c = mask_partition_torch(mask)
+        if order is None:
+            return o, r, c
+        order.copy_(o), rank.copy_(r), count.copy_(c)
+        return order, rank, count
+    if order is None:
+        order, rank = torch.empty(n, dtype=torch.int32, device=flat.device), torch.empty(n, dtype=torch.int32, device=flat.device)
+        count = torch.empty(1, dtype=torch.int32, device=flat.device)
+    L.check(L.lib().hero_mask_partition(L.ptr(flat), n, L.ptr(order), L.ptr(rank), L.ptr(count), L.stream()))
+    return order, rank, count
+
+
+def nce_pack_torch(out, targets, count, cap, dtype):
+    """The statement of hero_nce_pack_fwd / _bwd in PyTorch ops (differentiable through autograd)."""
+    n, D = out.shape
+    r = torch.arange(n, device=out.device).unsqueeze(1)
+    cand = torch.where(r < _live_rows(count, n, out.device), targets.detach().to(out.dtype), out).to(dtype)
+    if n % 8:
+        cand = torch.cat([cand, cand.new_zeros(8 - n % 8, D)], 0)
+    return cand, out[:cap].to(dtype)
+
+
+class NcePackFn(torch.autograd.Function):
+    """(cand, masked) = the two operands of the MFM-NCE logits GEMM from the regressed rows in partition order: cand[r] =
+    targets[r] below the device count, out[r] from it on, zero rows up to a multiple of 8; masked = out[:cap]."""
+
+    @staticmethod
+    def forward(ctx, out, targets, count, cap, dtype):
+        n, D = out.shape
+        cand = torch.empty(((n + 7) // 8 * 8, D), dtype=dtype, device=out.device)
+        masked = torch.empty((cap, D), dtype=dtype, device=out.device)
+        L.check(L.lib().hero_nce_pack_fwd(L.ptr(out), L.ptr(targets), L.ptr(count), L.ptr(cand), L.ptr(masked), n, cap, D, L.dt(cand),
+                                          L.stream()))
+        ctx.save_for_backward(count)
+        ctx.dims = (n, cap, D)
+        return cand, masked
+
+    @staticmethod
+    def backward(ctx, d_cand, d_masked):
+        (count,) = ctx.saved_tensors
+        n, cap, D = ctx.dims
+        dc = d_cand.contiguous() if d_cand is not None else None
+        dm = d_masked.contiguous() if d_masked is not None else None
+        ref = dc if dc is not None else dm
+        d_out = torch.empty((n, D), dtype=torch.float32, device=ref.device)
+        L.check(L.lib().hero_nce_pack_bwd(L.ptr(dc), L.ptr(dm), L.ptr(count), L.ptr(d_out), n, cap, D, L.dt(ref), L.stream()))
+        return d_out, None, None, None, None
+
+
+def nce_pack(out, targets, count, cap, dtype):
+    """out [n, D] fp32 (partition order), targets [n, D] fp32, count an int32 device word, 1 <= cap <= n."""
+    cnt = count.reshape(-1)[:1]
+    if not (_fixed_kernel_ok(out, targets) and out.dtype == torch.float32 and targets.dtype == torch.float32 and out.shape == targets.shape
+            and cnt.is_cuda and cnt.dtype == torch.int32 and out.shape[1] % 4 == 0 and 1 <= cap <= out.shape[0]
+            and dtype in (torch.float32, torch.bfloat16)):
+        return nce_pack_torch(out, targets, count, cap, dtype)
+    return NcePackFn.apply(out, targets, cnt.contiguous(), int(cap), dtype)
 
 
 class EmbedLnFn(torch.autograd.Function):

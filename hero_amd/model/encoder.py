@@ -190,7 +190,8 @@ class CrossModalTrm(RobertaPreTrainedModel):
         if task.startswith("mlm"):
             return self.forward_mlm(batch["input_ids"], batch["position_ids"], batch["v_feat"],
                                     batch["f_pos_ids"], batch["attn_masks"], batch["gather_index"],
-                                    batch["txt_mask_tgt"], batch["txt_labels"], compute_loss)
+                                    batch["txt_mask_tgt"], batch["txt_labels"], compute_loss,
+                                    txt_mask_rows=batch["txt_mask_rows"], mask_counts=batch["mask_counts"])
         raise ValueError(f"Unrecognized task {task}")
 
     def forward_repr(self, input_ids, position_ids, img_feat, img_pos_ids, attention_mask,
@@ -202,10 +203,15 @@ class CrossModalTrm(RobertaPreTrainedModel):
         pooled = self.pooler(seq) if self.run_pooler else None
         return (seq, pooled)
 
-    def _mlm_masked_rows(self, input_ids, position_ids, img_feat, img_pos_ids, attention_mask, gather_index, txt_mask_tgt):
+    def _mlm_masked_rows(self, input_ids, position_ids, img_feat, img_pos_ids, attention_mask, gather_index, txt_mask_tgt,
+                         txt_mask_rows=None):
+        """txt_mask_rows: the fixed-capacity row list of hero_amd.pretrain_data.PretrainMasker (int32 flat rows, -1 behind the
+        count: those gather a zero row) instead of torch.nonzero of the mask - nothing then has a mask-dependent shape."""
         emb = self._compute_img_txt_embeddings(input_ids, position_ids, img_feat, img_pos_ids,
                                                gather_index, attention_mask=attention_mask)
         seq = self.encoder(emb, attention_mask)[0]
+        if txt_mask_rows is not None:
+            return HF.GatherRowsFn.apply(seq.reshape(-1, seq.shape[-1]), None, txt_mask_rows)
         rows = HF.memo("mask_rows", (txt_mask_tgt,),     # once per batch object: nonzero synchronises (no graph capture)
                        lambda: torch.nonzero(txt_mask_tgt.reshape(-1), as_tuple=False).reshape(-1).to(torch.int32).contiguous())
         return HF.GatherRowsFn.apply(seq.reshape(-1, seq.shape[-1]), None, rows)
@@ -219,10 +225,14 @@ class CrossModalTrm(RobertaPreTrainedModel):
         return logits, logits.shape[1] - self.vocab_pad
 
     def forward_mlm(self, input_ids, position_ids, img_feat, img_pos_ids, attention_mask,
-                    gather_index, txt_mask_tgt, txt_labels=None, compute_loss=True):
-        masked = self._mlm_masked_rows(input_ids, position_ids, img_feat, img_pos_ids, attention_mask, gather_index, txt_mask_tgt)
+                    gather_index, txt_mask_tgt, txt_labels=None, compute_loss=True, txt_mask_rows=None, mask_counts=None):
+        masked = self._mlm_masked_rows(input_ids, position_ids, img_feat, img_pos_ids, attention_mask, gather_index, txt_mask_tgt,
+                                       txt_mask_rows)
         if compute_loss:      # fused log-softmax + NLL over the vocabulary GEMM output, padding columns excluded
             logits = self.lm_head(masked, raw=True)
+            if txt_mask_rows is not None:     # fixed capacity: the 0-dim mean over the rows below the device count
+                return HF.counted_cross_entropy(logits, txt_labels, count=None if mask_counts is None else mask_counts[0:1],
+                                                ncols=logits.shape[1] - self.vocab_pad)
             return HF.cross_entropy(logits, txt_labels, ncols=logits.shape[1] - self.vocab_pad)
         scores = self.lm_head(masked)
         if self.vocab_pad:

@@ -208,6 +208,8 @@ class HierarchicalVlModel(VideoPreTrainedModel):
         # no aten embedding backward: 112 us per MFM micro-step, profiles/r03_kernel_stats_D3.csv), row 0 = padding_idx
         batch["_c_v_mask_rows"] = HF.memo("c_v_mask_rows", (c_v_mask,), lambda: c_v_mask.reshape(-1).to(torch.int32).contiguous())
         clip_outputs = self.forward_repr(batch)
+        if batch["mfm_order"] is not None:
+            return self._forward_mfm_fixed(batch, clip_outputs, compute_loss, loss)
         pred = self.feat_regress(self._compute_masked_hidden(clip_outputs, c_v_mask))
         neg = self.feat_regress(self._compute_masked_hidden(clip_outputs, c_v_mask, invert=True)) \
             if loss == "nce" else None
@@ -217,6 +219,27 @@ class HierarchicalVlModel(VideoPreTrainedModel):
         if loss == "regression":
             return F.mse_loss(pred, targets, reduction="none")
         return self.mfm_nce(pred, targets, neg)
+
+    def _forward_mfm_fixed(self, batch, clip_outputs, compute_loss, loss):
+        """The MFM heads on a fixed-capacity batch (hero_amd.pretrain_data.PretrainMasker.static_batch('mfm')): nothing has a
+        mask-dependent shape, the masked-frame count m = mask_counts[1] stays on the device.  The B * NF clip rows are
+        permuted into partition order (the m masked frames in nonzero order, then every other frame: the reference's
+        cat([pos, neg]) order, model/model.py:271-291) and regressed in ONE GEMM - the compact form regresses the same
+        m + (B * NF - m) rows in two.  Masked frames behind the row capacity keep their mask in the input and carry no
+        loss; the means divide by the live rows."""
+        order, count = batch["mfm_order"], batch["mask_counts"][1:2]
+        targets = batch["feat_targets"]
+        n, cap = order.numel(), batch["nce_labels"].numel()
+        out = self.feat_regress(HF.PermuteRowsFn.apply(clip_outputs.reshape(n, clip_outputs.shape[-1]), order, batch["mfm_rank"]))
+        if not compute_loss:
+            return out if loss == "regression" else (out[:cap], out)
+        if loss == "regression":         # mean over the m * D elements of the masked rows, in captured torch ops
+            live = (torch.arange(cap, device=out.device) < count).unsqueeze(1)
+            sq = torch.where(live, (out[:cap] - targets[:cap]) ** 2, torch.zeros((), dtype=out.dtype, device=out.device))
+            return sq.sum() / (count.clamp(1, cap).to(out.dtype) * out.shape[1]).squeeze(0)
+        cand, masked = HF.nce_pack(out, targets, count, cap, HF.compute_dtype())
+        logits = HF.matmul_nt(masked, cand)                                   # [cap, round_up(B * NF, 8)]
+        return HF.counted_cross_entropy(logits, batch["nce_labels"], count=count, ncols=n, inv_temp=1.0 / self.nce_temp)
 
     def mfm_nce_logits(self, masked_output, pos_output, neg_output):
         """(logits, n): the candidate GEMM's own output [n_masked, n_masked + n_neg (+ padding)] in the compute dtype,
@@ -258,6 +281,8 @@ class HierarchicalVlModel(VideoPreTrainedModel):
         if raw:
             return logits
         logits = HF.cast(logits, torch.float32)
+        if compute_loss and batch["_masker"] is not None:       # fixed-capacity batch: the 0-dim mean from the loss kernel's own fold
+            return HF.counted_cross_entropy(logits, batch["targets"].reshape(-1), count=None, ignore_index=-1)
         if compute_loss:                                        # mean over the rows that carry a target
             tgt = batch["targets"].reshape(-1)
             rows = HF.cross_entropy(logits, tgt, ignore_index=-1)

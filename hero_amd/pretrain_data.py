@@ -18,6 +18,10 @@ Outputs live at fixed addresses with fixed capacities (`static_entries()`):
 `mlm_batch()` / `mfm_batch()` / `fom_batch()` return dicts with the reference collates' keys; the compact tensors are narrowed
 to their counts there, which costs one host read of the counts per draw (the model synchronises on `nonzero` of the masks
 for these batches anyway).
+
+The FIXED-CAPACITY forms (`draw_fixed`, `static_batch`) read nothing on the host: the loss heads take the
+device counts (hero_ce_counted_*, hero_nce_pack_*), the compact tensors keep a capacity of `row_capacity(...)` rows, and a
+captured step replays on a fresh draw per micro-step (hero_amd.step.TrainStep draws for a batch that carries `_masker`).
 """
 import math
 
@@ -46,7 +50,7 @@ def _signed(word):
 
 class PretrainMasker:
     def __init__(self, T, max_sl, max_vl, out_size, B, NF, vfeat_dim, device, mask_id, v_range, cls_id, mlm_prob=0.15, mfm_prob=0.15,
-                 fom_prob=0.15, sites=None, seed=0):
+                 fom_prob=0.15, sites=None, seed=0, mlm_rows=None, mfm_rows=None):
         self.T, self.max_sl, self.max_vl, self.Lf, self.B, self.NF, self.D = T, max_sl, max_vl, out_size, B, NF, vfeat_dim
         self.device = torch.device(device)
         self.mask_id, self.v_range, self.cls_id = int(mask_id), (int(v_range[0]), int(v_range[1])), int(cls_id)
@@ -68,7 +72,14 @@ class PretrainMasker:
         self.shuffled_orders = z(B, NF, dt=torch.int64)
         self.targets = z(B, NF, dt=torch.int64)
         self._row_src = z(2 * B * NF + T * max_vl, dt=torch.int32)
-        self._clean, self._host_counts = None, None
+        # fixed-capacity forms: row capacities of the loss heads, the MFM partition, what the heads read besides the draws
+        self.mlm_rows = self._capacity("mlm_rows", mlm_rows, self.cap, mlm_prob, T)
+        self.mfm_rows = self._capacity("mfm_rows", mfm_rows, B * NF, mfm_prob, B)
+        self.mfm_order = z(B * NF, dt=torch.int32)
+        self.mfm_rank = z(B * NF, dt=torch.int32)
+        self.nce_labels = torch.arange(max(self.mfm_rows, 1), dtype=torch.int64, device=self.device)
+        self.overflow = z(2, dt=torch.int64)          # draws whose (masked tokens, masked frames) exceeded the capacity
+        self._clean, self._host_counts, self._lengths_src, self._static = None, None, None, {}
         self.set_seed(seed)
 
     @classmethod
@@ -78,6 +89,22 @@ class PretrainMasker:
         B, NF = batch["c_attn_masks"].shape
         return cls(T, batch["f_sub_input_ids"].shape[1], max_vl, batch["f_attn_masks"].shape[1], B, NF, D, device, mask_id, v_range,
                    cls_id, **kw)
+
+    @staticmethod
+    def row_capacity(n, p, forced):
+        """Rows kept for a mask over at most n selectable positions drawn with probability p, plus `forced` selections of the
+        at-least-one rule: mean + six standard deviations of the binomial (a tail bound: about 1e-9 per draw by the normal
+        approximation - not a measurement), rounded up to the GEMM's 8-row granularity, never more than n."""
+        if not 0.0 <= p <= 1.0 or n < 0 or forced < 0:
+            raise ValueError("row_capacity: n, forced >= 0 and p in [0, 1]")
+        rows = int(math.ceil(n * p + 6.0 * math.sqrt(n * p * (1.0 - p)))) + int(forced)
+        return min(int(n), (rows + 7) // 8 * 8)
+
+    def _capacity(self, name, given, n, p, forced):
+        rows = self.row_capacity(n, p, forced) if given is None else int(given)
+        if not (1 <= rows <= n or n == 0):
+            raise ValueError("PretrainMasker: %s = %d outside [1, %d]" % (name, rows, n))
+        return rows
 
     # ---- the seed word (device ops: stream-ordered with the draws) -----------------------------------------------------
     def set_seed(self, s):
@@ -106,6 +133,12 @@ class PretrainMasker:
     def draw(self, clean_batch, collate_or_lengths, tasks=("mlm", "mfm", "fom")):
         """Launch the draws of `tasks` for the clean device batch: kernels only - no host data, no synchronisation, nothing
         allocated (capturable in a hipGraph).  The clean tensors are only read."""
+        self._rewritten(self._launch(clean_batch, collate_or_lengths, tasks) + [self.counts])
+        self._clean, self._lengths_src = clean_batch, collate_or_lengths
+        return self
+
+    def _launch(self, clean_batch, collate_or_lengths, tasks):
+        """The kernels of `tasks`; returns the tensors they wrote."""
         ln, s, lib = self._lengths(collate_or_lengths), L.stream(), L.lib()
         written = []
         for task in tasks:
@@ -134,9 +167,59 @@ class PretrainMasker:
                 written += [self.shuffled_orders, self.targets]
             else:
                 raise ValueError("PretrainMasker.draw: unknown task %r (mlm, mfm, fom)" % (task,))
-        self._rewritten(written + [self.counts])
-        self._clean = clean_batch
+        return written
+
+    # ---- the fixed-capacity forms ----------------------------------------------------------------------------------------
+    def draw_fixed(self, clean_batch, collate_or_lengths, task):
+        """draw() of ONE task for a consumer that holds everything by address (a captured step): the same kernels, plus the
+        stable partition of the frame mask for MFM and the overflow counter.  Memo entries are kept - captured graphs hold the
+        derived tensors (`row_index` / `seg_order` of input_ids, `c_v_mask_rows`) - and redone in place from the new draw;
+        only row lists taken with torch.nonzero for the compact forms go (their shape follows the mask, no graph can hold
+        them).  Launches and stream-ordered device ops only: no host read.  Not inside a capture (it moves version counters
+        and re-keys memo entries, which a replay would not do)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("PretrainMasker.draw_fixed: call it in front of the capture / replay, not inside")
+        written = self._launch(clean_batch, collate_or_lengths, (task,))
+        if task == "mlm":
+            self.overflow[0:1] += self.counts[0:1] > self.mlm_rows
+        elif task == "mfm":
+            HF.mask_partition(self.c_v_masks, self.mfm_order, self.mfm_rank, self.counts[1:2])     # the count again: same value
+            self.overflow[1:2] += self.counts[1:2] > self.mfm_rows
+            written += [self.mfm_order, self.mfm_rank]
+        written.append(self.counts)
+        torch._C._increment_version(written)
+        HF.forget_memo(written, tags=("mask_rows",))
+        HF.restamp_memo(HF.refresh_memo(sources=written))
+        self._host_counts = None
+        self._clean, self._lengths_src = clean_batch, collate_or_lengths
         return self
+
+    def redraw(self, task):
+        """advance() + draw_fixed() on the clean batch and lengths of the last draw: a fresh mask for the next micro-step."""
+        self._need_clean()
+        return self.advance().draw_fixed(self._clean, self._lengths_src, task)
+
+    def static_batch(self, task):
+        """The batch of `task` ('mlm', 'mfm', 'fom') in its fixed-capacity form: ONE dict object per task (a captured step
+        accepts only the object it was captured on), the clean batch's keys plus the draw's tensors at fixed addresses and
+        the device counts.  `_static_buffers` keeps host-derived pack plans away from it, `_masker` lets TrainStep draw."""
+        if task not in self._static:
+            out = dict(self._need_clean())
+            if task == "mlm":
+                c = self._clean
+                out.update(input_ids=self.input_ids, position_ids=c["f_sub_pos_ids"], v_feat=c["f_v_feats"], attn_masks=c["f_attn_masks"],
+                           gather_index=c["f_gather_index"], txt_mask_tgt=self.txt_mask_tgt, txt_mask_rows=self.txt_mask_rows[:self.mlm_rows],
+                           txt_labels=self.txt_labels[:self.mlm_rows])
+            elif task == "mfm":
+                out.update(f_v_feats=self.f_v_feats, c_v_feats=self.c_v_feats, f_v_masks=self.f_v_masks, c_v_masks=self.c_v_masks,
+                           feat_targets=self.feat_targets, mfm_order=self.mfm_order, mfm_rank=self.mfm_rank, nce_labels=self.nce_labels)
+            elif task == "fom":
+                out.update(shuffled_orders=self.shuffled_orders, targets=self.targets)
+            else:
+                raise ValueError("PretrainMasker.static_batch: unknown task %r (mlm, mfm, fom)" % (task,))
+            out.update(mask_counts=self.counts, _static_buffers=True, _masker=self)
+            self._static[task] = out
+        return self._static[task]
 
     def _rewritten(self, tensors):
         # raw kernels wrote them: caches keyed on (address, version) must miss (DeviceCollate.rebuild does the same), and what

@@ -56,6 +56,25 @@ def draw_st_ed_gate(model, task):
     return gate
 
 
+def mask_task_of(task):
+    """The PretrainMasker draw behind a step's task: 'mlm*' -> 'mlm', 'mffr' / 'mfm-nce' -> 'mfm', 'fom' -> 'fom'; None for
+    the tasks that draw no mask."""
+    if task.startswith("mlm"):
+        return "mlm"
+    return {"mffr": "mfm", "mfm-nce": "mfm", "fom": "fom"}.get(task)
+
+
+def draw_masks(batch, task):
+    """The per-micro-step draw of a fixed-capacity pre-training batch (PretrainMasker.static_batch: it carries `_masker`):
+    the next seed, then the task's masks, in stream order in front of the launches or the replay that read them."""
+    masker = batch.get("_masker") if hasattr(batch, "get") else None
+    which = mask_task_of(task)
+    if masker is None or which is None:
+        return None
+    masker.redraw(which)
+    return masker
+
+
 def qkv_groups(model):
     """Gradient-arena groups: each attention block's query/key/value weights (and biases) back to
     back, so that their gradients are one [3D, D] GEMM (+ one column sum) in the backward."""
@@ -194,10 +213,12 @@ class TrainStep:
         StEdGate(next(m.parameters()).device).attach(m)
         return True
 
-    def _begin_micro(self, task, boundary):
+    def _begin_micro(self, task, boundary, batch=None):
         """Host side of a micro-step that no capture may hold: the draw of the start / end gate, and - on the boundary
-        micro-step - the window's verdict for the gated optimiser step.  Both are stream-ordered fills in front of the launches
-        (or the graph replay) that read them.  Returns the gate if this step runs behind one."""
+        micro-step - the window's verdict for the gated optimiser step; for a fixed-capacity pre-training batch the draw of
+        this micro-step's masks.  All are stream-ordered fills / launches in front of the launches (or the graph replay) that
+        read them.  Returns the gate if this step runs behind one."""
+        draw_masks(batch, task)
         gate = draw_st_ed_gate(self.model, task)
         if gate is not None and boundary:
             gate.close_window()
@@ -250,7 +271,7 @@ class TrainStep:
         accum = self.opts.gradient_accumulation_steps
         boundary = (self.micro + 1) % accum == 0
         self.arena.set_sync(boundary)
-        gate = self._begin_micro(task, boundary)     # None unless a StEdGate was attached to the model by hand
+        gate = self._begin_micro(task, boundary, batch)     # None unless a StEdGate was attached to the model by hand
         loss = self._fwd_bwd(batch, task)
         self.micro += 1
         if boundary:
@@ -273,7 +294,7 @@ class TrainStep:
         with torch.cuda.stream(side):
             for i in range(2 * accum):
                 self.arena.set_sync((i + 1) % accum == 0)
-                self._begin_micro(task, (i + 1) % accum == 0)
+                self._begin_micro(task, (i + 1) % accum == 0, batch)
                 self.warmup_losses.append(self._fwd_bwd(batch, task))
                 if (i + 1) % accum == 0:
                     lr = self._set_lr()
@@ -303,7 +324,7 @@ class TrainStep:
         if boundary:
             self._window = []
         self.arena.set_sync(boundary)
-        self._begin_micro(task, boundary)
+        self._begin_micro(task, boundary, batch)
         loss = self._fwd_bwd(batch, task)
         self.micro += 1
         if boundary:
@@ -415,7 +436,7 @@ class TrainStep:
             self._window = []
         self.micro += 1
         self.counts["replayed"] += 1
-        self._begin_micro(task, boundary)        # the draw of this micro-step: a fill the replay reads, never part of a capture
+        self._begin_micro(task, boundary, batch)  # the draws of this micro-step: what the replay reads, never part of a capture
         if boundary:
             self._fill_lr(self._set_lr())        # stream-ordered scalar fill (no pinned-buffer race)
             gb.replay()

@@ -901,6 +901,23 @@ typedef struct HeroCrossEntropy {
 int hero_cross_entropy_fwd(const HeroCrossEntropy* a, hero_stream_t stream);
 int hero_cross_entropy_bwd(const HeroCrossEntropy* a, hero_stream_t stream);
 
+/* The same loss with the live row count ON THE DEVICE - the loss heads of the fixed-capacity pre-training batches, whose    */
+/* masks change under a replayed hipGraph.  count: one device word, NULL = rows.  Row r is live when r < min(*count, rows)     */
+/* and labels[r] is not ignore_index and lies in [0, cols).                                                                   */
+/* fwd: a row below the count gets loss[r] / lse[r] bit for bit as hero_cross_entropy_fwd writes them (one row body); a row at */
+/*   or behind the count gets loss = lse = 0 and its logits are NOT read.  Then one workgroup folds the live rows' losses in   */
+/*   float64 in a fixed order: mean_cnt[0] = (float)(sum / max(n_live, 1)), mean_cnt[1] = (float)n_live; no live row (or       */
+/*   rows == 0) gives (0, 0).                                                                                                 */
+/* bwd: g = dloss[0] / max(mean_cnt[1], 1), both read on the device; live rows get (softmax - onehot) * g * inv_temp with the  */
+/*   columns [cols, ld) zero; every other row gets +0 over all ld columns, and no logits are read for it.  dlogits may alias    */
+/*   logits.  No atomics, nothing read on the host: both calls can be captured.  logits / dlogits 16-byte aligned,            */
+/* inv_temp > 0.  Plain arguments: a backward-compatible addition, HERO_ABI_VERSION stays.                                    */
+int hero_ce_counted_fwd(const void* logits, const long long* labels, const int32_t* count, float* loss, float* lse, float* mean_cnt,
+                        int rows, int cols, int ld, int dtype, float inv_temp, long long ignore_index, hero_stream_t stream);
+int hero_ce_counted_bwd(const void* logits, const long long* labels, const int32_t* count, const float* lse, const float* dloss,
+                        const float* mean_cnt, void* dlogits, int rows, int cols, int ld, int dtype, float inv_temp,
+                        long long ignore_index, hero_stream_t stream);
+
 /* Label-smoothed loss of the captioning decoder (model/tvc.py:19-64): the KL divergence of softmax(x) to the smoothed one-hot */
 /* of label t, over the first `cols` columns of [rows, ld] logits, in closed form - no [rows, cols] target matrix:            */
 /*   C = cols, s = eps / (C - 1), conf = 1 - eps, H0 = conf ln conf + (C - 1) s ln s with 0 ln 0 = 0 (eps = 1 is allowed)       */
@@ -1005,6 +1022,22 @@ int hero_mfm_mask(const float* c_v_feats, const int32_t* vid_nfrm, const int32_t
                   float* f_v_feats_out, int32_t* row_src, int T, int max_vl, int B, int NF, int D, hero_stream_t stream);
 int hero_fom_shuffle(const int32_t* vid_nfrm, const unsigned long long* seed_dev, unsigned long long site, unsigned long long threshold,
                      int64_t* shuffled_orders, int64_t* targets, int B, int NF, hero_stream_t stream);
+
+/* Consumers of the fixed-capacity draws (nothing has a mask-dependent shape; counts stay on the device).                    */
+/* hero_mask_partition: mask [n] bytes 0 / non-zero, m = number set.  order [n] int32: order[r] = the r-th set index for      */
+/*   r < m, the (r - m)-th unset index for r >= m (both ascending: the row order of the reference's cat([pos, neg]) in         */
+/*   mfm_nce); rank [n] int32 = its inverse (rank[order[r]] = r); count [1] int32 = m.  One workgroup, 1 <= n <= 2^20.         */
+/* hero_nce_pack_fwd: out [n, D] fp32 = the regressed rows in partition order, targets [n, D] fp32, count = m (clamped to     */
+/*   [0, n]), 1 <= cap <= n.  Writes, in `dtype`, cand [round_up(n, 8), D]: cand[r] = targets[r] (r < m), out[r] (m <= r < n), */
+/*   zero rows behind n; and masked [cap, D] = out[:cap].                                                                     */
+/* hero_nce_pack_bwd: d_out [n, D] fp32 = (r < cap ? d_masked[r] : 0) + (r >= m ? d_cand[r] : 0); d_cand / d_masked in        */
+/*   `dtype`, either may be NULL (zero); the targets receive no gradient.  D % 4 == 0, 16-byte aligned buffers.               */
+/* All capturable.  Plain arguments: a backward-compatible addition, HERO_ABI_VERSION stays.                                  */
+int hero_mask_partition(const unsigned char* mask, int n, int32_t* order, int32_t* rank, int32_t* count, hero_stream_t stream);
+int hero_nce_pack_fwd(const float* out, const float* targets, const int32_t* count, void* cand, void* masked, int n, int cap, int D,
+                      int dtype, hero_stream_t stream);
+int hero_nce_pack_bwd(const void* d_cand, const void* d_masked, const int32_t* count, float* d_out, int n, int cap, int D, int dtype,
+                      hero_stream_t stream);
 
 /* Everything the model derives from the int64 index / mask tensors of a batch, in one launch: additive attention   */
 /* masks (1 - m) * -10000 (model/layers.py:299-302), fp32 masks, int32 row indices, and f_gather_index as flat rows   */
