@@ -5,7 +5,7 @@ runs in hand-written HIP kernels behind a C ABI (include/hero_hip.h, hero_amd/li
 """
 from .functional import (advance_seed, compute_dtype, manual_seed,  # noqa: F401
                          notify_weights_updated, set_compute_dtype)
-from .retrieval import (CorpusIndex, RecallMeter, encode_corpus, k_first_hit, k_moment_nms, postprocess, postprocess_host,  # noqa: F401
-                        search, search_torch)
+from .retrieval import (CorpusIndex, RecallMeter, encode_corpus, k_first_hit, k_first_hit_multi, k_moment_nms, pack_gt_ts,  # noqa: F401
+                        postprocess, postprocess_host, search, search_torch)
 
 __version__ = "0.1.0"

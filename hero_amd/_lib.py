@@ -32,7 +32,7 @@ EXPORTS = [
     "hero_dec_attention_row_in_envelope", "hero_dec_attention_row", "hero_dec_attention_step",
     "hero_dec_attention_row_grouped", "hero_dec_attention_step_beam", "hero_beam_in_envelope", "hero_beam_select",
     "hero_sample_in_envelope", "hero_sample_select", "hero_caption_in_envelope", "hero_caption_score",
-    "hero_topk_rows", "hero_st_ed_probs", "hero_moment_topk", "hero_moment_nms", "hero_first_hit",
+    "hero_topk_rows", "hero_st_ed_probs", "hero_moment_topk", "hero_moment_nms", "hero_first_hit", "hero_first_hit_multi",
     "hero_collate_subs", "hero_collate_clip_mask", "hero_collate_frame_map", "hero_collate_gather_feats", "hero_derive_multi",
     "hero_mlm_mask", "hero_mfm_mask", "hero_fom_shuffle",
     "hero_ce_counted_fwd", "hero_ce_counted_bwd", "hero_mask_partition", "hero_nce_pack_fwd", "hero_nce_pack_bwd",
@@ -277,6 +277,8 @@ def lib():
         L.hero_moment_topk.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 3
         L.hero_moment_nms.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 3
         L.hero_first_hit.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.hero_first_hit_multi.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_void_p]
         L.hero_collate_subs.argtypes = [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]
         L.hero_collate_gather_feats.argtypes = [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p]
         L.hero_derive_multi.argtypes = [C.POINTER(Derive), C.c_int, C.c_void_p]

@@ -6,7 +6,11 @@ Host half - same names, inputs and outputs as the reference, so a reference Data
     video_collate   video_collate + get_gather_index     data/data.py:406-471, 504-512
     query_collate   query_collate                        data/vcmr.py:120-137
     vcmr_collate    vcmr_collate                         data/vcmr.py:140-159
-    videoqa_item    VideoQaDataset.__getitem__           data/videoQA.py:62-121 (one question)
+    video_only_item VideoFeatDataset.__getitem__         data/vr_video_only.py:29-49 (a corpus without subtitles: [CLS] + every frame)
+    vr_item, vr_collate, vr_eval_collate, vr_full_eval_item, vr_full_eval_collate       data/vr.py:98-200
+    vcmr_eval_collate, vcmr_full_eval_item, vcmr_full_eval_collate                      data/vcmr.py:171-253
+        (pinned by tests/golden/case_vr.npz)
+    videoqa_item    VideoQaDataset.__getitem__          data/videoQA.py:62-121 (one question)
     video_qa_collate  video_qa_collate                   data/videoQA.py:155-182 (pinned by tests/golden/case_videoqa.npz)
     violin_item     ViolinDataset.__getitem__            data/violin.py:66-110
     violin_collate / violin_eval_collate                 data/violin.py:118-141, 163-170 (pinned by tests/golden/case_violin.npz)
@@ -162,6 +166,76 @@ def vcmr_collate(inputs):
     where = {v: i for i, v in enumerate(vids)}
     batch["q_vidx"] = torch.tensor([where[q[2]] for q in qs], dtype=torch.long)
     return batch
+
+
+def video_only_item(v_feat, cls_=0):
+    """One video of a corpus without subtitles -> the 7-tuple of VideoFeatDataset.__getitem__ (data/vr_video_only.py:29-49, which
+    data/vcmr_video_only.py shares): ONE fake subtitle holding the single token `cls_` (CLS, not SEP) and every frame of the video,
+    so its row is 1 + n_frames positions long."""
+    n = v_feat.shape[0]
+    return ([torch.tensor([cls_])], [v_feat], [torch.ones(1 + n, dtype=torch.long)], v_feat, torch.ones(n, dtype=torch.long), 1,
+            [(0, list(range(n)))])
+
+
+def _query_row(toks, vid, target, cls_):
+    ids = torch.tensor([cls_] + list(toks), dtype=torch.long)
+    return (ids, torch.ones_like(ids), vid, torch.tensor(target, dtype=torch.long))
+
+
+def vr_item(video, vid, queries, cls_=0):
+    """video: a video_item / video_only_item tuple; queries: token id lists -> VrDataset.__getitem__'s (video, vid, ((ids, mask,
+    vid, [-1, -1]), ...)) (data/vr.py:98-120): video retrieval has no moment to point at."""
+    return (video, vid, tuple(_query_row(toks, vid, [-1, -1], cls_) for toks in queries))
+
+
+def vr_collate(inputs):
+    """data/vr.py:123-124."""
+    return vcmr_collate(inputs)
+
+
+def vcmr_eval_collate(inputs):
+    """list of (qids, vcmr_item tuple) -> vcmr_collate's batch plus `qids` (data/vcmr.py:171-178)."""
+    batch = vcmr_collate([item for _, item in inputs])
+    batch["qids"] = [q for ids, _ in inputs for q in ids]
+    return batch
+
+
+def vr_eval_collate(inputs):
+    """data/vr.py:134-141."""
+    return vcmr_eval_collate(inputs)
+
+
+def vcmr_full_eval_item(qid, toks, vid, ts=None, n_frames=None, cls_=0, frame_interval=1.5):
+    """One query of a full-corpus evaluation -> VcmrFullEvalDataset.__getitem__'s (qid, [(ids, mask, vid, target)])
+    (data/vcmr.py:215-242): the target is st_ed_label(ts) in the `n_frames` frames of its video when the query carries a
+    timestamp, [-1, -1] otherwise."""
+    if ts is None:
+        target = [-1, -1]
+    else:
+        if n_frames is None:
+            raise ValueError("vcmr_full_eval_item: a query with a timestamp needs n_frames of its video")
+        target = st_ed_label(ts, n_frames - 1, frame_interval)
+    return (qid, [_query_row(toks, vid, target, cls_)])
+
+
+def vr_full_eval_item(qid, toks, vid, cls_=0):
+    """VrFullEvalDataset.__getitem__ (data/vr.py:175-196): the target is always [-1, -1]."""
+    return vcmr_full_eval_item(qid, toks, vid, cls_=cls_)
+
+
+def vcmr_full_eval_collate(inputs):
+    """list of full-eval items -> the query-only batch of data/vcmr.py:245-253: query_input_ids / query_pos_ids / query_attn_masks,
+    targets, `vids` (one per query) and `qids`."""
+    qs = [q for _, rows in inputs for q in rows]
+    batch = query_collate([q[0] for q in qs], [q[1] for q in qs], [q[3] for q in qs])
+    batch["vids"] = [q[2] for q in qs]
+    batch["qids"] = [qid for qid, _ in inputs]
+    return batch
+
+
+def vr_full_eval_collate(inputs):
+    """data/vr.py:199-200."""
+    return vcmr_full_eval_collate(inputs)
 
 
 def videoqa_item(video, question, answers, target, ts, sep=2, frame_interval=1.5, vid=None):

@@ -10,8 +10,9 @@
 // barrier, no atomics, no workspace; the result depends on the row alone.  The float64 division runs only for candidates
 // of the pivot's video that overlap it.
 //
-// hero_first_hit: one wavefront per query; the lanes stride over the predictions, each keeps the first position it saw per
-// column, a butterfly minimum folds them.
+// hero_first_hit / hero_first_hit_multi: one wavefront per query; the lanes stride over the predictions, each keeps the first
+// position it saw per column, a butterfly minimum folds them.  One row scan serves both: one [st, ed] per query is the
+// G = 1 instance of the several-annotator rule (DiDeMo).
 #include "common.h"
 
 namespace hero {
@@ -78,14 +79,27 @@ __global__ __launch_bounds__(64) void moment_nms_kernel(const int* video, const 
   if (lane == 0) count[q] = kept;
 }
 
+// The row scan of both recall exports.  GCAP annotator timestamps of the query sit in registers; n of them are real (n is
+// wave-uniform: q goes through readfirstlane, so the ground truth comes by scalar loads and `g < n` is a scalar branch).
+// A prediction is correct at a threshold when at least `need` annotators reach it: 1, or the reference's least_n_overlap = 2
+// from four annotators on (utils/tvr_standalone_eval.py:159-170).  gt_n == nullptr: one [st, ed] per query, GCAP = 1.
+template <int GCAP>
 __global__ __launch_bounds__(256) void first_hit_kernel(const int* video, const int* st, const int* ed, int Nq, int P, int ld, const int* gt_video,
-                                                        const float* gt_ts, float interval, const float* thds, int T, int* first) {
+                                                        const float* gt_ts, const int* gt_n, int G, float interval, const float* thds, int T,
+                                                        int* first) {
   const int lane = threadIdx.x & 63;
-  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int q = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (q >= Nq) return;                                              // whole waves leave; no barrier below
   const int gv = gt_video[q];
   const bool timed = st != nullptr && T > 0;
-  const float g0 = timed ? gt_ts[2 * q] : 0.f, g1 = timed ? gt_ts[2 * q + 1] : 0.f;
+  const int n = !timed ? 0 : gt_n == nullptr ? 1 : max(1, min(gt_n[q], min(G, GCAP)));       // never past the row's G slots
+  const int need = n >= 4 ? 2 : 1;
+  float g0[GCAP], g1[GCAP];
+#pragma unroll
+  for (int g = 0; g < GCAP; ++g) {                                  // slots >= n are padding: never read
+    g0[g] = g < n ? gt_ts[((size_t)q * G + g) * 2] : 0.f;
+    g1[g] = g < n ? gt_ts[((size_t)q * G + g) * 2 + 1] : 0.f;
+  }
   float thd[HIT_MAX_T];
 #pragma unroll
   for (int t = 0; t < HIT_MAX_T; ++t) thd[t] = t < T ? thds[t] : 0.f;
@@ -104,12 +118,22 @@ __global__ __launch_bounds__(256) void first_hit_kernel(const int* video, const 
     best[0] = min(best[0], p);
     if (!timed) continue;
     const float p0 = (float)ps * interval, p1 = (float)(pe + 1) * interval;
-    const float inter = fmaxf(0.f, fminf(p1, g1) - fmaxf(p0, g0));
-    const float uni = fmaxf(p1, g1) - fminf(p0, g0);
-    const float iou = uni != 0.f ? inter / uni : 0.f;
+    int reached[HIT_MAX_T];                                         // annotators with iou >= thd[t]
+#pragma unroll
+    for (int t = 0; t < HIT_MAX_T; ++t) reached[t] = 0;
+#pragma unroll
+    for (int g = 0; g < GCAP; ++g) {
+      if (g < n) {
+        const float inter = fmaxf(0.f, fminf(p1, g1[g]) - fmaxf(p0, g0[g]));
+        const float uni = fmaxf(p1, g1[g]) - fminf(p0, g0[g]);
+        const float iou = uni != 0.f ? inter / uni : 0.f;
+#pragma unroll
+        for (int t = 0; t < HIT_MAX_T; ++t) reached[t] += t < T && iou >= thd[t] ? 1 : 0;
+      }
+    }
 #pragma unroll
     for (int t = 0; t < HIT_MAX_T; ++t)
-      if (t < T && iou >= thd[t]) best[1 + t] = min(best[1 + t], p);
+      if (t < T && reached[t] >= need) best[1 + t] = min(best[1 + t], p);
   }
 #pragma unroll
   for (int t = 0; t <= HIT_MAX_T; ++t) {
@@ -120,6 +144,16 @@ __global__ __launch_bounds__(256) void first_hit_kernel(const int* video, const 
       if (lane == 0) first[(size_t)q * (T + 1) + t] = b;
     }
   }
+}
+
+constexpr int HIT_MAX_G = 16;
+
+template <int GCAP>
+int launch_first_hit(const char* what, const int* video, const int* st, const int* ed, int Nq, int P, int ld, const int* gt_video, const float* gt_ts,
+                     const int* gt_n, int G, float interval, const float* thds, int T, int* first, hero_stream_t stream) {
+  hipLaunchKernelGGL(first_hit_kernel<GCAP>, dim3((Nq + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), video, st, ed, Nq, P, ld, gt_video,
+                     gt_ts, gt_n, G, interval, thds, T, first);
+  return check_launch(what);
 }
 
 }  // namespace
@@ -147,7 +181,19 @@ extern "C" int hero_first_hit(const int* video, const int* st, const int* ed, in
   HERO_REQUIRE(T >= 0 && T <= HIT_MAX_T, "hero_first_hit: need 0 <= T <= %d (T=%d)", HIT_MAX_T, T);
   HERO_REQUIRE(T == 0 || (thds && gt_ts && st), "hero_first_hit: IoU thresholds need thds, gt_ts, st and ed");
   if (Nq <= 0) return HERO_OK;
-  hipLaunchKernelGGL(first_hit_kernel, dim3((Nq + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), video, st, ed, Nq, P, ld, gt_video, gt_ts,
-                     interval, thds, T, first);
-  return check_launch("hero_first_hit");
+  return launch_first_hit<1>("hero_first_hit", video, st, ed, Nq, P, ld, gt_video, gt_ts, nullptr, 1, interval, thds, T, first, stream);
+}
+
+extern "C" int hero_first_hit_multi(const int* video, const int* st, const int* ed, int Nq, int P, int ld, const int* gt_video, const float* gt_ts,
+                                    const int* gt_n, int G, float interval, const float* thds, int T, int* first, hero_stream_t stream) {
+  HERO_REQUIRE(video && gt_video && first, "hero_first_hit_multi: null pointer");
+  HERO_REQUIRE((st == nullptr) == (ed == nullptr), "hero_first_hit_multi: st and ed are given together or not at all");
+  HERO_REQUIRE(G >= 1 && G <= HIT_MAX_G, "hero_first_hit_multi: need 1 <= G <= %d (G=%d)", HIT_MAX_G, G);
+  HERO_REQUIRE(P >= 1 && ld >= P, "hero_first_hit_multi: need 1 <= P <= ld (P=%d ld=%d)", P, ld);
+  HERO_REQUIRE(T >= 0 && T <= HIT_MAX_T, "hero_first_hit_multi: need 0 <= T <= %d (T=%d)", HIT_MAX_T, T);
+  HERO_REQUIRE(T == 0 || (thds && gt_ts && gt_n && st), "hero_first_hit_multi: IoU thresholds need thds, gt_ts, gt_n, st and ed");
+  if (Nq <= 0) return HERO_OK;
+  if (G == 1) return launch_first_hit<1>("hero_first_hit_multi", video, st, ed, Nq, P, ld, gt_video, gt_ts, gt_n, G, interval, thds, T, first, stream);
+  if (G <= 4) return launch_first_hit<4>("hero_first_hit_multi", video, st, ed, Nq, P, ld, gt_video, gt_ts, gt_n, G, interval, thds, T, first, stream);
+  return launch_first_hit<HIT_MAX_G>("hero_first_hit_multi", video, st, ed, Nq, P, ld, gt_video, gt_ts, gt_n, G, interval, thds, T, first, stream);
 }

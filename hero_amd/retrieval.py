@@ -27,6 +27,9 @@ What follows a search is on the device too (hero_moment_nms, hero_first_hit; no 
     meter.update(post, gt_vidx, gt_ts, desc_type)                                    # RecallMeter: hit counts of R@K at IoU thresholds
     metrics = meter.compute()                                                        # the dictionary of eval_retrieval, one synchronisation
 
+Ground truth with several annotators per query (DiDeMo) goes through `pack_gt_ts` and `meter.update(post, gt_vidx, gt_ts, gt_n=gt_n)`
+(hero_first_hit_multi); hero_amd/retrieval_eval.py holds the drivers that return the reference's val_log and submission.
+
 `postprocess_host` is the reference's post-processing restated on the host (utils/tvr_eval_utils.py:35-92, 132-234): what
 `postprocess` takes beyond N = 1024, and the speed baseline.  Writing the prediction JSON stays with the caller."""
 import ctypes as C
@@ -138,6 +141,72 @@ def k_first_hit(video, gt_video, st=None, ed=None, gt_ts=None, interval=1.5, thd
                                    L.ptr(gt_video), L.ptr(gt_ts) if T else None, float(interval), L.ptr(thds) if T else None, T, L.ptr(first),
                                    L.stream()))
     return first
+
+
+MAX_GT = 16          # annotators per query hero_first_hit_multi takes (include/hero_hip.h)
+
+
+def k_first_hit_multi(video, gt_video, st, ed, gt_ts, gt_n, interval=1.5, thds=None, n_pred=None):
+    """`k_first_hit` for ground truth with several annotators (DiDeMo): gt_ts fp32 [Nq, G, 2] seconds (padded, G <= 16), gt_n
+    int32 [Nq] = the real timestamps of each query.  Column 1 + t of first [Nq, T + 1] is the rank of the first prediction in
+    the ground-truth video at which at least `need` timestamps have IoU >= thds[t]; need = 2 from four timestamps on
+    (utils/tvr_standalone_eval.py:159-170), else 1.  Slots at index >= gt_n[q] are never read."""
+    _need_cuda(video, gt_video, st, ed, gt_ts, gt_n, thds)
+    if (st is None) != (ed is None):
+        raise ValueError("k_first_hit_multi: st and ed are given together or not at all")
+    for t in (video, st, ed):
+        if t is not None and (t.dim() != 2 or t.dtype != torch.int32 or t.stride(1) != 1 or t.shape != video.shape or t.stride(0) != video.stride(0)):
+            raise ValueError("k_first_hit_multi: video, st and ed must be int32 [Nq, P] tensors of one shape and row stride, rows contiguous")
+    Nq, cols = video.shape
+    if gt_video.dtype != torch.int32 or gt_video.shape != (Nq,) or not gt_video.is_contiguous():
+        raise ValueError("k_first_hit_multi: gt_video must be a contiguous int32 [Nq] tensor")
+    T = 0 if thds is None else int(thds.numel())
+    G = 1
+    if gt_ts is not None or gt_n is not None:
+        if (gt_ts is None or gt_n is None or gt_ts.dtype != torch.float32 or gt_ts.dim() != 3 or gt_ts.shape[0] != Nq or gt_ts.shape[2] != 2
+                or not gt_ts.is_contiguous() or gt_n.dtype != torch.int32 or gt_n.shape != (Nq,) or not gt_n.is_contiguous()):
+            raise ValueError("k_first_hit_multi: gt_ts must be a contiguous fp32 [Nq, G, 2] tensor and gt_n a contiguous int32 [Nq] tensor")
+        G = int(gt_ts.shape[1])
+    if T:
+        if thds.dtype != torch.float32 or not thds.is_contiguous():
+            raise ValueError("k_first_hit_multi: thds must be a contiguous fp32 tensor")
+        if st is None or gt_ts is None:
+            raise ValueError("k_first_hit_multi: IoU thresholds need st, ed, gt_ts and gt_n")
+    n_pred = cols if n_pred is None else min(int(n_pred), cols)
+    first = torch.empty((Nq, T + 1), dtype=torch.int32, device=video.device)
+    ld = video.stride(0) if Nq > 1 else cols
+    L.check(L.lib().hero_first_hit_multi(video.data_ptr(), None if st is None else st.data_ptr(), None if ed is None else ed.data_ptr(), Nq, n_pred,
+                                         ld, L.ptr(gt_video), L.ptr(gt_ts) if T else None, L.ptr(gt_n) if T else None, G, float(interval),
+                                         L.ptr(thds) if T else None, T, L.ptr(first), L.stream()))
+    return first
+
+
+def pack_gt_ts(ts_list):
+    """Ground-truth timestamps as the reference's JSON holds them - per query either [st, ed] (TVR, How2R) or a list of at least
+    four [st, ed] pairs (DiDeMo's annotators) - on the host -> (gt_ts fp32 [Nq, G, 2] zero-padded, gt_n int32 [Nq]): the inputs
+    of `k_first_hit_multi` / `RecallMeter.update`.  Two or three pairs raise: eval_by_task_type takes `len(ts) >= 4` for the
+    annotator list and everything shorter for ONE [st, ed], which a list of two or three pairs is not
+    (utils/tvr_standalone_eval.py:159, 172-173).  More than 16 pairs raise: the kernel's envelope."""
+    rows = []
+    for q, ts in enumerate(ts_list):
+        ts = list(ts)
+        if len(ts) == 2 and not isinstance(ts[0], (list, tuple, np.ndarray)):
+            rows.append([[float(ts[0]), float(ts[1])]])
+            continue
+        if not all(isinstance(p, (list, tuple, np.ndarray)) and len(p) == 2 for p in ts):
+            raise ValueError("pack_gt_ts: query %d: expected [st, ed] or a list of [st, ed] pairs, got %r" % (q, ts))
+        if len(ts) < 4:
+            raise ValueError("pack_gt_ts: query %d has %d timestamps: the reference's rule is defined for one or for at least four" % (q, len(ts)))
+        if len(ts) > MAX_GT:
+            raise ValueError("pack_gt_ts: query %d has %d timestamps, at most %d are supported" % (q, len(ts), MAX_GT))
+        rows.append([[float(p[0]), float(p[1])] for p in ts])
+    if not rows:
+        raise ValueError("pack_gt_ts: no query")
+    G = max(len(r) for r in rows)
+    gt_ts = np.zeros((len(rows), G, 2), dtype=np.float32)
+    for q, r in enumerate(rows):
+        gt_ts[q, :len(r)] = np.asarray(r, dtype=np.float32)
+    return torch.from_numpy(gt_ts), torch.tensor([len(r) for r in rows], dtype=torch.int32)
 
 
 def _unravel(flat, length):
@@ -493,8 +562,8 @@ class RecallMeter:
 
     A query counts for R@K at a threshold when hero_first_hit's rank of its first correct prediction is below K.  In the
     reference's SVMR branch ranks are counted among the predictions in the ground-truth video; every SVMR prediction is in that
-    video, so this is the plain rank.  Only single-timestamp ground truth (TVR, How2R) is covered: the DiDeMo branch of the
-    reference (>= 4 timestamps, two of which must overlap) is not.  Pass `device` to allocate the counters at construction
+    video, so this is the plain rank.  Ground truth is one [st, ed] per query (TVR, How2R; hero_first_hit) or several
+    annotators' timestamps (DiDeMo: from four on, two must reach the threshold; `pack_gt_ts`, hero_first_hit_multi).  Pass `device` to allocate the counters at construction
     (needed before capturing `update` in a graph); otherwise the first update allocates them."""
 
     TASKS = ("VCMR", "SVMR", "VR")
@@ -539,23 +608,36 @@ class RecallMeter:
             self.typed = True
 
     @torch.no_grad()
-    def update(self, out_or_post, gt_vidx, gt_ts=None, desc_type=None):
+    def update(self, out_or_post, gt_vidx, gt_ts=None, desc_type=None, gt_n=None):
         """One query batch.  out_or_post: a dictionary of `postprocess` (TASK_nms_* keys, preferred) and / or of `search`; VR is read
-        from vr_indices.  gt_vidx int [Nq]; gt_ts fp32 [Nq, 2] seconds (without it only VR is counted); desc_type optional int [Nq],
-        0 / 1 / 2 = v / t / vt.  Only the first max_pred_per_query predictions count.  Enqueues kernels, never waits for them."""
+        from vr_indices.  gt_vidx int [Nq]; gt_ts fp32 [Nq, 2] seconds (without it only VR is counted), or fp32 [Nq, G, 2] with
+        gt_n int [Nq] (`pack_gt_ts`: several annotators per query); desc_type optional int [Nq], 0 / 1 / 2 = v / t / vt.  Only the
+        first max_pred_per_query predictions count.  Enqueues kernels, never waits for them."""
         d = out_or_post
         gt = gt_vidx.reshape(-1).to(torch.int32).contiguous()
-        _need_cuda(gt, gt_ts, desc_type)
+        _need_cuda(gt, gt_ts, desc_type, gt_n)
         if self.hits is None:
             self._allocate(gt.device)
-        ts = None if gt_ts is None else gt_ts.to(torch.float32).reshape(-1, 2).contiguous()
+        multi = gt_ts is not None and gt_ts.dim() == 3
+        if multi:
+            if gt_n is None:
+                raise ValueError("RecallMeter.update: gt_ts [Nq, G, 2] needs gt_n [Nq] (pack_gt_ts gives both)")
+            ts, n = gt_ts.to(torch.float32).contiguous(), gt_n.reshape(-1).to(torch.int32).contiguous()
+        else:
+            if gt_n is not None:
+                raise ValueError("RecallMeter.update: gt_n goes with a 3-D gt_ts [Nq, G, 2]")
+            ts = None if gt_ts is None else gt_ts.to(torch.float32).reshape(-1, 2).contiguous()
         for task in MOMENT_TASKS:
             pre = task + "_nms_" if task + "_nms_st" in d else task + "_"
             if pre + "st" not in d or ts is None:
                 continue
             st, ed = d[pre + "st"], d[pre + "ed"]
             video = d[pre + "video"] if task == "vcmr" else torch.where(st >= 0, gt.view(-1, 1), torch.full_like(st, -1))
-            first = k_first_hit(video, gt, st, ed, ts, self.vfeat_interval, self._thds if self.iou_thds else None, self.max_pred_per_query)
+            thds = self._thds if self.iou_thds else None
+            if multi:
+                first = k_first_hit_multi(video, gt, st, ed, ts, n, self.vfeat_interval, thds, self.max_pred_per_query)
+            else:
+                first = k_first_hit(video, gt, st, ed, ts, self.vfeat_interval, thds, self.max_pred_per_query)
             self.add_first(task.upper(), first, min(self.max_pred_per_query, st.shape[1]), desc_type)
         if "vr_indices" in d:
             vi = d["vr_indices"]

@@ -41,8 +41,9 @@ QA_TASKS = ("tvqa", "how2qa")
 # captioning the "head" is everything outside v_encoder - the decoder, its position embedding and emb_LayerNorm)
 HEAD_LR_TASKS = QA_TASKS + ("violin", "tvc")
 # tasks that run the VSM / VCMR head (HeroForPretraining 'vsm', HeroForVcmr's fine-tuning tasks): the ones whose start / end
-# term is drawn per micro-step (drop_svmr_prob)
-VSM_TASKS = ("vsm", "tvr", "how2r", "didemo_video_sub", "didemo_video_only")
+# term is drawn per micro-step (drop_svmr_prob).  HeroForVr's two tasks run the same head with lw_st_ed == 0: they never get a
+# gate, but set_hard_negative makes their captured steps stale in the same way
+VSM_TASKS = ("vsm", "tvr", "how2r", "didemo_video_sub", "didemo_video_only", "msrvtt_video_sub", "msrvtt_video_only")
 
 
 def draw_st_ed_gate(model, task):
@@ -186,6 +187,8 @@ class TrainStep:
             # 'mlm' / 'mfm-nce' / 'fom': one loss tensor
             if (task or self.task) in QA_TASKS:       # (qa_loss, temporal_loss), train_videoQA.py:157-166
                 loss = out[0] + self.opts.lw_st_ed * out[1]
+            elif isinstance(out, (tuple, list)) and len(out) == 2:       # HeroForVr: loss_neg_ctx + loss_neg_q, train_vr.py:213-214
+                loss = out[0] + out[1]
             else:
                 loss = (out[0] + out[1] + out[2]) if isinstance(out, (tuple, list)) else out
             if loss.dim() > 0:                       # train_vcmr.py:226 `.mean()` of per-GPU losses; a 0-dim loss is its own mean

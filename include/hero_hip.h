@@ -42,6 +42,7 @@ const char* hero_last_error(void);
  * Still 3: the retrieval entry points hero_topk_rows, hero_st_ed_probs and hero_moment_topk were ADDED later (plain pointer /
  * scalar arguments, no struct) - a backward-compatible addition, no struct moved, so the version stays.
  * Still 3: hero_moment_nms and hero_first_hit (what follows a search: NMS and recall ranks) were ADDED the same way.
+ * Still 3: hero_first_hit_multi (recall ranks against several annotators' timestamps: DiDeMo) was ADDED the same way.
  * Still 3: hero_qa_pool_fwd and hero_qa_pool_bwd (the video-QA head) were ADDED the same way.
  * Still 3: hero_frame_pool_fwd/bwd and hero_bce_head_fwd/bwd (the VIOLIN head) were ADDED the same way.
  * Still 3: hero_dec_attention_fwd/bwd/in_envelope and hero_smooth_ce_fwd/bwd, the captioning decoder's kernels, were ADDED the
@@ -877,6 +878,14 @@ int hero_moment_nms(const int* video, const int* st, const int* ed, int Nq, int 
  * min(start), 0 where that is 0, compared iou >= thd in fp32.  Single-timestamp ground truth only (TVR, How2R). */
 int hero_first_hit(const int* video, const int* st, const int* ed, int Nq, int P, int ld, const int* gt_video, const float* gt_ts, float interval,
                    const float* thds, int T, int* first, hero_stream_t stream);
+/* hero_first_hit for ground truth with several annotators (DiDeMo; utils/tvr_standalone_eval.py:157-170).  gt_ts fp32
+ * [Nq, G, 2] seconds, padded; gt_n int32 [Nq], 1 <= gt_n[q] <= G (values outside are clamped), 1 <= G <= 16; slots at index
+ * >= gt_n[q] are never read.  Column 1 + t = first position with a video match at which at least `need` of the gt_n[q]
+ * timestamps have IoU >= thds[t]; need = 2 when gt_n[q] >= 4 (the reference's least_n_overlap), else 1.  Column 0, vacancy,
+ * the fp32 IoU and every other argument are hero_first_hit's: the same row scan, of which hero_first_hit is the G = 1
+ * instance.  T > 0 needs st, ed, gt_ts and gt_n. */
+int hero_first_hit_multi(const int* video, const int* st, const int* ed, int Nq, int P, int ld, const int* gt_video, const float* gt_ts,
+                         const int* gt_n, int G, float interval, const float* thds, int T, int* first, hero_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Softmax cross-entropy over wide logit rows (pre-training heads, BASELINE configs[3]):        */
