@@ -215,11 +215,17 @@ int check_launch(const char* what);
 // Host: f(DType<T>()) with the element type that a dtype code names, for launches whose branches differ only in T:
 //   return by_dtype(dtype, "hero_x", [&](auto tag) { using T = typename decltype(tag)::type; hipLaunchKernelGGL(x_kernel<T>, ...); });
 // An unknown code sets "<what>: bad dtype <code>" and launches nothing; after f the result is check_launch(what).
+// with_dtype is the dispatch alone (false: unknown code, f not called), for an entry point that launches again before its
+// one check_launch.
 template <typename T> struct DType { using type = T; };
-template <class F> int by_dtype(int dtype, const char* what, F f) {
+template <class F> bool with_dtype(int dtype, F f) {
   if (dtype == HERO_F32) f(DType<float>());
   else if (dtype == HERO_BF16) f(DType<bf16_t>());
-  else { set_error("%s: bad dtype %d", what, dtype); return HERO_ERR_ARG; }
+  else return false;
+  return true;
+}
+template <class F> int by_dtype(int dtype, const char* what, F f) {
+  if (!with_dtype(dtype, f)) { set_error("%s: bad dtype %d", what, dtype); return HERO_ERR_ARG; }
   return check_launch(what);
 }
 

@@ -9,6 +9,15 @@
 // them once more and writes the gradient in the logits' dtype (may alias the logits):
 //   loss_r = lse_r - x[r, y_r],   dx[r, c] = (exp(x[r, c] - lse_r) - [c == y_r]) * g_r * inv_temp
 // with x = logits * inv_temp; rows whose label equals ignore_index give loss 0 and a zero gradient row.
+//
+// Four families live here - the plain loss, the same with the live row count on the device, the label-smoothed captioning
+// loss, the validation counters - and all of them are built from ONE copy each of
+//   label_live   which labels take part
+//   row_walk     a 256-thread workgroup over one row: 16-byte groups of 8 columns where the rows are aligned, single columns behind
+//   row_lse      the online soft-max scan: lse of the row on thread 0, in the FAST (x * t, __expf, __logf) or the accurate
+//                (expf, logf) arithmetic, with the caller's hooks on the stored values (sum of x; arg-max)
+//   grad_row     the gradient row of an element functor (column, x) -> dx, padding columns zero, dx may alias x
+//   fold_tree    K sums over a workgroup's 256 partials in a fixed order, in the caller's accumulator type
 #include <math.h>
 #include "common.h"
 
@@ -37,82 +46,148 @@ template <> __device__ __forceinline__ void st8<float>(float* p, const float (&v
   *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
 }
 
-// (max, sum exp(x - max)) pairs combine associatively
-__device__ __forceinline__ void ms_merge(float& m, float& s, float m2, float s2) {
-  const float mx = fmaxf(m, m2);
-  s = s * __expf(m - mx) + s2 * __expf(m2 - mx);
-  m = mx;
+// ---- the shared pieces ----------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool label_live(long long y, long long ignore_index, int cols) { return !(y == ignore_index || y < 0 || y >= cols); }
+
+// One row, the whole 256-thread workgroup: f8(c) for every group of 8 columns below cols when the leading dimension(s), OR-ed
+// into `align`, allow 16-byte loads, then f1(c) for the single columns from there to `end` (cols, or ld to reach the padding).
+// A thread meets its columns in ascending order.
+__device__ __forceinline__ int row_vec_end(int align, int cols) { return ((align & 7) == 0) ? (cols & ~7) : 0; }
+template <class F8, class F1>
+__device__ __forceinline__ void row_walk(int align, int cols, int end, F8 f8, F1 f1) {
+  const int vec_end = row_vec_end(align, cols);
+  for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) f8(c);
+  for (int c = vec_end + threadIdx.x; c < end; c += 256) f1(c);
 }
 
-// One row, the whole 256-thread workgroup: thread 0 writes lse and the loss.  The one statement of the row arithmetic -
-// ce_fwd_kernel and ce_counted_fwd_kernel both call it, so their bits agree by construction.
-template <typename T>
-__device__ __forceinline__ void ce_row_fwd(const T* x, long long y, int cols, int ld, float t, long long ignore_index, float* lse_out,
-                                           float* loss_out, float (&sm)[4], float (&ss)[4]) {
+// The two arithmetics of the soft-max: FAST for the pre-training heads (scaled by inv_temp), accurate for the smoothed loss,
+// which is judged at a few 2^-24 (no scale: it has no temperature)
+template <bool FAST> __device__ __forceinline__ float sm_exp(float x) { return FAST ? __expf(x) : expf(x); }
+template <bool FAST> __device__ __forceinline__ float sm_log(float x) { return FAST ? __logf(x) : logf(x); }
+template <bool FAST> __device__ __forceinline__ float sm_scale(float v, float t) { return FAST ? v * t : v; }
+// (max, sum exp(x - max)) pairs combine associatively
+template <bool FAST> __device__ __forceinline__ void ms_merge(float& m, float& s, float m2, float s2) {
+  const float mx = fmaxf(m, m2);
+  s = s * sm_exp<FAST>(m - mx) + s2 * sm_exp<FAST>(m2 - mx);
+  m = mx;
+}
+struct NoHook { template <class... A> __device__ __forceinline__ void operator()(A&&...) const {} };
+
+// The online soft-max scan of one row: every thread's (max, sum exp) over its columns, folded over the wave (DPP) and the four
+// waves; returns lse = log sum_c exp(x_c * t) on thread 0 (0 elsewhere).  The ONE statement of this arithmetic: the plain, counted
+// and validation losses all call it, so their bits agree by construction.  h8(c, v[8]) / h1(c, v) see the stored values of the
+// columns the thread meets.  park(lane, wave) is called once by EVERY thread behind the walk and before the one __syncthreads:
+// there the caller folds what its hooks gathered over the wave (wave intrinsics are fine: no thread has left) and parks it
+// in LDS of its own, to read it on thread 0 after row_lse returns.
+template <bool FAST, typename T, class H8, class H1, class Park>
+__device__ __forceinline__ float row_lse(const T* x, int cols, int ld, float t, H8 h8, H1 h1, Park park) {
+  __shared__ float sm[4], ss[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float m = -3.0e38f, s = 0.f;
-  const int vec_end = ((ld & 7) == 0) ? (cols & ~7) : 0;              // 16-byte loads need aligned rows
-  for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
-    float v[8];
-    ld8<T>(x + c, v);
-    float mx = v[0] * t;
+  row_walk(
+      ld, cols, cols,
+      [&](int c) {
+        float v[8];
+        ld8<T>(x + c, v);
+        float mx = sm_scale<FAST>(v[0], t);
 #pragma unroll
-    for (int k = 1; k < 8; ++k) mx = fmaxf(mx, v[k] * t);
-    float e = 0.f;
+        for (int k = 1; k < 8; ++k) mx = fmaxf(mx, sm_scale<FAST>(v[k], t));
+        float e = 0.f;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) e += __expf(v[k] * t - mx);
-    ms_merge(m, s, mx, e);
-  }
-  for (int c = vec_end + threadIdx.x; c < cols; c += 256) ms_merge(m, s, ld1<T>(x + c) * t, 1.f);
-  // wave, then block
+        for (int k = 0; k < 8; ++k) e += sm_exp<FAST>(sm_scale<FAST>(v[k], t) - mx);
+        ms_merge<FAST>(m, s, mx, e);
+        h8(c, v);
+      },
+      [&](int c) {
+        const float v = ld1<T>(x + c);
+        ms_merge<FAST>(m, s, sm_scale<FAST>(v, t), 1.f);
+        h1(c, v);
+      });
   const float wm = wave_max(m);
-  s = wave_sum(s * __expf(m - wm));
+  s = wave_sum(s * sm_exp<FAST>(m - wm));
   if (lane == 0) { sm[wave] = wm; ss[wave] = s; }
+  park(lane, wave);
   __syncthreads();
+  float lse = 0.f;
   if (threadIdx.x == 0) {
     float M = sm[0], S = ss[0];
 #pragma unroll
-    for (int w = 1; w < 4; ++w) ms_merge(M, S, sm[w], ss[w]);
-    const float lse = M + __logf(S);
-    *lse_out = lse;
-    *loss_out = (y == ignore_index || y < 0 || y >= cols) ? 0.f : lse - ld1<T>(x + y) * t;
+    for (int w = 1; w < 4; ++w) ms_merge<FAST>(M, S, sm[w], ss[w]);
+    lse = M + sm_log<FAST>(S);
+  }
+  return lse;
+}
+
+// One gradient row dx[c] = f(c, x[c]) for c < cols and +0 in the padding; dx may alias x: a thread reads its columns before it
+// writes them
+template <typename T, class F>
+__device__ __forceinline__ void grad_row(const T* x, T* dx, int cols, int ld, F f) {
+  row_walk(
+      ld, cols, ld,
+      [&](int c) {
+        float v[8];
+        ld8<T>(x + c, v);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = f(c + k, v[k]);
+        st8<T>(dx + c, v);
+      },
+      [&](int c) {
+        float v = 0.f;
+        if (c < cols) v = f(c, ld1<T>(x + c));
+        st1<T>(dx + c, v);                                             // padding columns get a zero gradient
+      });
+}
+
+// K sums over one 256-thread workgroup in a fixed order: thread i brings the partial sums v of its rows i, i + 256, ... (added
+// in order), a halving tree adds the 256 partials; afterwards ps[k][0] is sum k, visible to every thread
+template <typename A, int K>
+__device__ __forceinline__ void fold_tree(A (&ps)[K][256], const A (&v)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) ps[k][threadIdx.x] = v[k];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) ps[k][threadIdx.x] += ps[k][threadIdx.x + w];
+    }
+    __syncthreads();
   }
 }
 
-// One gradient row with upstream g (already times inv_temp); dx may alias x: a thread reads its columns before it writes them
+// ---- the plain loss ---------------------------------------------------------------------------------------------------
+// thread 0 writes lse and the loss of one row
+template <typename T>
+__device__ __forceinline__ void ce_row_fwd(const T* x, long long y, int cols, int ld, float t, long long ignore_index, float* lse_out,
+                                           float* loss_out) {
+  const float lse = row_lse<true, T>(x, cols, ld, t, NoHook(), NoHook(), NoHook());
+  if (threadIdx.x == 0) {
+    *lse_out = lse;
+    *loss_out = label_live(y, ignore_index, cols) ? lse - ld1<T>(x + y) * t : 0.f;
+  }
+}
+
+// one gradient row with upstream g (already times inv_temp)
 template <typename T>
 __device__ __forceinline__ void ce_row_bwd(const T* x, T* dx, long long y, int cols, int ld, float t, float lse, float g) {
-  const int vec_end = ((ld & 7) == 0) ? (cols & ~7) : 0;
-  for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
-    float v[8];
-    ld8<T>(x + c, v);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = (__expf(v[k] * t - lse) - ((long long)(c + k) == y ? 1.f : 0.f)) * g;
-    st8<T>(dx + c, v);
-  }
-  for (int c = vec_end + threadIdx.x; c < ld; c += 256) {
-    float v = 0.f;
-    if (c < cols) v = (__expf(ld1<T>(x + c) * t - lse) - ((long long)c == y ? 1.f : 0.f)) * g;
-    st1<T>(dx + c, v);                                               // padding columns get a zero gradient
-  }
+  grad_row<T>(x, dx, cols, ld, [=](int c, float v) { return (sm_exp<true>(v * t - lse) - ((long long)c == y ? 1.f : 0.f)) * g; });
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(HeroCrossEntropy a) {
-  __shared__ float sm[4], ss[4];
   const int row = blockIdx.x;
   ce_row_fwd<T>(static_cast<const T*>(a.logits) + (size_t)row * a.ld, a.labels[row], a.cols, a.ld, a.inv_temp, a.ignore_index, a.lse + row,
-                a.loss + row, sm, ss);
+                a.loss + row);
 }
 
+// a dead row is multiplied by g = 0, not skipped: -0 under a label inside [0, cols) that equals ignore_index, NaN from a
+// non-finite logit (ce_counted_bwd_kernel writes +0 and reads nothing)
 template <typename T>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(HeroCrossEntropy a) {
   const int row = blockIdx.x;
   const long long y = a.labels[row];
-  const bool live = !(y == a.ignore_index || y < 0 || y >= a.cols);
   const float t = a.inv_temp;
   ce_row_bwd<T>(static_cast<const T*>(a.logits) + (size_t)row * a.ld, static_cast<T*>(a.dlogits) + (size_t)row * a.ld, y, a.cols, a.ld, t,
-                a.lse[row], live ? a.dloss[row] * t : 0.f);
+                a.lse[row], label_live(y, a.ignore_index, a.cols) ? a.dloss[row] * t : 0.f);
 }
 
 // ---- the same loss with the LIVE ROW COUNT ON THE DEVICE (fixed-capacity pre-training heads under graph replay) ------
@@ -137,32 +212,23 @@ __device__ __forceinline__ int ce_live_rows(const CeCounted& a) { return a.count
 
 template <typename T>
 __global__ __launch_bounds__(256) void ce_counted_fwd_kernel(CeCounted a) {
-  __shared__ float sm[4], ss[4];
   const int row = blockIdx.x;
   if (row >= ce_live_rows(a)) {                                       // uniform over the workgroup
     if (threadIdx.x == 0) { a.loss[row] = 0.f; a.lse[row] = 0.f; }
     return;
   }
   ce_row_fwd<T>(static_cast<const T*>(a.logits) + (size_t)row * a.ld, a.labels[row], a.cols, a.ld, a.inv_temp, a.ignore_index, a.lse + row,
-                a.loss + row, sm, ss);
+                a.loss + row);
 }
 
-// thread i adds rows i, i + 256, ... in order, then a fixed tree (eval_fold_kernel's pattern); rows == 0 gives (0, 0)
+// rows == 0 gives (0, 0)
 __global__ __launch_bounds__(256) void ce_counted_fold_kernel(CeCounted a) {
   __shared__ double ps[2][256];
   const int n = ce_live_rows(a);
-  double s = 0.0, c = 0.0;
-  for (int r = threadIdx.x; r < n; r += 256) {
-    const long long y = a.labels[r];
-    if (!(y == a.ignore_index || y < 0 || y >= a.cols)) { s += (double)a.loss[r]; c += 1.0; }
-  }
-  ps[0][threadIdx.x] = s;
-  ps[1][threadIdx.x] = c;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) { ps[0][threadIdx.x] += ps[0][threadIdx.x + w]; ps[1][threadIdx.x] += ps[1][threadIdx.x + w]; }
-    __syncthreads();
-  }
+  double v[2] = {0.0, 0.0};
+  for (int r = threadIdx.x; r < n; r += 256)
+    if (label_live(a.labels[r], a.ignore_index, a.cols)) { v[0] += (double)a.loss[r]; v[1] += 1.0; }
+  fold_tree(ps, v);
   if (threadIdx.x == 0) {
     const double live = ps[1][0];
     a.mean_cnt[0] = (float)(ps[0][0] / (live > 1.0 ? live : 1.0));
@@ -178,13 +244,11 @@ __global__ __launch_bounds__(256) void ce_counted_bwd_kernel(CeCounted a) {
   long long y = -1;
   if (live) {
     y = a.labels[row];
-    live = !(y == a.ignore_index || y < 0 || y >= a.cols);
+    live = label_live(y, a.ignore_index, a.cols);
   }
   if (!live) {                                                        // +0 over all ld columns, nothing read
     const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const int vec_end = ((a.ld & 7) == 0) ? a.ld : 0;
-    for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) st8<T>(dx + c, z);
-    for (int c = vec_end + threadIdx.x; c < a.ld; c += 256) st1<T>(dx + c, 0.f);
+    row_walk(a.ld, a.ld, a.ld, [&](int c) { st8<T>(dx + c, z); }, [&](int c) { st1<T>(dx + c, 0.f); });
     return;
   }
   const float t = a.inv_temp, g = a.dloss[0] / fmaxf(a.mean_cnt[1], 1.f);
@@ -195,7 +259,7 @@ __global__ __launch_bounds__(256) void ce_counted_bwd_kernel(CeCounted a) {
 // KL(smoothed one-hot || softmax(x)) of a row with label t, C = cols, s = eps / (C - 1), conf = 1 - eps, in closed form:
 //   loss = H0 - (conf - s) (x_t - lse) - s (sum_c x_c - C lse),   H0 = conf ln conf + (C - 1) s ln s   (0 ln 0 = 0)
 //   dx_c = (softmax(x)_c - s - (conf - s) [c == t]) * upstream
-// so no [rows, C] target matrix exists.  Forward: one pass over the row (online max / sum of exponentials as above, plus
+// so no [rows, C] target matrix exists.  Forward: one pass over the row (row_lse in the accurate arithmetic, its hook adding
 // sum_c x_c in fp32), then ONE workgroup folds the row losses and counts the valid rows in a fixed order into a device pair.
 // Backward: upstream is a device scalar (times an optional per-row factor); in mean mode it is divided by the valid count
 // read from that pair - no host synchronisation.  Zero valid rows: loss 0, zero gradients.
@@ -210,52 +274,25 @@ struct SmoothCe {
   double cms, s, h0;                                  // conf - s, s, H0
 };
 
-// ms_merge with the accurate exponential: the loss is judged at a few 2^-24
-__device__ __forceinline__ void ms_merge_acc(float& m, float& s, float m2, float s2) {
-  const float mx = fmaxf(m, m2);
-  s = s * expf(m - mx) + s2 * expf(m2 - mx);
-  m = mx;
-}
 __device__ __forceinline__ float sum8(const float (&v)[8]) { return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7])); }
 
 template <typename T>
 __global__ __launch_bounds__(256) void smooth_ce_fwd_kernel(SmoothCe a) {
-  __shared__ float sm[4], ss[4], sx[4];
-  const int row = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ float sx[4];
+  const int row = blockIdx.x;
   const T* x = static_cast<const T*>(a.logits) + (size_t)row * a.ld;
-  float m = -3.0e38f, s = 0.f, tot = 0.f;
-  const int vec_end = ((a.ld & 7) == 0) ? (a.cols & ~7) : 0;
-  for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
-    float v[8];
-    ld8<T>(x + c, v);
-    float mx = v[0];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) mx = fmaxf(mx, v[k]);
-    float e = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) e += expf(v[k] - mx);
-    ms_merge_acc(m, s, mx, e);
-    tot += sum8(v);
-  }
-  for (int c = vec_end + threadIdx.x; c < a.cols; c += 256) {
-    const float v = ld1<T>(x + c);
-    ms_merge_acc(m, s, v, 1.f);
-    tot += v;
-  }
-  const float wm = wave_max(m);
-  s = wave_sum(s * expf(m - wm));
-  tot = wave_sum(tot);
-  if (lane == 0) { sm[wave] = wm; ss[wave] = s; sx[wave] = tot; }
-  __syncthreads();
+  float tot = 0.f;
+  const float lse = row_lse<false, T>(
+      x, a.cols, a.ld, 1.f, [&](int, const float (&v)[8]) { tot += sum8(v); }, [&](int, float v) { tot += v; },
+      [&](int lane, int wave) {
+        tot = wave_sum(tot);
+        if (lane == 0) sx[wave] = tot;
+      });
   if (threadIdx.x == 0) {
-    float M = sm[0], S = ss[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) ms_merge_acc(M, S, sm[w], ss[w]);
-    const float lse = M + logf(S);
     const long long y = a.labels[row];
     a.lse[row] = lse;
     float loss = 0.f;
-    if (!(y == a.ignore_index || y < 0 || y >= a.cols)) {
+    if (label_live(y, a.ignore_index, a.cols)) {
       const double all = ((double)sx[0] + (double)sx[1]) + ((double)sx[2] + (double)sx[3]) - (double)a.cols * (double)lse;
       loss = (float)(a.h0 - a.cms * ((double)ld1<T>(x + y) - (double)lse) - a.s * all);
     }
@@ -263,31 +300,21 @@ __global__ __launch_bounds__(256) void smooth_ce_fwd_kernel(SmoothCe a) {
   }
 }
 
-// sum_cnt = (sum of the row losses, number of valid rows): one workgroup, strided partial sums, a fixed tree
+// sum_cnt = (sum of the row losses, number of valid rows), in fp32
 __global__ __launch_bounds__(256) void smooth_ce_fold_kernel(SmoothCe a) {
-  __shared__ float ps[256], pc[256];
-  float s = 0.f, c = 0.f;
-  for (int r = threadIdx.x; r < a.rows; r += 256) {
-    const long long y = a.labels[r];
-    if (!(y == a.ignore_index || y < 0 || y >= a.cols)) { s += a.loss[r]; c += 1.f; }
-  }
-  ps[threadIdx.x] = s;
-  pc[threadIdx.x] = c;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) { ps[threadIdx.x] += ps[threadIdx.x + w]; pc[threadIdx.x] += pc[threadIdx.x + w]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { a.sum_cnt[0] = ps[0]; a.sum_cnt[1] = pc[0]; }
+  __shared__ float ps[2][256];
+  float v[2] = {0.f, 0.f};
+  for (int r = threadIdx.x; r < a.rows; r += 256)
+    if (label_live(a.labels[r], a.ignore_index, a.cols)) { v[0] += a.loss[r]; v[1] += 1.f; }
+  fold_tree(ps, v);
+  if (threadIdx.x == 0) { a.sum_cnt[0] = ps[0][0]; a.sum_cnt[1] = ps[1][0]; }
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void smooth_ce_bwd_kernel(SmoothCe a) {
   const int row = blockIdx.x;
-  const T* x = static_cast<const T*>(a.logits) + (size_t)row * a.ld;
-  T* dx = static_cast<T*>(a.dlogits) + (size_t)row * a.ld;
   const long long y = a.labels[row];
-  const bool live = !(y == a.ignore_index || y < 0 || y >= a.cols);
+  const bool live = label_live(y, a.ignore_index, a.cols);
   const float lse = a.lse[row];
   float g = 0.f;
   if (live) {
@@ -296,83 +323,59 @@ __global__ __launch_bounds__(256) void smooth_ce_bwd_kernel(SmoothCe a) {
     if (a.mean_cnt) g /= fmaxf(a.mean_cnt[1], 1.f);
   }
   const float s = (float)a.s, cms = (float)a.cms;
-  const int vec_end = ((a.ld & 7) == 0) ? (a.cols & ~7) : 0;
-  for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
-    float v[8];
-    ld8<T>(x + c, v);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = live ? ((expf(v[k] - lse) - s) - ((long long)(c + k) == y ? cms : 0.f)) * g : 0.f;
-    st8<T>(dx + c, v);
-  }
-  for (int c = vec_end + threadIdx.x; c < a.ld; c += 256) {
-    float v = 0.f;
-    if (live && c < a.cols) v = ((expf(ld1<T>(x + c) - lse) - s) - ((long long)c == y ? cms : 0.f)) * g;
-    st1<T>(dx + c, v);                                               // padding columns get a zero gradient
-  }
+  grad_row<T>(static_cast<const T*>(a.logits) + (size_t)row * a.ld, static_cast<T*>(a.dlogits) + (size_t)row * a.ld, a.cols, a.ld,
+              [=](int c, float v) { return live ? ((sm_exp<false>(v - lse) - s) - ((long long)c == y ? cms : 0.f)) * g : 0.f; });
 }
 
 // ---- validation counters of the pre-training heads (pretrain.py:462-608) --------------------------------------------
 // One pass over the raw logits gives what validate_mlm / validate_mfm_nce / validate_fom take from F.cross_entropy(sum) and
-// scores.max(-1): the row loss (the arithmetic of ce_fwd_kernel, statement for statement) and the arg-max of the STORED
-// values, lowest column first among equal maxima.  Row results go to a workspace; one workgroup folds them into float64
-// counters in a fixed order (no atomics: two runs give the same bits).
+// scores.max(-1): the row loss (row_lse in the FAST arithmetic, the call ce_fwd_kernel makes) and, from its hooks, the arg-max
+// of the STORED values, lowest column first among equal maxima.  Row results go to a workspace; one workgroup folds them into
+// float64 counters in a fixed order (no atomics: two runs give the same bits).
 template <typename T>
 __global__ __launch_bounds__(256) void ce_eval_kernel(const T* logits, const long long* labels, int cols, int ld, float t, long long ignore_index,
                                                       float* row_loss, float* row_hit, float* row_valid, int32_t* pred) {
-  __shared__ float sm[4], ss[4];
   __shared__ unsigned long long sb[4];
-  const int row = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = blockIdx.x;
   const T* x = logits + (size_t)row * ld;
-  float m = -3.0e38f, s = 0.f;
   float bv = -INFINITY;                                               // a thread meets its columns in ascending order, so a
   int bi = 0x7fffffff;                                                // strict > keeps the first of equal values
-  const int vec_end = ((ld & 7) == 0) ? (cols & ~7) : 0;
-  for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
-    float v[8];
-    ld8<T>(x + c, v);
-    float mx = v[0] * t;
+  const float lse = row_lse<true, T>(
+      x, cols, ld, t,
+      [&](int c, const float (&v)[8]) {
+        float b = bv;                                                 // local copies: updating bv through the reference eight times
+        int i = bi;                                                   // made the compiler carry a second copy of it round the loop
 #pragma unroll
-    for (int k = 1; k < 8; ++k) mx = fmaxf(mx, v[k] * t);
-    float e = 0.f;
+        for (int k = 0; k < 8; ++k)
+          if (v[k] > b) { b = v[k]; i = c + k; }
+        bv = b;
+        bi = i;
+      },
+      [&](int c, float v) {
+        if (v > bv) { bv = v; bi = c; }
+      },
+      [&](int lane, int wave) {
+        if (bi == 0x7fffffff) {                                       // nothing above -inf: the thread's first column, if it has one
+          const int vec_end = row_vec_end(ld, cols);
+          const int first = ((int)threadIdx.x * 8 < vec_end) ? (int)threadIdx.x * 8 : vec_end + (int)threadIdx.x;
+          if (first < cols) bi = first;
+        }
+        // larger composite = larger value, then lower column (-0 and +0 tie): the maximum over the row is the prediction
+        unsigned long long best = compose(order_bits(bv), (uint32_t)bi);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) e += __expf(v[k] * t - mx);
-    ms_merge(m, s, mx, e);
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      if (v[k] > bv) { bv = v[k]; bi = c + k; }
-  }
-  for (int c = vec_end + threadIdx.x; c < cols; c += 256) {
-    const float v = ld1<T>(x + c);
-    ms_merge(m, s, v * t, 1.f);
-    if (v > bv) { bv = v; bi = c; }
-  }
-  if (bi == 0x7fffffff) {                                             // nothing above -inf: the thread's first column, if it has one
-    const int first = ((int)threadIdx.x * 8 < vec_end) ? (int)threadIdx.x * 8 : vec_end + (int)threadIdx.x;
-    if (first < cols) bi = first;
-  }
-  // larger composite = larger value, then lower column (-0 and +0 tie): the maximum over the row is the prediction
-  unsigned long long best = compose(order_bits(bv), (uint32_t)bi);
-#pragma unroll
-  for (int w = 32; w > 0; w >>= 1) {
-    const unsigned long long o = __shfl_xor(best, w, 64);
-    best = o > best ? o : best;
-  }
-  const float wm = wave_max(m);
-  s = wave_sum(s * __expf(m - wm));
-  if (lane == 0) { sm[wave] = wm; ss[wave] = s; sb[wave] = best; }
-  __syncthreads();
+        for (int w = 32; w > 0; w >>= 1) {
+          const unsigned long long o = __shfl_xor(best, w, 64);
+          best = o > best ? o : best;
+        }
+        if (lane == 0) sb[wave] = best;
+      });
   if (threadIdx.x == 0) {
-    float M = sm[0], S = ss[0];
     unsigned long long B = sb[0];
 #pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      ms_merge(M, S, sm[w], ss[w]);
-      B = sb[w] > B ? sb[w] : B;
-    }
-    const float lse = M + __logf(S);
+    for (int w = 1; w < 4; ++w) B = sb[w] > B ? sb[w] : B;
     const int p = (int)~(uint32_t)B;
     const long long y = labels[row];
-    const bool live = !(y == ignore_index || y < 0 || y >= cols);
+    const bool live = label_live(y, ignore_index, cols);
     row_loss[row] = live ? lse - ld1<T>(x + y) * t : 0.f;
     row_hit[row] = (live && (long long)p == y) ? 1.f : 0.f;
     row_valid[row] = live ? 1.f : 0.f;
@@ -390,21 +393,20 @@ __global__ __launch_bounds__(256) void feat_eval_kernel(const T* pred, const T* 
   const T* p = pred + (size_t)row * ld_p;
   const T* g = target + (size_t)row * ld_t;
   float dd = 0.f, pg = 0.f, pp = 0.f, gg = 0.f;
-  const int vec_end = (((ld_p | ld_t) & 7) == 0) ? (cols & ~7) : 0;
-  for (int c = threadIdx.x * 8; c < vec_end; c += 256 * 8) {
-    float a[8], b[8];
-    ld8<T>(p + c, a);
-    ld8<T>(g + c, b);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float d = a[k] - b[k];
-      dd += d * d; pg += a[k] * b[k]; pp += a[k] * a[k]; gg += b[k] * b[k];
-    }
-  }
-  for (int c = vec_end + threadIdx.x; c < cols; c += 256) {
-    const float a = ld1<T>(p + c), b = ld1<T>(g + c), d = a - b;
+  const auto add = [&](float a, float b) {
+    const float d = a - b;
     dd += d * d; pg += a * b; pp += a * a; gg += b * b;
-  }
+  };
+  row_walk(
+      ld_p | ld_t, cols, cols,
+      [&](int c) {
+        float a[8], b[8];
+        ld8<T>(p + c, a);
+        ld8<T>(g + c, b);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) add(a[k], b[k]);
+      },
+      [&](int c) { add(ld1<T>(p + c), ld1<T>(g + c)); });
   dd = wave_sum(dd); pg = wave_sum(pg); pp = wave_sum(pp); gg = wave_sum(gg);
   if (lane == 0) { sq[0][wave] = dd; sq[1][wave] = pg; sq[2][wave] = pp; sq[3][wave] = gg; }
   __syncthreads();
@@ -417,26 +419,24 @@ __global__ __launch_bounds__(256) void feat_eval_kernel(const T* pred, const T* 
   }
 }
 
-// acc[0..2] += (sum a, sum b, sum c) in float64 (c == nullptr: the row count): one workgroup, thread i adds rows i, i + 256,
-// ... in order, then a fixed tree
+// acc[0..2] += (sum a, sum b, sum c) in float64 (c == nullptr: the row count)
 __global__ __launch_bounds__(256) void eval_fold_kernel(const float* a, const float* b, const float* c, int rows, double* acc) {
   __shared__ double ps[3][256];
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  double v[3] = {0.0, 0.0, 0.0};
   for (int r = threadIdx.x; r < rows; r += 256) {
-    s0 += (double)a[r];
-    s1 += (double)b[r];
-    s2 += c ? (double)c[r] : 1.0;
+    v[0] += (double)a[r];
+    v[1] += (double)b[r];
+    v[2] += c ? (double)c[r] : 1.0;
   }
-  ps[0][threadIdx.x] = s0; ps[1][threadIdx.x] = s1; ps[2][threadIdx.x] = s2;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) ps[k][threadIdx.x] += ps[k][threadIdx.x + w];
-    }
-    __syncthreads();
-  }
+  fold_tree(ps, v);
   if (threadIdx.x < 3) acc[threadIdx.x] += ps[threadIdx.x][0];
+}
+
+// the dims check, then the dtype check: adjacent and in this order in six entries; min_cols is 2 for the smoothed pair, else 1
+static int check_shape(const char* what, int rows, int cols, int ld, int min_cols, int dtype) {
+  HERO_REQUIRE(rows >= 0 && cols >= min_cols && ld >= cols, "%s: bad dims rows=%d cols=%d ld=%d", what, rows, cols, ld);
+  HERO_REQUIRE(dtype == HERO_F32 || dtype == HERO_BF16, "%s: bad dtype %d", what, dtype);
+  return HERO_OK;
 }
 
 }  // namespace
@@ -446,8 +446,7 @@ using namespace hero;
 
 extern "C" int hero_ce_eval(const void* logits, const long long* labels, int rows, int cols, int ld, int dtype, float inv_temp,
                             long long ignore_index, double* acc, int32_t* pred, void* workspace, hero_stream_t stream) {
-  HERO_REQUIRE(rows >= 0 && cols > 0 && ld >= cols, "hero_ce_eval: bad dims rows=%d cols=%d ld=%d", rows, cols, ld);
-  HERO_REQUIRE(dtype == HERO_F32 || dtype == HERO_BF16, "hero_ce_eval: bad dtype %d", dtype);
+  if (const int rc = check_shape("hero_ce_eval", rows, cols, ld, 1, dtype)) return rc;
   HERO_REQUIRE(inv_temp > 0.f, "hero_ce_eval: inv_temp must be positive, got %g", (double)inv_temp);
   if (rows == 0) return HERO_OK;
   HERO_REQUIRE(logits && labels && acc && workspace, "hero_ce_eval: null pointer");
@@ -489,8 +488,7 @@ extern "C" int hero_feat_eval(const void* pred, const void* target, int rows, in
 
 static int check_ce(const HeroCrossEntropy* a, bool bwd) {
   HERO_REQUIRE(a && a->logits && a->labels && a->lse, "hero_cross_entropy: null pointer");
-  HERO_REQUIRE(a->rows >= 0 && a->cols > 0 && a->ld >= a->cols, "hero_cross_entropy: bad dims rows=%d cols=%d ld=%d", a->rows, a->cols, a->ld);
-  HERO_REQUIRE(a->dtype == HERO_F32 || a->dtype == HERO_BF16, "hero_cross_entropy: bad dtype %d", a->dtype);
+  if (const int rc = check_shape("hero_cross_entropy", a->rows, a->cols, a->ld, 1, a->dtype)) return rc;
   HERO_REQUIRE((((uintptr_t)a->logits) & 15) == 0, "hero_cross_entropy: logits must be 16-byte aligned");
   if (bwd) HERO_REQUIRE(a->dloss && a->dlogits && (((uintptr_t)a->dlogits) & 15) == 0, "hero_cross_entropy_bwd: dloss / dlogits required (16-byte aligned)");
   else HERO_REQUIRE(a->loss, "hero_cross_entropy_fwd: loss required");
@@ -517,8 +515,7 @@ extern "C" int hero_cross_entropy_bwd(const HeroCrossEntropy* a, hero_stream_t s
 
 static int check_counted(const char* what, const void* logits, const long long* labels, const float* lse, const float* mean_cnt, int rows,
                          int cols, int ld, int dtype, float inv_temp) {
-  HERO_REQUIRE(rows >= 0 && cols > 0 && ld >= cols, "%s: bad dims rows=%d cols=%d ld=%d", what, rows, cols, ld);
-  HERO_REQUIRE(dtype == HERO_F32 || dtype == HERO_BF16, "%s: bad dtype %d", what, dtype);
+  if (const int rc = check_shape(what, rows, cols, ld, 1, dtype)) return rc;
   HERO_REQUIRE(inv_temp > 0.f, "%s: inv_temp must be positive, got %g", what, (double)inv_temp);
   HERO_REQUIRE(mean_cnt && (((uintptr_t)mean_cnt) & 3) == 0, "%s: mean_cnt required (4-byte aligned)", what);
   if (rows == 0) return HERO_OK;
@@ -533,10 +530,7 @@ extern "C" int hero_ce_counted_fwd(const void* logits, const long long* labels, 
   HERO_REQUIRE(rows == 0 || loss, "hero_ce_counted_fwd: loss required");
   const CeCounted a = {logits, labels, count, loss, lse, mean_cnt, nullptr, nullptr, rows, cols, ld, inv_temp, ignore_index};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (rows > 0) {
-    if (dtype == HERO_BF16) hipLaunchKernelGGL(ce_counted_fwd_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(ce_counted_fwd_kernel<float>, dim3(rows), dim3(256), 0, s, a);
-  }
+  if (rows > 0) with_dtype(dtype, [&](auto tag) { hipLaunchKernelGGL(ce_counted_fwd_kernel<typename decltype(tag)::type>, dim3(rows), dim3(256), 0, s, a); });
   hipLaunchKernelGGL(ce_counted_fold_kernel, dim3(1), dim3(256), 0, s, a);    // rows == 0: the pair is (0, 0)
   return check_launch("hero_ce_counted_fwd");
 }
@@ -557,8 +551,7 @@ extern "C" int hero_ce_counted_bwd(const void* logits, const long long* labels, 
 static int check_smooth(const char* what, const void* logits, const long long* labels, const float* lse, int rows, int cols, int ld, int dtype,
                         double eps) {
   HERO_REQUIRE(logits && labels && lse, "%s: null pointer", what);
-  HERO_REQUIRE(rows >= 0 && cols >= 2 && ld >= cols, "%s: bad dims rows=%d cols=%d ld=%d", what, rows, cols, ld);
-  HERO_REQUIRE(dtype == HERO_F32 || dtype == HERO_BF16, "%s: bad dtype %d", what, dtype);
+  if (const int rc = check_shape(what, rows, cols, ld, 2, dtype)) return rc;
   HERO_REQUIRE(eps > 0.0 && eps <= 1.0, "%s: smoothing must be in (0, 1], got %g", what, eps);
   HERO_REQUIRE((((uintptr_t)logits) & 15) == 0, "%s: logits must be 16-byte aligned", what);
   return HERO_OK;
@@ -578,10 +571,7 @@ extern "C" int hero_smooth_ce_fwd(const void* logits, const long long* labels, f
   SmoothCe a = {logits, labels, loss, lse, sum_cnt, nullptr, nullptr, nullptr, nullptr, rows, cols, ld, ignore_index, 0.0, 0.0, 0.0};
   smooth_consts(a, eps);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (rows > 0) {
-    if (dtype == HERO_BF16) hipLaunchKernelGGL(smooth_ce_fwd_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(smooth_ce_fwd_kernel<float>, dim3(rows), dim3(256), 0, s, a);
-  }
+  if (rows > 0) with_dtype(dtype, [&](auto tag) { hipLaunchKernelGGL(smooth_ce_fwd_kernel<typename decltype(tag)::type>, dim3(rows), dim3(256), 0, s, a); });
   hipLaunchKernelGGL(smooth_ce_fold_kernel, dim3(1), dim3(256), 0, s, a);     // rows == 0: the pair is (0, 0)
   return check_launch("hero_smooth_ce_fwd");
 }

@@ -150,6 +150,46 @@ def test_ce_eval_captured_in_a_graph():
     assert torch.equal(acc.cpu(), 2 * eager) and eager[2].item() == _ce_want(shape, 1.0)[0][2]
 
 
+def _fold_f64(rows_f32):
+    """The fold's documented order in float64: thread i adds rows i, i + 256, ... in order, then the halving tree w = 128 ... 1."""
+    part = np.zeros(256, dtype=np.float64)
+    for r, v in enumerate(np.asarray(rows_f32, dtype=np.float64)):
+        part[r % 256] += v
+    w = 128
+    while w:
+        part[:w] += part[w:2 * w]
+        w >>= 1
+    return part[0]
+
+
+@pytest.mark.parametrize("shape", [(5, 7, 7), (5, 37, 40), (300, 2051, 2056), (5, 4101, 4104)], ids=str)
+@pytest.mark.parametrize("dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("inv_temp", [1.0, 0.7])
+def test_ce_eval_loss_is_the_training_loss_bit_for_bit(shape, dtype, inv_temp):
+    """hero_ce_eval and hero_cross_entropy_fwd share one row scan: the loss counter is the float64 sum, in the fold's order, of the
+    training kernel's per-row losses - the same int64 bit pattern - and the valid count is the number of live labels."""
+    import ctypes as C
+    from hero_amd import _lib as L
+    from hero_amd import pretrain_eval as E
+    rows, cols, ld = shape
+    x, y = _ce_case(shape)
+    y = y.copy()
+    y[3], y[4] = R.CE_IGNORE, cols                                    # some ignored labels at every shape
+    logits, labels = torch.from_numpy(x.copy()).cuda().to(dtype), torch.from_numpy(y).cuda()
+    loss = torch.full((rows,), SENTINEL, dtype=torch.float32, device="cuda")
+    lse = torch.empty((rows,), dtype=torch.float32, device="cuda")
+    a = L.CrossEntropy(L.ptr(logits), L.ptr(labels), L.ptr(loss), L.ptr(lse), None, None, rows, cols, ld, L.dt(logits), inv_temp, R.CE_IGNORE)
+    L.check(L.lib().hero_cross_entropy_fwd(C.byref(a), L.stream()))
+    acc = E.ce_eval(logits, labels, ncols=cols, ignore_index=R.CE_IGNORE, inv_temp=inv_temp).cpu()
+    live = (y != R.CE_IGNORE) & (y >= 0) & (y < cols)
+    row_loss = loss.cpu().numpy()
+    assert (row_loss[~live] == 0.0).all() and 0 < live.sum() < rows
+    want = np.array([_fold_f64(row_loss)])
+    print("ce_eval against cross_entropy_fwd", shape, dtype, inv_temp, "counter", acc[0].item(), "fold of the row losses", want[0])
+    assert acc[:1].view(torch.int64).item() == want.view(np.int64)[0]
+    assert acc[2].item() == live.sum()
+
+
 # ---- hero_feat_eval ----------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _feat(rows, cols):
