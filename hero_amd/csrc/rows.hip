@@ -103,7 +103,9 @@ __global__ __launch_bounds__(SORT_NT) void segment_sort_kernel(const int32_t* __
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int cpt = (rows + SORT_NT - 1) / SORT_NT;
   const int beg = min(t * cpt, rows), end = min(beg + cpt, rows);
-  const uint32_t last_key = (1u << nbits) - 1u;      // dropped rows (idx < 0 or == skip) sort behind every real destination
+  // dropped rows (idx < 0 or == skip) sort behind every real destination: the all-ones key of nbits bits (n_dst >= 2^28 gives
+  // nbits = 32, where 1u << nbits is no longer defined - the hardware shifts by nbits & 31 = 0 and the key came out as 0)
+  const uint32_t last_key = nbits >= 32 ? 0xffffffffu : (1u << nbits) - 1u;
   for (int i = beg; i < end; ++i) {
     const int v = idx[i];
     buf0[i] = make_uint2((v < 0 || v == skip) ? last_key : (uint32_t)v, (uint32_t)i);
